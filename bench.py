@@ -2,7 +2,7 @@
 """
 bench.py -- headline benchmark of the MI355X hot path (driver contract).
 
-  python bench.py --gpus N --steps K --warmup W          (N>1: under torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]     (N>1: under torch.distributed.run)
 
 Primary line (BASELINE.json configs[1], "2D slices/sec (train)"):
   one step = one Keras-equivalent train step (forward with batch-stat BN, sparse
@@ -10,7 +10,22 @@ Primary line (BASELINE.json configs[1], "2D slices/sec (train)"):
   of the depth-4 / 64-filter U-Net on a batch of 16 bf16 128x128x1 slices per
   GPU, inputs resident in HBM. value = N*16*K / max-over-ranks time.
 
-Added objects:
+A plain run sets up and runs the W warm-up steps. At N=1 it then captures the
+step as a HIP graph and, without --graph / --no-graph, times graph replay
+against eager launches over 4 x max(10, W) further steps to pick the faster
+mode; the training state the warm-up left is put back after that. It then
+times the K steps and prints the line. Everything else it measures or
+checks runs only with --full: the loss guard, per-step event times, the kernel
+schedules of one step, and the objects below.
+
+--dump-outputs DIR: after the timed region, what its last step computed, as
+DIR/<name>.npy (float32 / float64, under 64 MB in all). Train configurations:
+the updated parameters and the step's gradient (sampled), BatchNorm state,
+class probabilities and mean loss -- the state after W + K train steps from the
+seeded initialisation, whichever launch mode ran them. Predict configurations:
+the fused label volume of the last timed run (sampled above 4 Mi voxels).
+
+Added objects (--full):
   roofline     : the dominant kernel (conv_igemm: forward + data-gradient MFMA
                  convolutions), algorithmic FLOPs / HIP-event kernel time measured
                  inside the timed region on the launch stream, vs 2.5 PFLOP/s dense bf16.
@@ -93,7 +108,13 @@ def main():
     ap.add_argument("--cf", type=float, default=1.0, help="complexity_factor of the train-leg network (2 = the default project YAML)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the train_e2e (sampler -> step pipeline) and f32_mode legs")
     ap.add_argument("--e2e-only", action="store_true", help="only the train_e2e leg (dev aid: prints its JSON object)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline figure (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step (train) or run (predict+fuse) computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.e2e_only:
+        ap.error("--dump-outputs does not cover --e2e-only")
 
     from multiplanarunet_amd import distributed as D
     from multiplanarunet_amd import _lib
@@ -113,9 +134,10 @@ def main():
         pD = args.predict_dim
     if args.predict_only or args.config in (2, 4):
         if world == 1:
-            res = bench_predict(device, quiet, D=pD, K=pK, C=pC)
+            res = bench_predict(device, quiet, D=pD, K=pK, C=pC, dump=args.dump_outputs)
         else:
-            res = bench_predict_sharded(device, quiet, rank, world, args.exchange, D=pD, K=pK, C=pC)
+            res = bench_predict_sharded(device, quiet, rank, world, args.exchange, D=pD, K=pK, C=pC,
+                                        dump=args.dump_outputs if rank == 0 else None)
         if rank == 0:
             if args.predict_only:
                 print(json.dumps({"predict_fuse": res}), flush=True)
@@ -175,8 +197,8 @@ def main():
         head = B * args.steps / (time.perf_counter() - t0)
         print(json.dumps({"headline_slices_per_s": round(head, 1), "train_e2e": bench_train_e2e(model, device, B, dim, headline=head)}), flush=True)
         return
-    loss_first = current_loss()
-    events = not args.no_kernel_events
+    loss_first = current_loss() if args.full else None
+    events = args.full and not args.no_kernel_events
     # N=1: the whole step (fwd + bwd + Adam + repack, ~260 launches) is replayed from one HIP graph; the
     # per-launch HIP events of the roofline leg need eager launches, so they are taken over a second region
     # of the same K steps right after (same kernels, same arguments). N>1 keeps eager launches (RCCL between).
@@ -184,6 +206,12 @@ def main():
     dt_eager = None
     launch_cal = None
     if graphed:
+        # The capture's warm-up step, the replay below and the launch calibration train the model too, and the graph's Adam
+        # step counter moves only on replays. The training state the W warm-up steps left is put back afterwards, so the
+        # timed steps (and --dump-outputs) compute the same in either launch mode.
+        model._ensure_adam()
+        state = (model.params, model._adam_m, model._adam_v, model.bn_state, model.packed)
+        saved, saved_iterations = [t.clone() for t in state], model.iterations
         replay = model.make_graphed_train_step(x, y, sw)
         replay()
         run = replay
@@ -205,6 +233,14 @@ def main():
             launch_cal = {k: round(min(v), 4) for k, v in cal.items()}
             if launch_cal["eager"] < launch_cal["graph"]:
                 graphed, run = False, step
+        for t, v in zip(state, saved):
+            t.copy_(v)
+        model.iterations = saved_iterations
+        step_dev = replay.keep_alive[0]                    # the graph's device-side Adam step counter (make_graphed_train_step)
+        assert step_dev.dtype == torch.int64 and step_dev.numel() == 1
+        step_dev.fill_(saved_iterations)
+        model._infer_dirty = True
+        del saved
     else:
         run = step
     barrier()
@@ -213,15 +249,18 @@ def main():
         run()
     barrier()
     dt = time.perf_counter() - t0
-    loss_last = current_loss()
-    # per-step times of a further K steps (events around each step): median next to the mean of the timed region
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    for a_, b_ in evs:
-        a_.record(); run(); b_.record()
-    torch.cuda.synchronize()
-    per_step = sorted(a_.elapsed_time(b_) for a_, b_ in evs)
+    if args.dump_outputs and rank == 0:
+        dump_train_outputs(args.dump_outputs, model)
+    loss_last = current_loss() if args.full else None
+    per_step = []
+    if args.full:                                # per-step times of a further K steps (events around each step): median next
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        for a_, b_ in evs:                       # to the mean of the timed region
+            a_.record(); run(); b_.record()
+        torch.cuda.synchronize()
+        per_step = sorted(a_.elapsed_time(b_) for a_, b_ in evs)
     sched = {}
-    if True:                                     # which kernel schedules one step dispatches to (tests assert the same);
+    if args.full:                                # which kernel schedules one step dispatches to (tests assert the same);
         import ctypes as C                       # every rank runs the step (it contains the all-reduce when N > 1)
         lib.mpu_schedule_log_enable(1)
         step()
@@ -233,7 +272,7 @@ def main():
             k = " ".join(line.split()[:2])
             sched[k] = sched.get(k, 0) + 1
     comm = None
-    if trainer is not None:                      # N>1: the all-reduce on the communication stream, timed by events
+    if trainer is not None and args.full:        # N>1: the all-reduce on the communication stream, timed by events
         barrier()                                # over a further K steps (outside the timed region)
         trainer.start_timing()
         for _ in range(args.steps):
@@ -260,7 +299,7 @@ def main():
             _lib.check(lib.mpu_profile_summary(kind, C.byref(ms), C.byref(fl), C.byref(n)), "mpu_profile_summary")
             roof[name] = (ms.value, fl.value, n.value)
         lib.mpu_profile_enable(0)
-    guard_bad = 0.0 if (np.isfinite(loss_first) and np.isfinite(loss_last) and loss_last <= 1.05 * loss_first) else 1.0
+    guard_bad = 0.0 if (not args.full or (np.isfinite(loss_first) and np.isfinite(loss_last) and loss_last <= 1.05 * loss_first)) else 1.0
     if world > 1:
         t = torch.tensor([dt, guard_bad], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -291,13 +330,16 @@ def main():
                        "launch_calibration_ms": launch_cal,
                        "algorithmic_gflop_per_slice": round(gf_slice, 2)},
             "step_tflops_algorithmic": round(gf_slice * B * world / 1e3 / (ms_step / 1e3), 1),
-            "ms_per_step_median": round(per_step[len(per_step) // 2], 4),
-            "ms_per_step_min": round(per_step[0], 4),
-            "guard": {"loss_before_timed_steps": round(loss_first, 5), "loss_after_timed_steps": round(loss_last, 5),
-                      "finite": bool(np.isfinite(loss_first) and np.isfinite(loss_last)),
-                      "decreasing": bool(loss_last < loss_first)},
-            "schedules": sched,
         }
+        if args.full:
+            out.update({
+                "ms_per_step_median": round(per_step[len(per_step) // 2], 4),
+                "ms_per_step_min": round(per_step[0], 4),
+                "guard": {"loss_before_timed_steps": round(loss_first, 5), "loss_after_timed_steps": round(loss_last, 5),
+                          "finite": bool(np.isfinite(loss_first) and np.isfinite(loss_last)),
+                          "decreasing": bool(loss_last < loss_first)},
+                "schedules": sched,
+            })
         if world > 1:
             out["rccl_ranks"] = torch.distributed.get_world_size()
             out["dist_backend"] = torch.distributed.get_backend()
@@ -306,24 +348,25 @@ def main():
                 out["comm"] = comm
         if dt_eager is not None:
             out["ms_per_step_eager_with_events"] = round(dt_eager / args.steps * 1e3, 4)
-        if world == 1 and not args.no_peaks:
+        if args.full and world == 1 and not args.no_peaks:
             # what the step's cycle counts are worth in time: the chip does not hold its 2.4 GHz maximum under these kernels
             out["shader_clock_mhz_during_step"] = clock_during(lambda: [run() for _ in range(14)], device)
         traffic = {}
-        try:   # HBM bytes per launch from the rocprofv3 PMC passes of this round (profiles/, see its note)
-            tfile = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_hbm_traffic_pmc.json"))[-1]
-            from multiplanarunet_amd.srchash import source_sha16, CONV_SOURCES
-            with open(os.path.join(ROOT, "profiles", tfile)) as f:
-                tj = json.load(f)
-            if args.config != 1:     # the counter passes ran on configs[1]: their bytes per launch are not this workload's
-                out["config"]["traffic_source"] = None
-            elif tj.get("source_sha16") == source_sha16(CONV_SOURCES):
-                traffic = {k: v["hbm_bytes_per_launch"] for k, v in tj["classes"].items()}
-                out["config"]["traffic_source"] = "from_file:profiles/" + tfile      # a separate rocprofv3 --pmc pass, not this run
-            else:   # the kernels changed after that counter pass: its bytes are not this build's
-                out["config"]["traffic_source"] = "stale:profiles/%s (kernel sources changed since that PMC pass)" % tfile
-        except Exception:
-            pass
+        if args.full:
+            try:   # HBM bytes per launch from the rocprofv3 PMC passes of this round (profiles/, see its note)
+                tfile = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_hbm_traffic_pmc.json"))[-1]
+                from multiplanarunet_amd.srchash import source_sha16, CONV_SOURCES
+                with open(os.path.join(ROOT, "profiles", tfile)) as f:
+                    tj = json.load(f)
+                if args.config != 1:     # the counter passes ran on configs[1]: their bytes per launch are not this workload's
+                    out["config"]["traffic_source"] = None
+                elif tj.get("source_sha16") == source_sha16(CONV_SOURCES):
+                    traffic = {k: v["hbm_bytes_per_launch"] for k, v in tj["classes"].items()}
+                    out["config"]["traffic_source"] = "from_file:profiles/" + tfile      # a separate rocprofv3 --pmc pass, not this run
+                else:   # the kernels changed after that counter pass: its bytes are not this build's
+                    out["config"]["traffic_source"] = "stale:profiles/%s (kernel sources changed since that PMC pass)" % tfile
+            except Exception:
+                pass
         if events:
             def leg(name):
                 ms, fl, n = roof[name]
@@ -339,7 +382,7 @@ def main():
             out["wgrad"] = leg("wgrad_igemm")
 
     # ---- secondary metric: 6-view predict+fuse on 256^3 (N>1: sharded over the ranks, whole-node voxels/s) ---
-    if not args.no_predict and args.config == 1:
+    if args.full and not args.no_predict and args.config == 1:
         if world == 1:
             out["predict_fuse"] = bench_predict(device, quiet, D=pD)
         else:
@@ -348,14 +391,14 @@ def main():
             pf = bench_predict_sharded(device, quiet, rank, world, args.exchange, D=pD)
             if rank == 0:
                 out["predict_fuse"] = pf
-    if rank == 0 and world == 1 and args.config == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and args.config == 1 and not args.no_e2e:
         out["train_e2e"] = bench_train_e2e(model, device, B, dim, headline=out["value"])
         out["f32_mode"] = bench_f32_mode(device, quiet, B, dim, args.cf, x, y, sw)
         out["bf16x3_mode"] = bench_f32_mode(device, quiet, B, dim, args.cf, x, y, sw, dtype="bf16x3")
-    if rank == 0 and world == 1 and not args.no_peaks:
+    if args.full and rank == 0 and world == 1 and not args.no_peaks:
         out["measured_peaks"] = measured_peaks(device)       # informational (box- and clock-dependent); every `frac` in this
                                                              # line is against the SPEC peaks of MI355X_MICROARCH.md
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(B, dim)
         if "predict_fuse" in out:
             out["predict_fuse"]["cpu_baseline"] = cpu_baseline_predict()
@@ -364,6 +407,39 @@ def main():
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
+
+
+DUMP_MAX_ELEMENTS = 1 << 22       # 16 MB of float32 per file: the three large arrays and the small ones stay under 64 MB
+
+
+def dump_arrays(outdir, arrays):
+    """--dump-outputs: every device tensor of `arrays` as outdir/<name>.npy, in float64 if it is float64, else in float32.
+    An array of more than DUMP_MAX_ELEMENTS elements is written at that many positions drawn with a fixed seed (the same
+    positions for arrays of the same size), so that two builds can be compared file for file."""
+    os.makedirs(outdir, exist_ok=True)
+    torch.cuda.synchronize()
+    picks = {}
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > DUMP_MAX_ELEMENTS:
+            if n not in picks:
+                idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ELEMENTS, replace=False))
+                picks[n] = torch.from_numpy(idx).to(t.device)
+            t = t.reshape(-1)[picks[n]]
+        t = t if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(outdir, name + ".npy"), t.cpu().numpy())
+
+
+def dump_train_outputs(outdir, model):
+    """What the last timed train step leaves its caller: the updated parameters, the step's gradient (sum over the batch),
+    the BatchNorm state, the class probabilities of the step's forward pass and its mean weighted per-pixel loss."""
+    from multiplanarunet_amd import _lib
+    torch.cuda.synchronize()
+    B, H, W, K = model._last_batch, model.img_shape[0], model.img_shape[1], model.n_classes
+    off = int(_lib.load().mpu_unet_workspace_probs_offset(model._h, B))      # (train-mode probabilities stay in the workspace)
+    probs = model._ws[off:off + 4 * B * H * W * K].view(torch.float32).reshape(B, H, W, K)
+    dump_arrays(outdir, {"params": model.params, "grads": model.grads, "bn_state": model.bn_state, "probs": probs,
+                         "loss_mean": model.loss_mean().double()})
 
 
 VIEWS6 = [[0, 0, 1], [1, 0, 0], [0, 1, 0], [0.5, 0.5, 0.707], [-0.6, 0.64, 0.48], [0.7, -0.5, 0.5]]
@@ -386,9 +462,10 @@ def _predict_setup(device, quiet, D, V, K, C):
     return vol, views, model, fm
 
 
-def bench_predict(device, quiet, D=256, V=6, K=3, reps=5, batch=None, C=1):
+def bench_predict(device, quiet, D=256, V=6, K=3, reps=5, batch=None, C=1, dump=None):
     """BASELINE.json configs[2] (D=256, C=1, K=3) / configs[4] (D=512, C=2, K=5): 6-view predict+fuse on one synthetic
-    volume, one GPU. Median of `reps` runs (the per-stage times are those of the median run)."""
+    volume, one GPU. Median of `reps` runs (the per-stage times are those of the median run). dump: directory for the
+    label volume of the last run (--dump-outputs)."""
     from multiplanarunet_amd.predict import multi_view_predict
     vol, views, model, fm = _predict_setup(device, quiet, D, V, K, C)
     batch = batch or (int(os.environ["MPU_BENCH_PREDICT_BATCH"]) if "MPU_BENCH_PREDICT_BATCH" in os.environ else None)
@@ -401,6 +478,8 @@ def bench_predict(device, quiet, D=256, V=6, K=3, reps=5, batch=None, C=1):
         _, labels = multi_view_predict(model, vol, views, D, float(D), fm, batch_size=batch, want_probs=False, timings=t)
         torch.cuda.synchronize()
         runs.append((time.perf_counter() - t0, t))
+    if dump:
+        dump_arrays(dump, {"labels": labels})
     runs.sort(key=lambda r: r[0])
     best, tim = runs[len(runs) // 2]
     clk = clock_during(lambda: multi_view_predict(model, vol, views, D, float(D), fm, batch_size=batch, want_probs=False),
@@ -445,11 +524,12 @@ def bench_predict(device, quiet, D=256, V=6, K=3, reps=5, batch=None, C=1):
             "label_histogram": hist}
 
 
-def bench_predict_sharded(device, quiet, rank, world, exchange="both", D=256, V=6, K=3, C=1, reps=3):
+def bench_predict_sharded(device, quiet, rank, world, exchange="both", D=256, V=6, K=3, C=1, reps=3, dump=None):
     """The same volume over all ranks (multiplanarunet_amd.distributed.multi_view_predict_sharded):
     every rank holds the volume, runs the U-Net on its (view, plane-chunk) work items and joins the exchange.
     value = D^3 / (barrier-to-barrier time, max over ranks) = whole-node voxels/s; the exchange (reduce-scatter of
-    the partial fusion sums + finalize + label all-gather, or the all-gather of per-view volumes) is timed on its own."""
+    the partial fusion sums + finalize + label all-gather, or the all-gather of per-view volumes) is timed on its own.
+    dump: directory for the label volume of the main exchange's last run (--dump-outputs; rank 0 passes it)."""
     import torch.distributed as dist
     from multiplanarunet_amd import distributed as Dm
     vol, views, model, fm = _predict_setup(device, quiet, D, V, K, C)
@@ -467,6 +547,8 @@ def bench_predict_sharded(device, quiet, rank, world, exchange="both", D=256, V=
             t = torch.tensor([el, tm["exchange_s"], tm["compute_s"]], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             runs.append((float(t[0]), float(t[1]), float(t[2]), tm))
+        if dump and not legs:                               # the first exchange timed is the line's main leg
+            dump_arrays(dump, {"labels": labels})
         runs.sort(key=lambda r: r[0])
         el, ex_s, comp_s, tm = runs[len(runs) // 2]
         hist = torch.bincount(labels.reshape(-1).long(), minlength=K).tolist()
