@@ -14,10 +14,6 @@
 
 namespace mpu {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
 namespace {
 
 constexpr int C8_ROWS_DEFAULT = 16;                             // output rows per workgroup (4 waves, interleaved rows)
@@ -153,8 +149,7 @@ int launch_c8(const ConvArgs& a_in, hipStream_t st) {
 
 // 1 = launched, 0 = shape not suited (the caller falls back to the tiled kernels), < 0 = error
 int try_conv_c8(int dtype, int mode, const ConvArgs& a, hipStream_t st) {
-    const bool on = env(ENV_CONV_C8) != 0;
-    if (!on || dtype != MPU_BF16 || mode != CONV3 || a.C1 != 0 || a.in1 || a.C0 != 8) return 0;
+    if (dtype != MPU_BF16 || mode != CONV3 || a.C1 != 0 || a.in1 || a.C0 != 8) return 0;
     if (a.Cout % 8 || a.Cout > 128 || a.mask || a.post_scale || a.ksplit > 1) return 0;
     int rc;
     switch (cdiv(a.Cout, 32)) {

@@ -32,28 +32,7 @@
 
 namespace mpu {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
 namespace {
-
-__device__ __forceinline__ i32x4 dk_rsrc(const void* p, long bytes) {
-    const unsigned long long pa = (unsigned long long)p;
-    i32x4 r;
-    r.x = (int)(unsigned)pa; r.y = (int)((unsigned)(pa >> 32) & 0xffffu); r.z = (int)bytes; r.w = 0x00020000;
-    return r;
-}
-template <int IMM>
-__device__ __forceinline__ void dk_dma(const i32x4& rsrc, unsigned voff, unsigned lds_base) {
-    asm volatile("s_add_u32 m0, %1, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                 :: "v"(voff), "s"(lds_base), "s"(rsrc), "n"(IMM) : "memory", "scc");
-}
-__device__ __forceinline__ int dk_xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-constexpr unsigned DK_POISON = 0x80001000u;                      // + any in-range byte offset (< 2 GiB - 8 KiB) stays >= num_records
 
 template <int W_>
 struct DkCfg {
@@ -70,8 +49,9 @@ struct DkCfg {
 };
 static_assert(DkCfg<16>::SMEM <= 160 * 1024, "LDS");
 
+// pixel (0..31) of a 32-pixel block whose fragment lane l31 holds (a block: two 16-pixel rows for W_ = 16, else four 8-pixel rows)
 template <int W_>
-__device__ __forceinline__ int dk_pix_in_block(int l31) {        // = deep_pix_in_block (conv_glds.hip)
+__device__ __forceinline__ int dk_pix_in_block(int l31) {
     const int q = l31 >> 2, t = l31 & 3;
     const int g = (0x96 >> q) & 1;
     const int k = (q >> 1) * 4 + t;
@@ -92,14 +72,14 @@ __global__ __launch_bounds__(512, 2) void conv_deepk_kernel(ConvArgs a, int tile
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int up = wave >> 1, uk = wave & 1;                     // the wave's unit of an interval: item slot 0..3, k-step 0..1
-    const int logical = dk_xcd_remap(blockIdx.x, gridDim.x);     // the pixel tiles of one filter tile share an XCD (its L2 holds the weights)
+    const int logical = xcd_contiguous(blockIdx.x, gridDim.x);   // the pixel tiles of one filter tile share an XCD (its L2 holds the weights)
     const int mt = logical % tiles_m, nt = logical / tiles_m;
     const int n0 = nt * BN, m0 = mt * BM;
     const int nch0 = a.C0 >> 6, nchunks = nch0 + (a.C1 >> 6), npairs = nchunks >> 1;
     const int M = a.B * HW;
-    const i32x4 rs0 = dk_rsrc(a.in0, (long)M * a.C0 * 2L);
-    const i32x4 rs1 = dk_rsrc(a.in1 ? a.in1 : a.in0, a.in1 ? (long)M * a.C1 * 2L : 0);
-    const i32x4 rsw = dk_rsrc(a.w, a.w_elems * 2L);
+    const i32x4 rs0 = make_rsrc(a.in0, (long)M * a.C0 * 2L);
+    const i32x4 rs1 = make_rsrc(a.in1 ? a.in1 : a.in0, a.in1 ? (long)M * a.C1 * 2L : 0);
+    const i32x4 rsw = make_rsrc(a.w, a.w_elems * 2L);
     const unsigned lds0 = (unsigned)(uintptr_t)smem;
     const unsigned ldsW = lds0 + Cfg::NB * PBUF;
     const unsigned w_tap_b = (unsigned)(a.w_tap_stride * 2L);
@@ -145,8 +125,8 @@ __global__ __launch_bounds__(512, 2) void conv_deepk_kernel(ConvArgs a, int tile
         const int cb = ((s1 ? c - nch0 : c) << 6);
         q.rs.x = s1 ? rs1.x : rs0.x; q.rs.y = s1 ? rs1.y : rs0.y; q.rs.z = s1 ? rs1.z : rs0.z; q.rs.w = rs0.w;
         q.pitch2 = (s1 ? a.C1 : a.C0) * 2;
-        q.cb2 = valid ? (unsigned)(cb * 2) : DK_POISON;
-        q.wcol2 = valid ? (unsigned)(((s1 ? a.C0 : 0) + cb) * 2) : DK_POISON;
+        q.cb2 = valid ? (unsigned)(cb * 2) : DMA_POISON;
+        q.wcol2 = valid ? (unsigned)(((s1 ? a.C0 : 0) + cb) * 2) : DMA_POISON;
         return q;
     };
     // half patch H4 (0..3) of the pair whose chunks are (Q0, Q1): the wave's two pieces into buffer H4
@@ -155,14 +135,14 @@ __global__ __launch_bounds__(512, 2) void conv_deepk_kernel(ConvArgs a, int tile
         const Chunk& q_ = ((H4) >> 1) ? (Q1) : (Q0);                                                                \
         const unsigned o0_ = (unsigned)(ppix[0] * q_.pitch2) + q_.cb2 + (unsigned)(((H4) & 1) * 64) + pch[0];       \
         const unsigned o1_ = (unsigned)(ppix[1] * q_.pitch2) + q_.cb2 + (unsigned)(((H4) & 1) * 64) + pch[1];       \
-        dk_dma<(H4) * PBUF>(q_.rs, o0_, sbase_p); dk_dma<(H4) * PBUF + 8192>(q_.rs, o1_, sbase_p);                   \
+        dma16_at<(H4) * PBUF>(q_.rs, o0_, sbase_p); dma16_at<(H4) * PBUF + 8192>(q_.rs, o1_, sbase_p);                   \
     } while (0)
     // the wave's two weight pieces of ITS item of interval IV_ (of the pair (Q0, Q1)) into the stage at ring offset STB_
 #define DK_WEIGHTS(Q0, Q1, IV_, STB_)                                                                                \
     do {                                                                                                            \
         const int idx_ = 4 * (IV_) + up, h4_ = (idx_ * 57) >> 9, tap_ = idx_ - 9 * h4_;                             \
         const unsigned so_ = (unsigned)tap_ * w_tap_b + ((h4_ >> 1) ? (Q1).wcol2 : (Q0).wcol2) + (unsigned)((h4_ & 1) * 64); \
-        dk_dma<0>(rsw, wpo[0] + so_, sbase_w + (STB_)); dk_dma<1024>(rsw, wpo[1] + so_, sbase_w + (STB_));            \
+        dma16_at<0>(rsw, wpo[0] + so_, sbase_w + (STB_)); dma16_at<1024>(rsw, wpo[1] + so_, sbase_w + (STB_));            \
     } while (0)
 
     // ---- prologue = slots -7 .. -2 of the request rule (R_{-1} follows the first barrier) -------------------------------
@@ -194,13 +174,12 @@ __global__ __launch_bounds__(512, 2) void conv_deepk_kernel(ConvArgs a, int tile
         if (W_ == 16) brow[j] = (ml >> 4) * PW + (ml & 15);
         else brow[j] = (ml >> 6) * IMG + ((ml >> 3) & 7) * PW + (ml & 7);
     }
-    typedef unsigned int dk_u32x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) const dk_u32x4* lds_u4;
+    typedef __attribute__((address_space(3))) const u32x4* lds_u4;
 #define DK_LD(DST, ADDR, IMM) DST = *(lds_u4)(uintptr_t)((ADDR) + (IMM))
 #define DK_SB() __builtin_amdgcn_sched_barrier(0)
 #define DK_MM(FA, FB, I, J)                                                                                        \
     acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(s16x8, FA[I]), __builtin_bit_cast(s16x8, FB[J]), acc[I][J], 0, 0, 0)
-    dk_u32x4 fa0[2], fb0[4], fa1[2], fb1[4];                     // two operand sets (intervals alternate)
+    u32x4 fa0[2], fb0[4], fa1[2], fb1[4];                     // two operand sets (intervals alternate)
     // address of the lane's pixel fragment of block J_ for the item of interval IV_
     auto pix_addr = [&](int iv, int j) -> unsigned {
         const int idx = 4 * iv + up, h4 = (idx * 57) >> 9, tap = idx - 9 * h4;
@@ -212,7 +191,7 @@ __global__ __launch_bounds__(512, 2) void conv_deepk_kernel(ConvArgs a, int tile
     unsigned stb = 0;                                            // ring offset of the CURRENT interval's stage
     bool first_pair = true;
     // One interval (see the header). Operands of interval IV sit in (FA, FB); those of IV + 1 are read into (GA, GB).
-    auto interval = [&](auto ivc, dk_u32x4 (&FA)[2], dk_u32x4 (&FB)[4], dk_u32x4 (&GA)[2], dk_u32x4 (&GB)[4]) {
+    auto interval = [&](auto ivc, u32x4 (&FA)[2], u32x4 (&FB)[4], u32x4 (&GA)[2], u32x4 (&GB)[4]) {
         constexpr int IV = decltype(ivc)::value;
         if (STAMP && stamps && IV == 4 && first_pair) stamps[8] = __builtin_amdgcn_s_memtime();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -294,7 +273,7 @@ __global__ __launch_bounds__(512, 2) void conv_deepk_kernel(ConvArgs a, int tile
                                                                            a.bn_x ? a.Cout * 4 : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsis = __builtin_amdgcn_make_buffer_rsrc((void*)(a.bn_x ? (const void*)a.bn_invstd : a.out), 0,
                                                                            a.bn_x ? a.Cout * 4 : 0, 0x00020000);
-    dk_u32x4 bq4[4], mu4[4], is4[4]; dk_u32x2 mk2[4], bx2[4];
+    u32x4 bq4[4], mu4[4], is4[4]; dk_u32x2 mk2[4], bx2[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int c = n0 + iw * 32 + 8 * q + 4 * fh;
@@ -429,7 +408,7 @@ int launch_deepk(const ConvArgs& a_in, hipStream_t st) {
 // about one 128-pixel x 64-filter tile per CU (192..512); epilogue: bias, ReLU, ReLU mask, fused BatchNorm statistics of the
 // stored values (forward: sum x, sum x^2; with bn_x: the BatchNorm-backward sums), no folded-BN affine / pooling / head.
 int try_conv_deepk(int dtype, int mode, const ConvArgs& a, hipStream_t st) {
-    if (!env(ENV_CONV_DEEPK) || dtype != MPU_BF16 || mode != CONV3 || a.Ho != 16 || a.Wo != 16) return 0;
+    if (dtype != MPU_BF16 || mode != CONV3 || a.Ho != 16 || a.Wo != 16) return 0;
     if (a.pooled || a.head_w || a.post_scale) return 0;
     if (a.bn_x && !(a.stats && a.bn_mean && a.bn_invstd)) return 0;
     const long M = (long)a.B * a.Ho * a.Wo;

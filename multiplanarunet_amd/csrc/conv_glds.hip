@@ -19,76 +19,6 @@
 
 namespace mpu {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-
-template <int MODE> struct GModeTraits;
-template <> struct GModeTraits<CONV3>   { static constexpr int NTAPS = 9, KW = 3; };
-template <> struct GModeTraits<UPCONV2> { static constexpr int NTAPS = 4, KW = 2; };
-template <> struct GModeTraits<CONV3S2> { static constexpr int NTAPS = 9, KW = 3; };
-template <> struct GModeTraits<CONV1>   { static constexpr int NTAPS = 1, KW = 1; };
-
-template <int MODE>
-__device__ __forceinline__ bool g_tap_src(int oy, int ox, int ky, int kx, int Ho, int Wo, int& iy, int& ix) {
-    if (MODE == CONV3) {
-        iy = oy + ky - 1; ix = ox + kx - 1;
-        return (unsigned)iy < (unsigned)Ho && (unsigned)ix < (unsigned)Wo;
-    } else if (MODE == UPCONV2) {
-        const int uy = oy + ky, ux = ox + kx;
-        iy = uy >> 1; ix = ux >> 1;
-        return uy < Ho && ux < Wo;
-    } else if (MODE == CONV3S2) {
-        iy = 2 * oy + ky - 1; ix = 2 * ox + kx - 1;
-        return (unsigned)iy < (unsigned)(2 * Ho) && (unsigned)ix < (unsigned)(2 * Wo);
-    } else {
-        iy = oy; ix = ox;
-        return true;
-    }
-}
-template <int MODE> __device__ __forceinline__ int g_in_h(int Ho) {
-    return MODE == UPCONV2 ? Ho / 2 : (MODE == CONV3S2 ? Ho * 2 : Ho);
-}
-
-template <typename T> struct GMma;
-template <> struct GMma<bf16_t> {
-    static __device__ __forceinline__ void run(const uint4& a, const uint4& b, f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(s16x8, a), __builtin_bit_cast(s16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct GMma<float> {
-    static __device__ __forceinline__ void run(const uint4& a, const uint4& b, f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
-    }
-};
-
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
-// raw buffer descriptor (stride 0, byte-granular range check) in four SGPRs
-__device__ __forceinline__ i32x4 make_rsrc(const void* p, long bytes) {
-    const unsigned long long pa = (unsigned long long)p;
-    i32x4 r;
-    r.x = (int)(unsigned)pa;
-    r.y = (int)((unsigned)(pa >> 32) & 0xffffu);
-    r.z = (int)bytes;
-    r.w = 0x00020000;
-    return r;
-}
-// One LDS-DMA piece: 64 lanes x 16 B -> LDS[lds_addr + lane*16]. Issued as inline asm so that the
-// compiler does not treat it as a pending LDS write (it would drain vmcnt(0) before every ds_read);
-// completion is tracked by the caller's counted s_waitcnt vmcnt(N) + s_barrier.
-__device__ __forceinline__ void dma16(const i32x4& rsrc, unsigned voff, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                 :: "v"(voff), "s"(lds_addr), "s"(rsrc) : "memory");
-}
-
-__device__ __forceinline__ int g_xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
 template <typename T, int BN, int BM>
 struct GldsCfg {
     static constexpr int STAGE = (BN + BM) * 128;
@@ -108,7 +38,7 @@ __global__ __launch_bounds__(256, 2) void conv_glds_kernel(ConvArgs a) {
     constexpr int BKE = 128 / sizeof(T);
     constexpr int TN = WN / 32, TM = WM / 32;
     constexpr int WAVES_N = BN / WN;
-    constexpr int NTAPS = GModeTraits<MODE>::NTAPS, KW = GModeTraits<MODE>::KW;
+    constexpr int NTAPS = ModeTraits<MODE>::NTAPS, KW = ModeTraits<MODE>::KW;
     constexpr int STAGE = Cfg::STAGE;
     constexpr int GW = BN / 32, GP = BM / 32;        // 8-row groups per wave (weights / pixels)
     static_assert((BN / WN) * (BM / WM) == 4, "4 waves");
@@ -118,7 +48,7 @@ __global__ __launch_bounds__(256, 2) void conv_glds_kernel(ConvArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave % WAVES_N, wm = wave / WAVES_N;
     const int tiles_n = (a.Cout + BN - 1) / BN;
-    const int logical = g_xcd_remap(blockIdx.x, gridDim.x);
+    const int logical = xcd_contiguous(blockIdx.x, gridDim.x);
     const int n0 = (logical % tiles_n) * BN;
     const long m0 = (long)(logical / tiles_n) * BM;
     const int nch0 = (a.C0 + BKE - 1) / BKE, nch1 = (a.C1 + BKE - 1) / BKE;
@@ -128,7 +58,7 @@ __global__ __launch_bounds__(256, 2) void conv_glds_kernel(ConvArgs a) {
     const int ks = a.ksplit > 1 ? a.ksplit : 1;
     const int it0 = (int)((long)blockIdx.y * nit_all / ks);
     const int nit = (int)((long)(blockIdx.y + 1) * nit_all / ks) - it0;
-    const int Hi = g_in_h<MODE>(a.Ho), Wi = g_in_h<MODE>(a.Wo);
+    const int Hi = in_h<MODE>(a.Ho), Wi = in_h<MODE>(a.Wo);
     const long M = (long)a.B * a.Ho * a.Wo;
     constexpr unsigned OOB = 0xfffffff0u;
     const long npix = (long)a.B * Hi * Wi;
@@ -190,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void conv_glds_kernel(ConvArgs a) {
 #pragma unroll
             for (int g = 0; g < GP; ++g) {
                 int iy, ix;
-                const bool v = g_tap_src<MODE>(py[g], px[g], ky, kx, a.Ho, a.Wo, iy, ix) && pb[g] >= 0;
+                const bool v = tap_src<MODE>(py[g], px[g], ky, kx, a.Ho, a.Wo, iy, ix) && pb[g] >= 0;
                 ptap[g] = v ? pb[g] + iy * Wi + ix : -1;
             }
         }
@@ -250,7 +180,7 @@ __global__ __launch_bounds__(256, 2) void conv_glds_kernel(ConvArgs a) {
 #pragma unroll
                 for (int i = 0; i < TN; ++i)
 #pragma unroll
-                    for (int j = 0; j < TM; ++j) GMma<T>::run(af[s][i], bf[s][j], acc[i][j]);
+                    for (int j = 0; j < TM; ++j) Mma<T>::run(af[s][i], bf[s][j], acc[i][j]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -596,7 +526,7 @@ static int launch_glds_cfg(const ConvArgs& a_in, hipStream_t st) {
     using Cfg = GldsCfg<T, BN, BM>;
     auto kern = conv_glds_kernel<T, MODE, BN, BM, WN, WM>;
     ConvArgs a = a_in;
-    constexpr int NT = GModeTraits<MODE>::NTAPS;
+    constexpr int NT = ModeTraits<MODE>::NTAPS;
     if (a.w_elems <= 0) a.w_elems = (NT - 1) * a.w_tap_stride + (long)a.Cout * a.w_row_stride;
     static unsigned long long attr_set = 0;
     if (first_use_on_device(attr_set)) {
@@ -662,28 +592,19 @@ struct PipeCfg {
     static constexpr int S0 = NS * STAGE > EPI ? NS * STAGE : EPI;
     static constexpr int SMEM = S0 > STG ? S0 : STG;
 };
-constexpr unsigned PIPE_POISON = 0x80001000u;                    // + any in-range byte offset stays >= num_records (< 2^31 - 8192)
-
-// LDS-DMA piece with the LDS destination = scalar base + immediate (one SALU op)
-template <int IMM>
-__device__ __forceinline__ void dma16_at(const i32x4& rsrc, unsigned voff, unsigned lds_base) {
-    asm volatile("s_add_u32 m0, %1, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                 :: "v"(voff), "s"(lds_base), "s"(rsrc), "n"(IMM) : "memory", "scc");
-}
-
 template <int MODE, bool RAGGED, int DBG>
 __global__ __launch_bounds__(512, 2) void conv_pipe_kernel(ConvArgs a, int tiles_m, int tiles_n, unsigned magic_w, unsigned magic_h) {
     typedef bf16_t T;
     constexpr int BN = PipeCfg::BN, BM = PipeCfg::BM, STAGE = PipeCfg::STAGE;
     constexpr int EPC = 8, BKE = 64;
-    constexpr int NTAPS = GModeTraits<MODE>::NTAPS, KW = GModeTraits<MODE>::KW;
+    constexpr int NTAPS = ModeTraits<MODE>::NTAPS, KW = ModeTraits<MODE>::KW;
     constexpr int GW = 2, GP = 4, NLD = GW + GP;                 // 8-row DMA pieces per wave: weights, pixels
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave & 1, wm = wave >> 1;                     // 2 x 4 waves of 64 channels x 64 pixels
-    const int logical = g_xcd_remap(blockIdx.x, gridDim.x);
+    const int logical = xcd_contiguous(blockIdx.x, gridDim.x);
     const int mt = logical % tiles_m, r1 = logical / tiles_m;
     const int nt = r1 % tiles_n, kz = r1 / tiles_n;
     const int n0 = nt * BN, m0 = mt * BM;
@@ -693,7 +614,7 @@ __global__ __launch_bounds__(512, 2) void conv_pipe_kernel(ConvArgs a, int tiles
     const int ks = a.ksplit > 1 ? a.ksplit : 1;
     const int it0 = (int)((long)kz * nit_all / ks);
     const int nit = (int)((long)(kz + 1) * nit_all / ks) - it0;
-    const int Hi = g_in_h<MODE>(a.Ho), Wi = g_in_h<MODE>(a.Wo);
+    const int Hi = in_h<MODE>(a.Ho), Wi = in_h<MODE>(a.Wo);
     const int M = a.B * a.Ho * a.Wo;                             // (all operands < 2 GiB: checked by the launcher)
     const long npix = (long)a.B * Hi * Wi;
     const i32x4 rs0 = make_rsrc(a.in0, npix * a.C0 * 2L);
@@ -725,7 +646,7 @@ __global__ __launch_bounds__(512, 2) void conv_pipe_kernel(ConvArgs a, int tiles
         const int rl = wave * (BN / 8) + g * 8 + lrow;           // tile-local weight row
         const int n = n0 + rl;
         wch[g] = (slot ^ ((rl >> 1) & 7)) * EPC;
-        wl[g] = n < a.Cout ? (unsigned)(n * a.w_row_stride * 2 + wch[g] * 2) : PIPE_POISON;
+        wl[g] = n < a.Cout ? (unsigned)(n * a.w_row_stride * 2 + wch[g] * 2) : DMA_POISON;
     }
     int pb[GP], py[GP], px[GP], pch[GP];
 #pragma unroll
@@ -757,8 +678,8 @@ __global__ __launch_bounds__(512, 2) void conv_pipe_kernel(ConvArgs a, int tiles
         const int s1 = cc >= nch0 ? 1 : 0;
         const int cb = (s1 ? cc - nch0 : cc) * BKE;
         const int Cs = s1 ? a.C1 : a.C0;
-        q_wsoff = valid ? (unsigned)((tap * wts + (s1 ? a.C0 : 0) + cb) * 2) : PIPE_POISON;
-        q_pcoff = valid ? (unsigned)(cb * 2) : PIPE_POISON;
+        q_wsoff = valid ? (unsigned)((tap * wts + (s1 ? a.C0 : 0) + cb) * 2) : DMA_POISON;
+        q_pcoff = valid ? (unsigned)(cb * 2) : DMA_POISON;
         q_room = Cs - cb;
         q_rs.x = s1 ? rs1.x : rs0.x; q_rs.y = s1 ? rs1.y : rs0.y; q_rs.z = s1 ? rs1.z : rs0.z; q_rs.w = rs0.w;
         if (valid && (tap != cur_tap || s1 != cur_src)) {        // rare: a new tap or the second concat source
@@ -767,18 +688,18 @@ __global__ __launch_bounds__(512, 2) void conv_pipe_kernel(ConvArgs a, int tiles
 #pragma unroll
             for (int g = 0; g < GP; ++g) {
                 int iy, ix;
-                const bool v = g_tap_src<MODE>(py[g], px[g], ky, kx, a.Ho, a.Wo, iy, ix) && pb[g] >= 0;
-                pbase[g] = v ? (unsigned)(((pb[g] + iy * Wi + ix) * Cs + pch[g]) * 2) : PIPE_POISON;
+                const bool v = tap_src<MODE>(py[g], px[g], ky, kx, a.Ho, a.Wo, iy, ix) && pb[g] >= 0;
+                pbase[g] = v ? (unsigned)(((pb[g] + iy * Wi + ix) * Cs + pch[g]) * 2) : DMA_POISON;
             }
         }
     };
     auto w_off = [&](int g) -> unsigned {
         const unsigned o = wl[g] + q_wsoff;
-        return (RAGGED && wch[g] >= q_room) ? PIPE_POISON : o;
+        return (RAGGED && wch[g] >= q_room) ? DMA_POISON : o;
     };
     auto p_off = [&](int g) -> unsigned {
         const unsigned o = pbase[g] + q_pcoff;
-        return (RAGGED && pch[g] >= q_room) ? PIPE_POISON : o;
+        return (RAGGED && pch[g] >= q_room) ? DMA_POISON : o;
     };
 #define PIPE_DMA_W(G, ST_) dma16_at<(ST_) * STAGE + (G) * 1024>(rsw, w_off(G), wdst)
 #define PIPE_DMA_P(G, ST_) dma16_at<(ST_) * STAGE + (G) * 1024>(q_rs, p_off(G), pdst)
@@ -809,15 +730,14 @@ __global__ __launch_bounds__(512, 2) void conv_pipe_kernel(ConvArgs a, int tiles
         LB[s_] = lds0 + BN * 128 + (wm * 64 + (lane & 31)) * 128 + so;
         LA2[s_] = LA[s_] + 2 * STAGE; LB2[s_] = LB[s_] + 2 * STAGE;
     }
-    typedef unsigned int pipe_u32x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) const pipe_u32x4* lds_u4;
+    typedef __attribute__((address_space(3))) const u32x4* lds_u4;
 #define PIPE_LD(DST, ARR, ARR2, ST_, S_, HALF)                                                         \
     DST = *(lds_u4)(uintptr_t)(((ST_) == 2 ? ARR2[S_] : ARR[S_]) + ((ST_) == 1 ? STAGE : 0) + (HALF) * 4096)
 #define PIPE_SB() __builtin_amdgcn_sched_barrier(0)
 #define PIPE_MM(FA, FB, I, J)                                                                          \
     acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(s16x8, FA[I]), __builtin_bit_cast(s16x8, FB[J]), acc[I][J], 0, 0, 0)
 
-    pipe_u32x4 fa0[2], fb0[2], fa1[2], fb1[2], fa2[2], fb2[2];   // three fragment sets
+    u32x4 fa0[2], fb0[2], fa1[2], fb1[2], fa2[2], fb2[2];   // three fragment sets
 
     // one K step on stage ST: 16 MFMAs, each followed by one fragment read and (12 of them) a share of the next DMA
     auto kstep = [&](auto stc, int it) {
@@ -985,7 +905,7 @@ template <int MODE, bool RAGGED, int DBG>
 static int launch_pipe(const ConvArgs& a_in, int ks, hipStream_t st) {
     auto kern = conv_pipe_kernel<MODE, RAGGED, DBG>;
     ConvArgs a = a_in;
-    constexpr int NT = GModeTraits<MODE>::NTAPS;
+    constexpr int NT = ModeTraits<MODE>::NTAPS;
     if (a.w_elems <= 0) a.w_elems = (NT - 1) * a.w_tap_stride + (long)a.Cout * a.w_row_stride;
     static unsigned long long attr_set = 0;
     if (first_use_on_device(attr_set)) {
@@ -1009,18 +929,18 @@ template <typename T, int MODE>
 static int try_pipe(const ConvArgs& a, hipStream_t st) {
     if constexpr (sizeof(T) != 2 || MODE == CONV1) return 0;
     else {
-        const int on = (int)env(ENV_CONV_PIPE), dbg = (int)env(ENV_PIPE_DEBUG);
+        const int dbg = (int)env(ENV_PIPE_DEBUG);
         constexpr int min_steps = 12, wgs = 256;                 // >= 12 K steps per workgroup; about one workgroup per CU
-        if (!on || a.Cout < 128) return 0;
+        if (a.Cout < 128) return 0;
         const long M = (long)a.B * a.Ho * a.Wo;
         const long tiles = (long)cdiv(M, PipeCfg::BM) * cdiv(a.Cout, PipeCfg::BN);
-        const int nit = GModeTraits<MODE>::NTAPS * (cdiv(a.C0, 64) + cdiv(a.C1, 64));
+        const int nit = ModeTraits<MODE>::NTAPS * (cdiv(a.C0, 64) + cdiv(a.C1, 64));
         if (tiles > 2L * wgs || nit < min_steps) return 0;      // large grids: the two-workgroup schedules fill the chip
         {   // 32-bit offsets with a poison margin: every operand (and the f32 output rows) below 2 GiB - 8 KiB
             const long hi = MODE == UPCONV2 ? a.Ho / 2 : (MODE == CONV3S2 ? a.Ho * 2 : a.Ho);
             const long wi = MODE == UPCONV2 ? a.Wo / 2 : (MODE == CONV3S2 ? a.Wo * 2 : a.Wo);
             const long cmax = a.C0 > a.C1 ? a.C0 : a.C1;
-            const long wel = a.w_elems > 0 ? a.w_elems : (GModeTraits<MODE>::NTAPS - 1) * a.w_tap_stride + (long)a.Cout * a.w_row_stride;
+            const long wel = a.w_elems > 0 ? a.w_elems : (ModeTraits<MODE>::NTAPS - 1) * a.w_tap_stride + (long)a.Cout * a.w_row_stride;
             const long lim = (1L << 31) - 8192;
             if ((long)a.B * hi * wi * cmax * 2L >= lim || wel * 2L >= lim || M * a.Cout * 2L >= lim || M >= (1L << 30)) return 0;
             if ((M + 256) * (a.Wo > a.Ho ? a.Wo : a.Ho) >= (1L << 32)) return 0;      // multiply-high division is exact
@@ -1084,7 +1004,7 @@ static int launch_glds_mode(const ConvArgs& a_in, hipStream_t st) {
     // few output tiles but a long reduction (deep U-Net levels): 128x128 tiles, K split over workgroups
     if (a.Cout >= 128 && a.partial && t128 < 256) {
         constexpr int BKE = 128 / sizeof(T);
-        const int nit = GModeTraits<MODE>::NTAPS * (cdiv(a.C0, BKE) + cdiv(a.C1, BKE));
+        const int nit = ModeTraits<MODE>::NTAPS * (cdiv(a.C0, BKE) + cdiv(a.C1, BKE));
         constexpr long sk_target = 512, sk_max = 8;              // ~2 workgroups per CU, at most 8 partial copies
         long ks = sk_target / (t128 > 0 ? t128 : 1);
         if (ks > sk_max) ks = sk_max;
@@ -1122,7 +1042,6 @@ int launch_conv_glds(int dtype, int mode, const ConvArgs& a, hipStream_t st) {
 // are spread over four 64-byte bank groups by XOR-ing the 64-byte granule index of the row
 // (256-byte rows: granule ^= row&3; 128-byte rows: granule ^= (row>>1)&1) on the DMA source side.
 // ------------------------------------------------------------------------- //
-typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 template <int ROWB> __device__ __forceinline__ int wg_swz16(int row) {   // XOR mask on the 16-byte slot index
     return ROWB == 256 ? ((row & 3) << 2) : (((row >> 1) & 1) << 2);
@@ -1146,7 +1065,7 @@ __device__ __forceinline__ void wgrad_glds_body(const WgradArgs& a, const unsign
     constexpr int NPX = PX / 4, NPZ = PZ / 4;                            // pieces per wave
     static_assert(NPX >= 1 && NPZ >= 1, "tile too small");
     constexpr int WCI = BCI / 2, WCO = BCO / 2, TI = WCI / 32, TJ = WCO / 32;
-    constexpr int KW = GModeTraits<MODE>::KW;
+    constexpr int KW = ModeTraits<MODE>::KW;
     static_assert(NSTAGE * STAGE == WgradGldsCfg<T, BCI, BCO>::SMEM, "LDS size");
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1157,7 +1076,7 @@ __device__ __forceinline__ void wgrad_glds_body(const WgradArgs& a, const unsign
     // XCD-aware decode of the 1-D grid: all taps (and tiles) of one pixel chunk z run on ONE XCD
     // (workgroup g is dispatched to XCD g % 8), back to back, so x and dZ of the chunk are fetched
     // from HBM once and re-read from that XCD's L2 by the other taps (PMC: 9x less FETCH_SIZE).
-    constexpr int NTAPS_ = GModeTraits<MODE>::NTAPS;
+    constexpr int NTAPS_ = ModeTraits<MODE>::NTAPS;
     const int ntile = tiles_co * ((Cin + BCI - 1) / BCI);
     // locality unit = (pixel chunk z, output tile): its taps sit on one XCD, units are dealt round-robin
     const int xcd = bid & 7, slot = bid >> 3;
@@ -1169,7 +1088,7 @@ __device__ __forceinline__ void wgrad_glds_body(const WgradArgs& a, const unsign
     const long M = (long)a.B * a.Ho * a.Wo;
     const long mbeg = (long)zsplit * a.mchunk;
     const long mend = (mbeg + a.mchunk < M) ? mbeg + a.mchunk : M;
-    const int Hi = g_in_h<MODE>(a.Ho), Wi = g_in_h<MODE>(a.Wo);
+    const int Hi = in_h<MODE>(a.Ho), Wi = in_h<MODE>(a.Wo);
     constexpr unsigned OOB = 0xfffffff0u;
     const long npix = (long)a.B * Hi * Wi;
     // the ci tile lies entirely in one concat source (host guarantees C0 % BCI == 0 when C1 > 0)
@@ -1222,14 +1141,14 @@ __device__ __forceinline__ void wgrad_glds_body(const WgradArgs& a, const unsign
     unsigned zoffl[NPZ];                                         // running dZ offsets (poison: channel beyond Cout)
 #pragma unroll
     for (int g = 0; g < NPZ; ++g)
-        zoffl[g] = co0 + zch[g] < a.Cout ? (unsigned)(((mbeg + zrow[g]) * a.Cout + co0 + zch[g]) * (long)sizeof(T)) : PIPE_POISON;
+        zoffl[g] = co0 + zch[g] < a.Cout ? (unsigned)(((mbeg + zrow[g]) * a.Cout + co0 + zch[g]) * (long)sizeof(T)) : DMA_POISON;
     const unsigned zstep = (unsigned)(KP * a.Cout * (int)sizeof(T));
     auto issue = [&](long /*mb: sequential, KP apart*/, int stage) {
         const unsigned sb = lds0 + stage * STAGE;
 #pragma unroll
         for (int g = 0; g < NPX; ++g) {
             int iy, ix;
-            const bool v = g_tap_src<MODE>(xoy[g], xox[g], ky, kx, a.Ho, a.Wo, iy, ix) && cs0 + xch[g] < Cs;
+            const bool v = tap_src<MODE>(xoy[g], xox[g], ky, kx, a.Ho, a.Wo, iy, ix) && cs0 + xch[g] < Cs;
             const unsigned off = v ? (unsigned)((((xb[g] * Hi + iy) * Wi + ix) * Cs + cs0 + xch[g]) * (int)sizeof(T)) : OOB;
             dma16(rsx, off, sb + (wave * NPX + g) * 1024);
             xm[g] += KP;
@@ -1466,7 +1385,7 @@ bool wgrad_glds_supported(int dtype, int mode, const WgradArgs& a) {
 template <typename T, int MODE>
 static int try_wgrad_glds_mode(const WgradArgs& a, hipStream_t st) {
     const int Cin = a.C0 + a.C1;
-    constexpr int ntaps = GModeTraits<MODE>::NTAPS;
+    constexpr int ntaps = ModeTraits<MODE>::NTAPS;
     if (!wgrad_glds_supported(sizeof(T) == 2 ? MPU_BF16 : MPU_F32, MODE, a)) return 0;
     bool big = false;
     if constexpr (sizeof(T) == 2) big = Cin >= 128 && a.Cout >= 128 && (a.C1 == 0 || a.C0 % 128 == 0);

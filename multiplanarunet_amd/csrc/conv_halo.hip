@@ -16,38 +16,7 @@
 
 namespace mpu {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
 namespace {
-
-__device__ __forceinline__ i32x4 h_make_rsrc(const void* p, long bytes) {
-    const unsigned long long pa = (unsigned long long)p;
-    i32x4 r;
-    r.x = (int)(unsigned)pa; r.y = (int)((unsigned)(pa >> 32) & 0xffffu); r.z = (int)bytes; r.w = 0x00020000;
-    return r;
-}
-__device__ __forceinline__ void h_dma16(const i32x4& rsrc, unsigned voff, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                 :: "v"(voff), "s"(lds_addr), "s"(rsrc) : "memory");
-}
-constexpr unsigned HALO_POISON = 0x80001000u;                    // + any in-range byte offset (< 2 GiB - 8 KiB) stays >= num_records
-template <typename T> struct HMma;
-template <> struct HMma<bf16_t> {
-    static __device__ __forceinline__ void run(const uint4& a, const uint4& b, f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(s16x8, a), __builtin_bit_cast(s16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct HMma<float> {
-    static __device__ __forceinline__ void run(const uint4& a, const uint4& b, f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
-    }
-};
 
 // MODE: CONV3 (3x3 SAME: halo of one pixel) or UPCONV2 (nearest-upsample x2 + 2x2 SAME with TF's 0/1 padding: the
 // patch lives at the LOW resolution, output pixel (oy, ox) and tap (ky, kx) read low-res pixel ((oy+ky)>>1, (ox+kx)>>1))
@@ -107,9 +76,9 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(ConvArgs a) {
     constexpr unsigned OOB = 0xfffffff0u;
     const int Hi = MODE == UPCONV2 ? H / 2 : H, Wi = MODE == UPCONV2 ? W / 2 : W;     // input resolution
     const long npix = (long)a.B * Hi * Wi;
-    const i32x4 rs0 = h_make_rsrc(a.in0, npix * a.C0 * (long)sizeof(T));
-    const i32x4 rs1 = h_make_rsrc(a.in1 ? a.in1 : a.in0, a.in1 ? npix * a.C1 * (long)sizeof(T) : 0);
-    const i32x4 rsw = h_make_rsrc(a.w, a.w_elems * (long)sizeof(T));
+    const i32x4 rs0 = make_rsrc(a.in0, npix * a.C0 * (long)sizeof(T));
+    const i32x4 rs1 = make_rsrc(a.in1 ? a.in1 : a.in0, a.in1 ? npix * a.C1 * (long)sizeof(T) : 0);
+    const i32x4 rsw = make_rsrc(a.w, a.w_elems * (long)sizeof(T));
     const unsigned lds0 = (unsigned)(uintptr_t)smem;
     const unsigned ldsW = lds0 + Cfg::PATCH;
 
@@ -157,8 +126,8 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(ConvArgs a) {
                 const int ch = cbase + pchunk[k] * EPC;
                 unsigned off = (unsigned)((ppix[k] * Cs + ch) * (int)sizeof(T));
                 if (tail) off = ch < Cs ? off : OOB;
-                if (s1) h_dma16(rs1, off, lds0 + piece * 1024);
-                else    h_dma16(rs0, off, lds0 + piece * 1024);
+                if (s1) dma16(rs1, off, lds0 + piece * 1024);
+                else    dma16(rs0, off, lds0 + piece * 1024);
             }
         }
     };
@@ -250,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(ConvArgs a) {
 #pragma unroll
                 for (int i = 0; i < TN; ++i)
 #pragma unroll
-                    for (int j = 0; j < TM; ++j) HMma<T>::run(af[s][i], bf[s][j], acc[i][j]);
+                    for (int j = 0; j < TM; ++j) Mma<T>::run(af[s][i], bf[s][j], acc[i][j]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -268,15 +237,15 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(ConvArgs a) {
     // by the launcher), so a request is one add per piece; only a tail chunk masks channels
     unsigned wpo[GW];
 #pragma unroll
-    for (int g = 0; g < GW; ++g) wpo[g] = wlane[g] == OOB ? HALO_POISON : wlane[g];
+    for (int g = 0; g < GW; ++g) wpo[g] = wlane[g] == OOB ? DMA_POISON : wlane[g];
     auto request_w = [&](unsigned soff, int room, int stage) {
         const unsigned dst = ldsW + stage * Cfg::WSTAGE + wave * (BN / 4) * 128;
         if (room >= BKE) {
 #pragma unroll
-            for (int g = 0; g < GW; ++g) h_dma16(rsw, wpo[g] + soff, dst + g * 8 * 128);
+            for (int g = 0; g < GW; ++g) dma16(rsw, wpo[g] + soff, dst + g * 8 * 128);
         } else {
 #pragma unroll
-            for (int g = 0; g < GW; ++g) h_dma16(rsw, wch[g] < room ? wpo[g] + soff : HALO_POISON, dst + g * 8 * 128);
+            for (int g = 0; g < GW; ++g) dma16(rsw, wch[g] < room ? wpo[g] + soff : DMA_POISON, dst + g * 8 * 128);
         }
     };
     const unsigned w_tap_b = (unsigned)(a.w_tap_stride * (long)sizeof(T));
@@ -576,9 +545,9 @@ __global__ __launch_bounds__(512, 2) void conv_halo8_kernel(ConvArgs a) {
     constexpr unsigned OOB = 0xfffffff0u;
     const int Hi = MODE == UPCONV2 ? H / 2 : H, Wi = MODE == UPCONV2 ? W / 2 : W;
     const long npix = (long)a.B * Hi * Wi;
-    const i32x4 rs0 = h_make_rsrc(a.in0, npix * a.C0 * 2L);
-    const i32x4 rs1 = h_make_rsrc(a.in1 ? a.in1 : a.in0, a.in1 ? npix * a.C1 * 2L : 0);
-    const i32x4 rsw = h_make_rsrc(a.w, a.w_elems * 2L);
+    const i32x4 rs0 = make_rsrc(a.in0, npix * a.C0 * 2L);
+    const i32x4 rs1 = make_rsrc(a.in1 ? a.in1 : a.in0, a.in1 ? npix * a.C1 * 2L : 0);
+    const i32x4 rsw = make_rsrc(a.w, a.w_elems * 2L);
     const unsigned lds0 = (unsigned)(uintptr_t)smem;
     const unsigned ldsW = lds0 + 2 * Cfg::PATCH;
 
@@ -618,7 +587,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo8_kernel(ConvArgs a) {
             unsigned off = (unsigned)((ppix[k] * Cs + ch) * 2);
             if (tail) off = ch < Cs ? off : OOB;
             const unsigned dst = lds0 + buf * Cfg::PATCH + __builtin_amdgcn_readfirstlane(ppiece[k]) * 1024;
-            h_dma16(qrs, off, dst);
+            dma16(qrs, off, dst);
         }
     };
     unsigned wlane[GW]; int wch[GW];
@@ -641,7 +610,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo8_kernel(ConvArgs a) {
 #pragma unroll
         for (int g = 0; g < GW; ++g) {
             const unsigned off = (wch[g] < room && wlane[g] != OOB) ? wlane[g] + soff : OOB;
-            h_dma16(rsw, off, dst + g * 8 * 128);
+            dma16(rsw, off, dst + g * 8 * 128);
         }
         w_tapoff += w_tap_bytes;
         if (++w_tap == NT) { w_tap = 0; w_tapoff = 0; ++w_cc; }
@@ -684,7 +653,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo8_kernel(ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < TN; ++i)
 #pragma unroll
-            for (int j = 0; j < TM; ++j) HMma<T>::run(af[set][i], bf[set][j], acc[i][j]);
+            for (int j = 0; j < TM; ++j) Mma<T>::run(af[set][i], bf[set][j], acc[i][j]);
     };
 
     // --- pipeline ---------------------------------------------------------------------------
@@ -790,15 +759,15 @@ __global__ __launch_bounds__(512, 2) void conv_halo8_kernel(ConvArgs a) {
         auto ksteps_of = [&](int room) { return room >= BKE ? 4 : (room + 15) / 16; };
         unsigned wpo[GW];                                         // (poison offset: see conv_halo_kernel)
 #pragma unroll
-        for (int g = 0; g < GW; ++g) wpo[g] = wlane[g] == OOB ? HALO_POISON : wlane[g];
+        for (int g = 0; g < GW; ++g) wpo[g] = wlane[g] == OOB ? DMA_POISON : wlane[g];
         auto request_w = [&](unsigned soff, int room, int stage) {         // weights of one tap: GW pieces per wave
             const unsigned dst = ldsW + stage * Cfg::WSTAGE + wave * (BN / NW) * 128;
             if (room >= BKE) {
 #pragma unroll
-                for (int g = 0; g < GW; ++g) h_dma16(rsw, wpo[g] + soff, dst + g * 8 * 128);
+                for (int g = 0; g < GW; ++g) dma16(rsw, wpo[g] + soff, dst + g * 8 * 128);
             } else {
 #pragma unroll
-                for (int g = 0; g < GW; ++g) h_dma16(rsw, wch[g] < room ? wpo[g] + soff : HALO_POISON, dst + g * 8 * 128);
+                for (int g = 0; g < GW; ++g) dma16(rsw, wch[g] < room ? wpo[g] + soff : DMA_POISON, dst + g * 8 * 128);
             }
         };
         const unsigned w_tap_b = (unsigned)(a.w_tap_stride * 2L);
@@ -880,7 +849,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo8_kernel(ConvArgs a) {
 #pragma unroll
                 for (int i = 0; i < TN; ++i)
 #pragma unroll
-                    for (int j = 0; j < TM; ++j) HMma<T>::run(fa[0][i], fb[0][j], acc[i][j]);
+                    for (int j = 0; j < TM; ++j) Mma<T>::run(fa[0][i], fb[0][j], acc[i][j]);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (!WREQ_IN_L) {   // weights three taps ahead: of this chunk, or the first taps of the next one
                     const int wt = tap + 3;
@@ -891,7 +860,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo8_kernel(ConvArgs a) {
 #pragma unroll
                 for (int i = 0; i < TN; ++i)
 #pragma unroll
-                    for (int j = 0; j < TM; ++j) HMma<T>::run(fa[1][i], fb[1][j], acc[i][j]);
+                    for (int j = 0; j < TM; ++j) Mma<T>::run(fa[1][i], fb[1][j], acc[i][j]);
                 __builtin_amdgcn_sched_barrier(0);
                 if (tap < PTAPS && hasnext) {
 #pragma unroll
@@ -900,7 +869,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo8_kernel(ConvArgs a) {
                             const int ch = ncbase + pchunk[k] * EPC;
                             unsigned off = (unsigned)((ppix[k] * nCs + ch) * 2);
                             if (nCs - ncbase < BKE) off = ch < nCs ? off : OOB;
-                            h_dma16(qrs, off, lds0 + pnext + __builtin_amdgcn_readfirstlane(ppiece[k]) * 1024);
+                            dma16(qrs, off, lds0 + pnext + __builtin_amdgcn_readfirstlane(ppiece[k]) * 1024);
                         }
                     }
                 }
@@ -911,7 +880,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo8_kernel(ConvArgs a) {
 #pragma unroll
                         for (int i = 0; i < TN; ++i)
 #pragma unroll
-                            for (int j = 0; j < TM; ++j) HMma<T>::run(fa[s_][i], fb[s_][j], acc[i][j]);
+                            for (int j = 0; j < TM; ++j) Mma<T>::run(fa[s_][i], fb[s_][j], acc[i][j]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 if (prio_c) __builtin_amdgcn_s_setprio(0);
@@ -1113,7 +1082,7 @@ int launch_halo8_cfg_n(const ConvArgs& a_in, hipStream_t st) {
     a.dbg_buf = stamp_buffer();
     a.dbg = 2;                                                   // (SCHED 2: s_setprio 1 in the load phase, as SCHED 1 has it compiled in)
     if (prof_on()) prof_begin(PROF_CONV, a.flops > 0 ? a.flops : 2.0 * M * a.Cout * Cfg::NT * (a.C0 + a.C1), st);
-    a.xcd = env(ENV_XCD_TILES) != 0;
+    a.xcd = 1;
     launch_k(kern, dim3((unsigned)tiles), dim3(512), Cfg::SMEM, st, a);
     if (prof_on()) prof_end(st);
     return launch_ok();
@@ -1145,7 +1114,7 @@ int launch_halo_cfg(const ConvArgs& a_in, hipStream_t st) {
     if (a.pooled && a.pooled_done && MODE == CONV3 && !a.mask && !(a.Ho & 1) && !(a.Wo & 1) && TH % 2 == 0) *a.pooled_done = 1;
     else a.pooled = nullptr;
     if (prof_on()) prof_begin(PROF_CONV, a.flops > 0 ? a.flops : 2.0 * M * a.Cout * Cfg::NT * (a.C0 + a.C1), st);
-    a.xcd = env(ENV_XCD_TILES) != 0;
+    a.xcd = 1;
     launch_k(kern, dim3((unsigned)tiles), dim3(256), Cfg::SMEM, st, a);
     if (prof_on()) prof_end(st);
     return launch_ok();
@@ -1170,11 +1139,11 @@ int try_conv_halo(int dtype, int mode, const ConvArgs& a, hipStream_t st) {
     if ((mode != CONV3 && mode != UPCONV2) || a.Wo < 32 || a.Ho < 4) return 0;
     int rc;
     {   // round 3: one 8-wave workgroup per CU with a double-buffered patch, for grids of about one workgroup per CU
-        // (configs[1] levels 1-2: the single-buffer kernel's patch bursts are exposed there). MPU_HALO8=0 disables.
+        // (configs[1] levels 1-2: the single-buffer kernel's patch bursts are exposed there).
         // Grids of 192..400 workgroups (sweeps R3ag / R3aa: below, half the CUs idle; above, two rounds of one
         // workgroup per CU lose to the 4-wave kernel's two workgroups per CU).
-        const bool h8 = env(ENV_HALO8) != 0; constexpr long h8_max = 400, h8_min = 192;
-        if (h8 && dtype == MPU_BF16 && a.Ho % 8 == 0 && !a.head_w && (mode == CONV3 || !(a.Wo & 1))) {
+        constexpr long h8_max = 400, h8_min = 192;
+        if (dtype == MPU_BF16 && a.Ho % 8 == 0 && !a.head_w && (mode == CONV3 || !(a.Wo & 1))) {
             const long pt = (long)a.B * (a.Ho / 8) * cdiv(a.Wo, 32);
             const long g128 = pt * cdiv(a.Cout, 128), g64 = pt * cdiv(a.Cout, 64);
             const bool wide = a.Cout > 64 && g128 >= h8_min;
@@ -1187,8 +1156,7 @@ int try_conv_halo(int dtype, int mode, const ConvArgs& a, hipStream_t st) {
         }
     }
     if (mode == UPCONV2) {                       // low-resolution patch variant of the up-convolution
-        const bool up_on = env(ENV_HALO_UPCONV) != 0;
-        if (!up_on || dtype != MPU_BF16 || (a.Ho & 3) || (a.Wo & 1)) return 0;
+        if (dtype != MPU_BF16 || (a.Ho & 3) || (a.Wo & 1)) return 0;
         // 8-row tiles on large grids (predict batches): twice the work per workgroup for the same patch / weight prologue
         const long up8_min = env(ENV_HALO_UP8_MIN);
         const long t8 = (long)a.B * cdiv(a.Ho, 8) * cdiv(a.Wo, 32) * cdiv(a.Cout, a.Cout > 64 ? 128 : 64);

@@ -35,27 +35,7 @@
 
 namespace mpu {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
 namespace {
-
-__device__ __forceinline__ i32x4 x_make_rsrc(const void* p, long bytes) {
-    const unsigned long long pa = (unsigned long long)p;
-    i32x4 r;
-    r.x = (int)(unsigned)pa; r.y = (int)((unsigned)(pa >> 32) & 0xffffu); r.z = (int)bytes; r.w = 0x00020000;
-    return r;
-}
-__device__ __forceinline__ void x_dma16(const i32x4& rsrc, unsigned voff, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                 :: "v"(voff), "s"(lds_addr), "s"(rsrc) : "memory");
-}
-constexpr unsigned X_POISON = 0x80001000u;                       // + any in-range byte offset (< 2 GiB - 8 KiB) stays >= num_records
-__device__ __forceinline__ void x_mma(const uint4& a, const uint4& b, f32x16& c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(s16x8, a), __builtin_bit_cast(s16x8, b), c, 0, 0, 0);
-}
 
 struct Halo16Cfg {
     static constexpr int NT = 9, KW = 3, BN = 128, TH = 16, TW = 32, PW = TW + 2, PH = TH + 2;
@@ -113,9 +93,9 @@ __global__ __launch_bounds__(512, 2) void conv_halo16p_kernel(ConvArgs a, int pt
     const int nblocks = (nc0 + nc1) / 2;
     constexpr unsigned OOB = 0xfffffff0u;
     const long npix = (long)a.B * H * W;
-    const i32x4 rs0 = x_make_rsrc(a.in0, npix * a.C0 * 2L);
-    const i32x4 rs1 = x_make_rsrc(a.in1 ? a.in1 : a.in0, a.in1 ? npix * a.C1 * 2L : 0);
-    const i32x4 rsw = x_make_rsrc(a.w, a.w_elems * 2L);
+    const i32x4 rs0 = make_rsrc(a.in0, npix * a.C0 * 2L);
+    const i32x4 rs1 = make_rsrc(a.in1 ? a.in1 : a.in0, a.in1 ? npix * a.C1 * 2L : 0);
+    const i32x4 rsw = make_rsrc(a.w, a.w_elems * 2L);
     const unsigned lds0 = (unsigned)(uintptr_t)smem;
     const unsigned ldsW = lds0 + 2 * Cfg::PBUF;
 
@@ -144,18 +124,18 @@ __global__ __launch_bounds__(512, 2) void conv_halo16p_kernel(ConvArgs a, int pt
         const int pix = v ? (tb * H + iy) * W + ix : (int)npix;
         const int ch = cbase + ((dslot ^ ((pr >> 2) & 3)) * EPC);
         const unsigned off = (unsigned)((pix * Cs + ch) * 2);
-        x_dma16(qrs, off, lds0 + pb * Cfg::PBUF + __builtin_amdgcn_readfirstlane(q) * 1024);
+        dma16(qrs, off, lds0 + pb * Cfg::PBUF + __builtin_amdgcn_readfirstlane(q) * 1024);
     };
     unsigned wpo;
     {
         const int rl = wave * 16 + drow;
         const int n = n0 + rl;
-        wpo = n < a.Cout ? (unsigned)((long)n * a.w_row_stride * 2L) + (unsigned)(((dslot ^ ((rl >> 2) & 3)) * EPC) * 2) : X_POISON;
+        wpo = n < a.Cout ? (unsigned)((long)n * a.w_row_stride * 2L) + (unsigned)(((dslot ^ ((rl >> 2) & 3)) * EPC) * 2) : DMA_POISON;
     }
     const unsigned w_tap_b = (unsigned)(a.w_tap_stride * 2L);
     auto request_item = [&](int c, int tap, int stage, int slot2) {
         const unsigned soff = (unsigned)tap * w_tap_b + chunk_woff(c);
-        x_dma16(rsw, wpo + soff, ldsW + stage * Cfg::WSTAGE + slot2 * (Cfg::WSTAGE / 2) + wave * 1024);
+        dma16(rsw, wpo + soff, ldsW + stage * Cfg::WSTAGE + slot2 * (Cfg::WSTAGE / 2) + wave * 1024);
     };
 
     f32x16 acc[TN][TM];
@@ -266,7 +246,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo16p_kernel(ConvArgs a, int pt
 #pragma unroll
                 for (int i = 0; i < TN; ++i)
 #pragma unroll
-                    for (int j = 0; j < TM; ++j) x_mma(fa[0][0][i], fb[0][0][j], acc[i][j]);
+                    for (int j = 0; j < TM; ++j) Mma<bf16_t>::run(fa[0][0][i], fb[0][0][j], acc[i][j]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < TN; ++i) fa[1][0][i] = *(const uint4*)(smem + wst + (Cfg::WSTAGE / 2) + i * 32 * 64);
@@ -274,7 +254,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo16p_kernel(ConvArgs a, int pt
 #pragma unroll
                 for (int i = 0; i < TN; ++i)
 #pragma unroll
-                    for (int j = 0; j < TM; ++j) x_mma(fa[0][1][i], fb[0][1][j], acc[i][j]);
+                    for (int j = 0; j < TM; ++j) Mma<bf16_t>::run(fa[0][1][i], fb[0][1][j], acc[i][j]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < TN; ++i) fa[1][1][i] = *(const uint4*)(smem + (wst ^ 32u) + (Cfg::WSTAGE / 2) + i * 32 * 64);
@@ -283,13 +263,13 @@ __global__ __launch_bounds__(512, 2) void conv_halo16p_kernel(ConvArgs a, int pt
 #pragma unroll
                 for (int i = 0; i < TN; ++i)
 #pragma unroll
-                    for (int j = 0; j < TM; ++j) x_mma(fa[1][0][i], fb[1][0][j], acc[i][j]);
+                    for (int j = 0; j < TM; ++j) Mma<bf16_t>::run(fa[1][0][i], fb[1][0][j], acc[i][j]);
                 __builtin_amdgcn_sched_barrier(0);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
                 for (int i = 0; i < TN; ++i)
 #pragma unroll
-                    for (int j = 0; j < TM; ++j) x_mma(fa[1][1][i], fb[1][1][j], acc[i][j]);
+                    for (int j = 0; j < TM; ++j) Mma<bf16_t>::run(fa[1][1][i], fb[1][1][j], acc[i][j]);
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_barrier();
                 stb += Cfg::WSTAGE; if (stb == Cfg::NWS * Cfg::WSTAGE) stb = 0;

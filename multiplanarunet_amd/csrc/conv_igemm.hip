@@ -1,291 +1,18 @@
-// NHWC implicit-GEMM convolution kernels for gfx950 MFMA.
+// Convolution dispatch (launch_conv: the forward / data-gradient schedules of conv_*.hip by shape) and the
+// weight-gradient launcher with its register-staged fallback kernel and the split-K reductions.
 //
-//   conv_igemm_kernel : forward conv and data-gradient (same kernel, different
-//                       packed weights). D[n][m] = sum_k W[n][k] * X[m][k] with
-//                       n = output channel (MFMA rows), m = output pixel (MFMA
-//                       cols), k = (tap, input channel). Modes:
+//   wgrad_igemm_kernel: weight gradient dW[tap][ci][co] = sum_m X[m@tap][ci] dZ[m][co]
+//                       split over the pixel dimension, deterministic second stage. Modes:
 //                         CONV3   3x3 SAME stride 1               (unet.py:120-179)
 //                         UPCONV2 UpSampling2D(2) + 2x2 SAME conv (unet.py:159-163;
 //                                 TF SAME for k=2 pads 0 top/left, 1 bottom/right)
-//                         CONV3S2 3x3 stride 2 pad 1: the data-gradient of UPCONV2
-//                                 with tap-combined weights
 //                         CONV1   1x1
-//   wgrad_igemm_kernel: weight gradient dW[tap][ci][co] = sum_m X[m@tap][ci] dZ[m][co]
-//                       split over the pixel dimension, deterministic second stage.
-//
-// Tiling: 256 threads = 4 waves (64 lanes each); K rows of 128 B (64 bf16 / 32 f32)
-// staged global -> VGPR -> LDS (rows padded to 144 B: conflict-free ds_read_b128),
-// double buffered, one barrier per K step, next tile's global loads in flight
-// under the MFMAs. bf16: v_mfma_f32_32x32x16_bf16; f32: v_mfma_f32_32x32x2_f32
-// (exact f32). The k-order inside a row is permuted identically for both
-// operands, which leaves the dot product unchanged.
+//                       It takes the shapes that neither wgrad_taps nor wgrad_glds takes.
 #include <stdlib.h>
 #include "kernels.h"
 #include "reduce.h"
 
 namespace mpu {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-template <int MODE> struct ModeTraits;
-template <> struct ModeTraits<CONV3>   { static constexpr int NTAPS = 9, KW = 3; };
-template <> struct ModeTraits<UPCONV2> { static constexpr int NTAPS = 4, KW = 2; };
-template <> struct ModeTraits<CONV3S2> { static constexpr int NTAPS = 9, KW = 3; };
-template <> struct ModeTraits<CONV1>   { static constexpr int NTAPS = 1, KW = 1; };
-
-// input pixel (iy,ix) read by output pixel (oy,ox) at tap (ky,kx); false = zero padding
-template <int MODE>
-__device__ __forceinline__ bool tap_src(int oy, int ox, int ky, int kx, int Ho, int Wo, int& iy, int& ix) {
-    if (MODE == CONV3) {
-        iy = oy + ky - 1; ix = ox + kx - 1;
-        return (unsigned)iy < (unsigned)Ho && (unsigned)ix < (unsigned)Wo;
-    } else if (MODE == UPCONV2) {
-        const int uy = oy + ky, ux = ox + kx;
-        iy = uy >> 1; ix = ux >> 1;
-        return uy < Ho && ux < Wo;
-    } else if (MODE == CONV3S2) {
-        iy = 2 * oy + ky - 1; ix = 2 * ox + kx - 1;
-        return (unsigned)iy < (unsigned)(2 * Ho) && (unsigned)ix < (unsigned)(2 * Wo);
-    } else {
-        iy = oy; ix = ox;
-        return true;
-    }
-}
-template <int MODE> __device__ __forceinline__ int in_h(int Ho) {
-    return MODE == UPCONV2 ? Ho / 2 : (MODE == CONV3S2 ? Ho * 2 : Ho);
-}
-
-template <typename T> struct Mma;
-template <> struct Mma<bf16_t> {
-    static __device__ __forceinline__ void run(const uint4& a, const uint4& b, f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(s16x8, a), __builtin_bit_cast(s16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<float> {
-    static __device__ __forceinline__ void run(const uint4& a, const uint4& b, f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
-    }
-};
-
-// XCD-aware bijective remap: consecutive logical tiles land on one XCD (one L2).
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
-
-template <typename T, int MODE, int BN, int BM, int WN, int WM>
-__global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a) {
-    constexpr int EPC = 16 / sizeof(T);          // elements per 16-B chunk
-    constexpr int BKE = 128 / sizeof(T);         // elements per K row
-    constexpr int LROW = 144;
-    constexpr int NW_ROWS = BN / 32, NP_ROWS = BM / 32;
-    constexpr int TN = WN / 32, TM = WM / 32;
-    constexpr int WAVES_N = BN / WN;
-    constexpr int NTAPS = ModeTraits<MODE>::NTAPS, KW = ModeTraits<MODE>::KW;
-    constexpr int STAGE = (BN + BM) * LROW;
-    static_assert((BN / WN) * (BM / WM) == 4, "4 waves");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wn = wave % WAVES_N, wm = wave / WAVES_N;
-    const int tiles_n = (a.Cout + BN - 1) / BN;
-    const int logical = xcd_remap(blockIdx.x, gridDim.x);
-    const int n0 = (logical % tiles_n) * BN;
-    const long m0 = (long)(logical / tiles_n) * BM;
-    // K steps: for every tap, the 128-byte channel rows of source 0, then those of source 1
-    // (a row never straddles the two concat sources, so the source is wave-uniform)
-    const int nch0 = (a.C0 + BKE - 1) / BKE, nch1 = (a.C1 + BKE - 1) / BKE;
-    const int nchunks = nch0 + nch1;
-    const int nit = NTAPS * nchunks;
-    const int Hi = in_h<MODE>(a.Ho), Wi = in_h<MODE>(a.Wo);
-    const long M = (long)a.B * a.Ho * a.Wo;
-    constexpr unsigned OOB = 0xfffffff0u;           // buffer loads beyond num_records return 0
-    const long npix = (long)a.B * Hi * Wi;
-    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)a.in0, 0, (int)(npix * a.C0 * (long)sizeof(T)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(a.in1 ? a.in1 : a.in0), 0, (int)(a.in1 ? npix * a.C1 * (long)sizeof(T) : 0), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)a.w, 0, (int)(a.w_elems * (long)sizeof(T)), 0x00020000);
-
-    const int ck = tid & 7, r0 = tid >> 3;
-    int pb[NP_ROWS], py[NP_ROWS], px[NP_ROWS];
-#pragma unroll
-    for (int i = 0; i < NP_ROWS; ++i) {
-        const long m = m0 + r0 + 32 * i;
-        if (m < M) {
-            const int ox = (int)(m % a.Wo); const long t = m / a.Wo;
-            const int oy = (int)(t % a.Ho); const int b = (int)(t / a.Ho);
-            pb[i] = b * Hi * Wi; py[i] = oy; px[i] = ox;
-        } else { pb[i] = -1; py[i] = 0; px[i] = 0; }
-    }
-    unsigned wrow[NW_ROWS];                          // byte offset of this thread's weight rows
-#pragma unroll
-    for (int i = 0; i < NW_ROWS; ++i) {
-        const int n = n0 + r0 + 32 * i;
-        wrow[i] = n < a.Cout ? (unsigned)((long)n * a.w_row_stride * (long)sizeof(T)) : OOB;
-    }
-
-    auto gload = [&](uint4 (&wr)[NW_ROWS], uint4 (&pr)[NP_ROWS], int tap, int cc) {
-        const bool s1 = cc >= nch0;
-        const int cbase = (s1 ? cc - nch0 : cc) * BKE;
-        const int Cs = s1 ? a.C1 : a.C0;
-        const int ch = cbase + ck * EPC;
-        const bool chv = ch < Cs;
-        const unsigned wk = (unsigned)(((long)tap * a.w_tap_stride + (s1 ? a.C0 : 0) + ch) * (long)sizeof(T));
-#pragma unroll
-        for (int i = 0; i < NW_ROWS; ++i) {
-            const unsigned off = (chv && wrow[i] != OOB) ? wrow[i] + wk : OOB;
-            wr[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsw, off, 0, 0));
-        }
-        const int ky = tap / KW, kx = tap % KW;
-#pragma unroll
-        for (int i = 0; i < NP_ROWS; ++i) {
-            int iy, ix;
-            const bool v = tap_src<MODE>(py[i], px[i], ky, kx, a.Ho, a.Wo, iy, ix) && chv && pb[i] >= 0;
-            const unsigned off = v ? (unsigned)(((pb[i] + iy * Wi + ix) * Cs + ch) * (int)sizeof(T)) : OOB;
-            pr[i] = s1 ? __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs1, off, 0, 0))
-                       : __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs0, off, 0, 0));
-        }
-    };
-    auto lstore = [&](const uint4 (&wr)[NW_ROWS], const uint4 (&pr)[NP_ROWS], int buf) {
-        unsigned char* base = smem + buf * STAGE + r0 * LROW + ck * 16;
-#pragma unroll
-        for (int i = 0; i < NW_ROWS; ++i) *(uint4*)(base + i * 32 * LROW) = wr[i];
-#pragma unroll
-        for (int i = 0; i < NP_ROWS; ++i) *(uint4*)(base + BN * LROW + i * 32 * LROW) = pr[i];
-    };
-
-    f32x16 acc[TN][TM];
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int j = 0; j < TM; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    auto compute = [&](int buf) {
-        const unsigned char* Wb = smem + buf * STAGE + (wn * WN + (lane & 31)) * LROW + (lane >> 5) * 16;
-        const unsigned char* Pb = smem + buf * STAGE + BN * LROW + (wm * WM + (lane & 31)) * LROW + (lane >> 5) * 16;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            uint4 af[TN], bf[TM];
-#pragma unroll
-            for (int i = 0; i < TN; ++i) af[i] = *(const uint4*)(Wb + i * 32 * LROW + s * 32);
-#pragma unroll
-            for (int j = 0; j < TM; ++j) bf[j] = *(const uint4*)(Pb + j * 32 * LROW + s * 32);
-#pragma unroll
-            for (int i = 0; i < TN; ++i)
-#pragma unroll
-                for (int j = 0; j < TM; ++j) Mma<T>::run(af[i], bf[j], acc[i][j]);
-        }
-    };
-
-    // Software pipeline, prefetch distance 2: tile t is consumed from LDS[t&1] while tile t+1
-    // waits in one register set and the loads of tile t+2 are issued into the other.
-    uint4 wA[NW_ROWS], pA[NP_ROWS], wB[NW_ROWS], pB[NP_ROWS];
-    int tapN = 0, ccN = 0;
-    auto advance = [&]() { if (++ccN == nchunks) { ccN = 0; ++tapN; } };
-    gload(wA, pA, tapN, ccN); advance();
-    if (nit > 1) { gload(wB, pB, tapN, ccN); advance(); }
-    lstore(wA, pA, 0);
-    __syncthreads();
-    for (int it = 0; it < nit; it += 2) {
-        if (it + 2 < nit) { gload(wA, pA, tapN, ccN); advance(); }
-        compute(0);
-        if (it + 1 < nit) lstore(wB, pB, 1);
-        __syncthreads();
-        if (it + 1 >= nit) break;
-        if (it + 3 < nit) { gload(wB, pB, tapN, ccN); advance(); }
-        compute(1);
-        if (it + 2 < nit) lstore(wA, pA, 0);
-        __syncthreads();
-    }
-
-    // epilogue. The last loop iteration ended with a barrier, so the staging LDS is free:
-    //   1. bias of this tile -> LDS; 2. +bias, ReLU, convert, write the [BM][BN] tile to LDS
-    //   (row = pixel); 3. 16-byte coalesced row stores (+ coalesced ReLU-mask loads).
-    constexpr int OROW = BN * (int)sizeof(T) + 16;          // padded output row
-    static_assert(BM * OROW + 3 * BN * 4 <= 2 * STAGE, "epilogue tile must fit the staging LDS");
-    float* sbias = (float*)(smem + BM * OROW);
-    if (tid < BN) {
-        const bool nv = n0 + tid < a.Cout;
-        sbias[tid] = (a.bias && nv) ? a.bias[n0 + tid] : 0.f;
-        sbias[BN + tid] = (a.post_scale && nv) ? a.post_scale[n0 + tid] : 1.f;
-        sbias[2 * BN + tid] = (a.post_scale && nv) ? a.post_shift[n0 + tid] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < TM; ++j) {
-        const int ml = wm * WM + j * 32 + (lane & 31);
-#pragma unroll
-        for (int i = 0; i < TN; ++i) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int nl = wn * WN + i * 32 + 8 * q + 4 * (lane >> 5);
-                const float4 bq = *(const float4*)(sbias + nl);
-                float v[4] = {acc[i][j][4 * q] + bq.x, acc[i][j][4 * q + 1] + bq.y,
-                              acc[i][j][4 * q + 2] + bq.z, acc[i][j][4 * q + 3] + bq.w};
-                if (a.relu) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                if (a.post_scale) {
-                    const float4 sq = *(const float4*)(sbias + BN + nl), hq = *(const float4*)(sbias + 2 * BN + nl);
-                    v[0] = v[0] * sq.x + hq.x; v[1] = v[1] * sq.y + hq.y;
-                    v[2] = v[2] * sq.z + hq.z; v[3] = v[3] * sq.w + hq.w;
-                }
-                unsigned char* dst = smem + ml * OROW + nl * (int)sizeof(T);
-                if (sizeof(T) == 2) {
-                    uint2 pk;
-                    pk.x = f32x2_to_bf16x2(v[0], v[1]);
-                    pk.y = f32x2_to_bf16x2(v[2], v[3]);
-                    *(uint2*)dst = pk;
-                } else {
-                    *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    {
-        constexpr int CPRO = BN * (int)sizeof(T) / 16;       // 16-byte chunks per output row
-        T* out = (T*)a.out; const T* mask = (const T*)a.mask;
-        for (int idx = tid; idx < BM * CPRO; idx += 256) {
-            const int row = idx / CPRO, c = idx % CPRO;
-            const long m = m0 + row;
-            const int n = n0 + c * EPC;
-            if (m >= M || n >= a.Cout) continue;
-            uint4 val = *(const uint4*)(smem + row * OROW + c * 16);
-            const long o = m * a.Cout + n;
-            if (mask) {
-                const uint4 mk = *(const uint4*)(mask + o);
-                if (sizeof(T) == 2) {
-                    // bf16 > 0  <=>  sign bit clear and magnitude non-zero
-                    auto keep = [](uint32_t mw, uint32_t vw) {
-                        const uint32_t lo = ((mw & 0x8000u) == 0 && (mw & 0x7fffu) != 0) ? 0x0000ffffu : 0u;
-                        const uint32_t hi = ((mw & 0x80000000u) == 0 && (mw & 0x7fff0000u) != 0) ? 0xffff0000u : 0u;
-                        return vw & (lo | hi);
-                    };
-                    val.x = keep(mk.x, val.x); val.y = keep(mk.y, val.y);
-                    val.z = keep(mk.z, val.z); val.w = keep(mk.w, val.w);
-                } else {
-                    if (!(__uint_as_float(mk.x) > 0.f)) val.x = 0;
-                    if (!(__uint_as_float(mk.y) > 0.f)) val.y = 0;
-                    if (!(__uint_as_float(mk.z) > 0.f)) val.z = 0;
-                    if (!(__uint_as_float(mk.w) > 0.f)) val.w = 0;
-                }
-            }
-            *(uint4*)(out + o) = val;
-        }
-    }
-}
 
 // ------------------------------------------------------------------------- //
 // weight gradient
@@ -666,66 +393,12 @@ int flush_wgrad_group(int dtype, WgradGroup& g, hipStream_t st, int which) {
     return rc;
 }
 
-// MPU_CONV_IMPL=regs selects the register-staged kernel of this file; default is the LDS-DMA
-// kernel of conv_glds.hip (same tiling, same results).
-static int conv_impl() {
-    const int impl = (int)env(ENV_CONV_IMPL);
-    return impl;
-}
-
 // ------------------------------------------------------------------------- //
 // host-side launchers (internal C++ API used by unet.hip and the op-level ABI)
 // ------------------------------------------------------------------------- //
-template <typename T, int MODE, int BN, int BM, int WN, int WM>
-static int launch_conv_cfg(const ConvArgs& a_in, hipStream_t st) {
-    constexpr int SMEM = 2 * (BN + BM) * 144;
-    auto kern = conv_igemm_kernel<T, MODE, BN, BM, WN, WM>;
-    ConvArgs a = a_in;
-    if (a.w_elems <= 0) a.w_elems = (ModeTraits<MODE>::NTAPS - 1) * a.w_tap_stride + (long)a.Cout * a.w_row_stride;
-    static unsigned long long attr_set = 0;
-    if (first_use_on_device(attr_set)) {
-        MPU_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-        mark_used_on_device(attr_set);
-    }
-    const long M = (long)a.B * a.Ho * a.Wo;
-    const long tiles = (long)cdiv(a.Cout, BN) * cdiv(M, BM);
-    {   // 32-bit buffer offsets: every operand must stay below 2 GiB
-        constexpr int NT = ModeTraits<MODE>::NTAPS;
-        const long hi = MODE == UPCONV2 ? a.Ho / 2 : (MODE == CONV3S2 ? a.Ho * 2 : a.Ho);
-        const long wi = MODE == UPCONV2 ? a.Wo / 2 : (MODE == CONV3S2 ? a.Wo * 2 : a.Wo);
-        const long cmax = a.C0 > a.C1 ? a.C0 : a.C1;
-        if ((long)a.B * hi * wi * cmax * (long)sizeof(T) >= (1L << 31) ||
-            ((NT - 1) * a.w_tap_stride + (long)a.Cout * a.w_row_stride) * (long)sizeof(T) >= (1L << 31))
-            return fail(MPU_EUNSUPPORTED, "%s", "conv: operand larger than 2 GiB (split the batch)");
-    }
-    if (prof_on()) {
-        const int taps = MODE == UPCONV2 ? 4 : (MODE == CONV1 ? 1 : 9);
-        prof_begin(PROF_CONV, a.flops > 0 ? a.flops : 2.0 * M * a.Cout * taps * (a.C0 + a.C1), st);
-    }
-    launch_k(kern, dim3((unsigned)tiles), dim3(256), SMEM, st, a);
-    if (prof_on()) prof_end(st);
-    return launch_ok();
-}
-
-template <typename T, int MODE>
-static int launch_conv_mode(const ConvArgs& a, hipStream_t st) {
-    const long M = (long)a.B * a.Ho * a.Wo;
-    const long t128 = (long)cdiv(a.Cout, 128) * cdiv(M, 128);
-    const long t64x128 = (long)cdiv(a.Cout, 64) * cdiv(M, 128);
-    if (a.Cout > 64 && t128 >= 384) return launch_conv_cfg<T, MODE, 128, 128, 64, 64>(a, st);
-    if (t64x128 >= 384 || a.Cout <= 64) {
-        if (M >= 128 * 64) return launch_conv_cfg<T, MODE, 64, 128, 64, 32>(a, st);
-    }
-    return launch_conv_cfg<T, MODE, 64, 64, 32, 32>(a, st);
-}
-
-static int halo_on() {
-    return (int)env(ENV_CONV_HALO);
-}
-
 static int launch_conv_impl(int dtype, int mode, const ConvArgs& a, hipStream_t st) {
     if (a.stats_rows) *a.stats_rows = 0;          // set by the schedules that produce the fused BN statistics
-    if (a.x3 && (conv_impl() != 1 || dtype != MPU_F32 || mode == CONV1))   // (packed hi | lo words: the LDS-DMA f32 kernels only)
+    if (a.x3 && (dtype != MPU_F32 || mode == CONV1))   // (packed hi | lo words: the LDS-DMA f32 kernels only)
         return fail(MPU_EUNSUPPORTED, "%s", "conv: split-bf16 products (f32x3) need the LDS-DMA kernels, f32 tensors and a 3x3 / 2x2 layer");
     auto note = [&](const char* sched) {
         if (sched_log_on())
@@ -733,38 +406,19 @@ static int launch_conv_impl(int dtype, int mode, const ConvArgs& a, hipStream_t 
                        a.C0 + a.C1, a.Cout, a.bias ? 0 : 1, (a.pooled_done && *a.pooled_done) ? 1 : 0,
                        (a.head_done && *a.head_done) ? 1 : 0);
     };
-    if (conv_impl() == 1) {
-        if (halo_on()) {
-            const int c = try_conv_c8(dtype, mode, a, st);
-            if (c != 0) { note("c8"); return c < 0 ? c : MPU_OK; }
-            const int w = try_conv_ws(dtype, mode, a, st);
-            if (w != 0) { note("ws"); return w < 0 ? w : MPU_OK; }
-            const int x = try_conv_halo16(dtype, mode, a, st);
-            if (x != 0) { note("halo16p"); return x < 0 ? x : MPU_OK; }
-            const int h = try_conv_halo(dtype, mode, a, st);
-            if (h != 0) { note(h == 2 ? "halo8" : "halo"); return h < 0 ? h : MPU_OK; }
-        }
-        if (halo_on()) {
-            const int k = try_conv_deepk(dtype, mode, a, st);
-            if (k != 0) { note("deepk"); return k < 0 ? k : MPU_OK; }
-        }
-        const int rc = launch_conv_glds(dtype, mode, a, st);
-        note(last_glds_schedule());
-        return rc;
-    }
-    note("regs");
-#define MPU_CONV_CASE(TT)                                                          \
-    switch (mode) {                                                                \
-        case CONV3: return launch_conv_mode<TT, CONV3>(a, st);                     \
-        case UPCONV2: return launch_conv_mode<TT, UPCONV2>(a, st);                 \
-        case CONV3S2: return launch_conv_mode<TT, CONV3S2>(a, st);                 \
-        case CONV1: return launch_conv_mode<TT, CONV1>(a, st);                     \
-        default: return fail(MPU_EINVAL, "%s", "conv: bad mode");                  \
-    }
-    if (dtype == MPU_BF16) { MPU_CONV_CASE(bf16_t) }
-    if (dtype == MPU_F32) { MPU_CONV_CASE(float) }
-#undef MPU_CONV_CASE
-    return fail(MPU_EINVAL, "%s", "conv: bad dtype");
+    const int c = try_conv_c8(dtype, mode, a, st);
+    if (c != 0) { note("c8"); return c < 0 ? c : MPU_OK; }
+    const int w = try_conv_ws(dtype, mode, a, st);
+    if (w != 0) { note("ws"); return w < 0 ? w : MPU_OK; }
+    const int x = try_conv_halo16(dtype, mode, a, st);
+    if (x != 0) { note("halo16p"); return x < 0 ? x : MPU_OK; }
+    const int h = try_conv_halo(dtype, mode, a, st);
+    if (h != 0) { note(h == 2 ? "halo8" : "halo"); return h < 0 ? h : MPU_OK; }
+    const int k = try_conv_deepk(dtype, mode, a, st);
+    if (k != 0) { note("deepk"); return k < 0 ? k : MPU_OK; }
+    const int rc = launch_conv_glds(dtype, mode, a, st);
+    note(last_glds_schedule());
+    return rc;
 }
 
 int launch_conv(int dtype, int mode, const ConvArgs& a, hipStream_t st) {
@@ -809,7 +463,7 @@ static int launch_wgrad_mode(WgradArgs a, float* dW, hipStream_t st, ReduceQueue
     // A concat layer whose first source is not a multiple of 64 channels (complexity_factor 2: 96 | 96, 184 | 184, ...)
     // cannot be tiled over both sources by the LDS-DMA kernels (a 64-channel tile would straddle them): each source runs
     // as its own job with its own partials, and the reduction writes its rows of dW (ReduceJob::cin_job).
-    if (a.C1 > 0 && a.C0 % 64 != 0 && a.cin_total == 0 && conv_impl() == 1 && dt_ == MPU_BF16 && rq && MODE == CONV3 &&
+    if (a.C1 > 0 && a.C0 % 64 != 0 && a.cin_total == 0 && dt_ == MPU_BF16 && rq && MODE == CONV3 &&
         rq->njobs + 2 <= REDUCE_MAX_JOBS) {
         WgradArgs h[2] = {a, a};
         h[0].C1 = 0; h[0].x1 = nullptr; h[0].cin_total = a.C0 + a.C1; h[0].ci_base = 0;
@@ -832,19 +486,16 @@ static int launch_wgrad_mode(WgradArgs a, float* dW, hipStream_t st, ReduceQueue
         }
     }
     const int Cin = a.C0 + a.C1;
-    if (conv_impl() == 1) {                      // first layer: 1-2 image channels in 8-channel records
-        const int c8 = try_wgrad_c8(dt_, MODE, a, dW, st);
-        if (c8 != 0) {
-            if (sched_log_on()) sched_note("wgrad c8 mode=%d B=%d H=%d W=%d Cin=%d Cout=%d ksplit=1", MODE, a.B, a.Ho, a.Wo, Cin, a.Cout);
-            return c8 < 0 ? c8 : MPU_OK;
-        }
+    const int c8 = try_wgrad_c8(dt_, MODE, a, dW, st);   // first layer: 1-2 image channels in 8-channel records
+    if (c8 != 0) {
+        if (sched_log_on()) sched_note("wgrad c8 mode=%d B=%d H=%d W=%d Cin=%d Cout=%d ksplit=1", MODE, a.B, a.Ho, a.Wo, Cin, a.Cout);
+        return c8 < 0 ? c8 : MPU_OK;
     }
-    TapsPlan taps; taps.use = 0;
-    const bool can_group = grp && rq && rq->njobs < REDUCE_MAX_JOBS && conv_impl() == 1 && dt_ == MPU_BF16;
-    if (conv_impl() == 1) taps = wgrad_taps_plan(dt_, MODE, a.B, a.Ho, a.Wo, a.C0, a.C1, a.Cout, can_group && grp->ntaps < TAPS_GROUP_MAX);
+    const bool can_group = grp && rq && rq->njobs < REDUCE_MAX_JOBS && dt_ == MPU_BF16;
+    const TapsPlan taps = wgrad_taps_plan(dt_, MODE, a.B, a.Ho, a.Wo, a.C0, a.C1, a.Cout, can_group && grp->ntaps < TAPS_GROUP_MAX);
     if (taps.use) a.ksplit = (taps.nstrips + 1) / 2;   // one partial copy per pair of pixel strips
     // the LDS-DMA kernels also sum dz over the pixels (bias gradient) when they handle the shape
-    a.fuse_db = (a.db && conv_impl() == 1 && (taps.use || wgrad_glds_supported(dt_, MODE, a))) ? 1 : 0;
+    a.fuse_db = (a.db && (taps.use || wgrad_glds_supported(dt_, MODE, a))) ? 1 : 0;
     if (a.db && !a.fuse_db) {
         int rc0 = launch_colsum(dt_, a.dz, (long)a.B * a.Ho * a.Wo, a.Cout, a.colsum_scratch, a.db, st);
         if (rc0) return rc0;
@@ -864,14 +515,14 @@ static int launch_wgrad_mode(WgradArgs a, float* dW, hipStream_t st, ReduceQueue
     if (a.ksplit == 1 && !strided) a.partial = dW;   // single split: the kernel's output IS the weight gradient
     const int ntaps = ModeTraits<MODE>::NTAPS;
     const long n = (long)ntaps * Cin * a.Cout;
-    const bool will_defer = grp && rq && rq->njobs < REDUCE_MAX_JOBS && conv_impl() == 1 && dt_ == MPU_BF16 &&
+    const bool will_defer = can_group &&
                             ((taps.use && grp->ntaps < TAPS_GROUP_MAX) || (!taps.use && grp->nglds < GLDS_GROUP_MAX && wgrad_glds_grid(MODE, a) > 0));
     if (prof_on() && !will_defer)
         prof_begin(PROF_WGRAD, a.flops > 0 ? a.flops : 2.0 * a.B * a.Ho * a.Wo * (double)n, st);
     bool big = false;
     int g_ = 0;
     bool deferred = false;                       // recorded in the group instead of launched (needs the deferred reduction too)
-    if (grp && rq && rq->njobs < REDUCE_MAX_JOBS && conv_impl() == 1 && dt_ == MPU_BF16) {
+    if (can_group) {
         if (taps.use && grp->ntaps < TAPS_GROUP_MAX) {
             TapsGroupJob& j = grp->taps[grp->ntaps++];
             j.a = a; j.p = taps; j.mode = MODE; j.blk_begin = 0;
@@ -886,7 +537,7 @@ static int launch_wgrad_mode(WgradArgs a, float* dW, hipStream_t st, ReduceQueue
     }
     if (!deferred) {                             // (a deferred job is timed as part of its grouped launch at the flush)
         if (taps.use) { g_ = launch_wgrad_taps(MODE, a, taps, st); if (g_) return g_; g_ = 1; }
-        else if (conv_impl() == 1) g_ = try_wgrad_glds(dt_, MODE, a, st);
+        else g_ = try_wgrad_glds(dt_, MODE, a, st);
     }
     if (g_ < 0) return g_;
     if (sched_log_on())
@@ -952,8 +603,7 @@ long wgrad_job_floats(int dtype, int mode, int B, int H, int W, int C0, int C1, 
     const long M = (long)B * H * W, n = (long)ntaps * Cin * Cout;
     int ks = 1, mchunk = 0;
     wgrad_partial_elems(mode, Cin, Cout, M, &ks, &mchunk, grouped);
-    TapsPlan taps; taps.use = 0;
-    if (conv_impl() == 1) taps = wgrad_taps_plan(dtype, mode, B, H, W, C0, C1, Cout, grouped);
+    const TapsPlan taps = wgrad_taps_plan(dtype, mode, B, H, W, C0, C1, Cout, grouped);
     if (taps.use) ks = (taps.nstrips + 1) / 2;
     const long nshare = taps.use ? ks : (long)ks * ntaps * cdiv(Cin, 64);     // (128-wide tiles: half of this)
     return (long)ks * n + nshare * Cout;
@@ -966,11 +616,11 @@ long wgrad_scratch_need(int dtype, int mode, int B, int H, int W, int C0, int C1
     const long a0 = wgrad_job_floats(dtype, mode, B, H, W, C0, C1, Cout, false);
     const long a1 = wgrad_job_floats(dtype, mode, B, H, W, C0, C1, Cout, true);
     long need = a0 > a1 ? a0 : a1;
-    if (C1 > 0 && C0 % 64 != 0 && conv_impl() == 1 && dtype == MPU_BF16 && mode == CONV3)   // two jobs (launch_wgrad_mode): both regions
+    if (C1 > 0 && C0 % 64 != 0 && dtype == MPU_BF16 && mode == CONV3)   // two jobs (launch_wgrad_mode): both regions
         return wgrad_scratch_need(dtype, mode, B, H, W, C0, 0, Cout) + wgrad_scratch_need(dtype, mode, B, H, W, C1, 0, Cout) +
                ((need + 63) / 64 * 64 + 64);                                                  // (+ the unsplit need: the fallback still fits)
     // the first-layer schedule (tried first) keeps one compact row per strip of image rows: its own layout and size
-    const long c8 = conv_impl() == 1 ? wgrad_c8_scratch_floats(dtype, mode, B, H, W, C0, C1, c0_logical, Cout) : 0;
+    const long c8 = wgrad_c8_scratch_floats(dtype, mode, B, H, W, C0, C1, c0_logical, Cout);
     if (c8 > need) need = c8;
     return (need + 63) / 64 * 64 + 64;
 }

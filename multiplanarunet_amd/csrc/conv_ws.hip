@@ -19,23 +19,7 @@
 
 namespace mpu {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
 namespace {
-
-__device__ __forceinline__ i32x4 ws_make_rsrc(const void* p, long bytes) {
-    const unsigned long long pa = (unsigned long long)p;
-    i32x4 r;
-    r.x = (int)(unsigned)pa; r.y = (int)((unsigned)(pa >> 32) & 0xffffu); r.z = (int)bytes; r.w = 0x00020000;
-    return r;
-}
-__device__ __forceinline__ void ws_dma16(const i32x4& rsrc, unsigned voff, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                 :: "v"(voff), "s"(lds_addr), "s"(rsrc) : "memory");
-}
 
 template <int TH>
 struct WsCfg {
@@ -73,8 +57,8 @@ __global__ __launch_bounds__(256, 2) void conv_ws_kernel(ConvArgs a, int ntiles,
     const int H = a.Ho, W = a.Wo;
     const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
     const long npix = (long)a.B * H * W;
-    const i32x4 rs0 = ws_make_rsrc(a.in0, npix * a.C0 * 2L);
-    const i32x4 rsw = ws_make_rsrc(a.w, a.w_elems * 2L);
+    const i32x4 rs0 = make_rsrc(a.in0, npix * a.C0 * 2L);
+    const i32x4 rsw = make_rsrc(a.w, a.w_elems * 2L);
     const unsigned lds0 = (unsigned)(uintptr_t)smem;
     const int lrow = lane >> 3, slot = lane & 7;
 
@@ -110,7 +94,7 @@ __global__ __launch_bounds__(256, 2) void conv_ws_kernel(ConvArgs a, int ntiles,
                 const bool v = pr < Cfg::PH * PW && (unsigned)(y0 - 1 + py) < (unsigned)H &&
                                (unsigned)(x0 - 1 + px) < (unsigned)W && ch < a.C0;
                 const int off = tbase + __mul24(py, rowB) + __mul24(px, pixB) + ch * 2;
-                ws_dma16(rs0, v ? (unsigned)off : OOB, base + piece * 1024);
+                dma16(rs0, v ? (unsigned)off : OOB, base + piece * 1024);
             }
         }
     };
@@ -121,7 +105,7 @@ __global__ __launch_bounds__(256, 2) void conv_ws_kernel(ConvArgs a, int ntiles,
         const int ch = (slot ^ ((rl >> 1) & 7)) * 8;
         const unsigned off = (rl < a.Cout && ch < a.C0)
             ? (unsigned)(((long)rl * a.w_row_stride + (long)tap * a.w_tap_stride + ch) * 2) : OOB;
-        ws_dma16(rsw, off, lds0 + p * 1024);
+        dma16(rsw, off, lds0 + p * 1024);
     }
     int tile = blockIdx.x;
     const int fsw = ((lane & 31) >> 1) & 7, fh = lane >> 5;
@@ -417,9 +401,9 @@ int launch_ws(const ConvArgs& a_in, hipStream_t st) {
     else a.pooled = nullptr;
     if (HEAD) *a.head_done = 1;
     else a.head_partial = nullptr;
-    // XCD-contiguous tile ranges (MPU_XCD_TILES): only the regular case -- every workgroup runs the same number of rounds
+    // XCD-contiguous tile ranges: only the regular case -- every workgroup runs the same number of rounds
     // (and tiles * grid < 2^32: the multiply-high division by the grid is exact)
-    const bool xcd = env(ENV_XCD_TILES) != 0 && !(grid & 7) && grid >= 8 && tiles % grid == 0 && tiles * (long)grid < (1L << 32);
+    const bool xcd = !(grid & 7) && grid >= 8 && tiles % grid == 0 && tiles * (long)grid < (1L << 32);
     const unsigned mg = xcd ? (unsigned)(((1UL << 32) + grid - 1) / grid) : 0u;
     launch_k(kern, dim3((unsigned)grid), dim3(256), Cfg::SMEM, st, a, (int)tiles, mx, my, mg, xcd ? (int)(tiles / 8) : 0);
     if (prof_on()) prof_end(st);
@@ -430,8 +414,7 @@ int launch_ws(const ConvArgs& a_in, hipStream_t st) {
 
 // 1 = launched, 0 = shape not suited (the caller falls back to the tiled kernels), < 0 = error
 int try_conv_ws(int dtype, int mode, const ConvArgs& a, hipStream_t st) {
-    const bool on = env(ENV_CONV_WS) != 0;
-    if (!on || dtype != MPU_BF16 || mode != CONV3 || a.C1 != 0 || a.in1 || a.C0 > 64 || a.Cout > 64) return 0;
+    if (dtype != MPU_BF16 || mode != CONV3 || a.C1 != 0 || a.in1 || a.C0 > 64 || a.Cout > 64) return 0;
     if (a.ksplit > 1) return 0;
     const long tiles4 = (long)a.B * cdiv(a.Ho, 4) * cdiv(a.Wo, 32);
     if (a.Wo < 32 || a.Ho < 4 || tiles4 < 1024) return 0;    // needs >= 2 tiles per workgroup to amortise the weight load

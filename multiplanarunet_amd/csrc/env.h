@@ -10,23 +10,13 @@ namespace mpu {
 enum EnvKind {
     ENV_ON,        // on unless the variable starts with '0'
     ENV_OFF,       // off unless the variable starts with '1'
-    ENV_NUM,       // integer (atol), the default when unset
-    ENV_IMPL       // MPU_CONV_IMPL: "regs" = 0 (register-staged reference kernels), anything else = 1
+    ENV_NUM        // integer (atol), the default when unset
 };
 
 // X(id, "NAME", kind, default, "what it does")
 #define MPU_ENV_TABLE(X)                                                                                                              \
-    X(CONV_IMPL, "MPU_CONV_IMPL", ENV_IMPL, 1, "regs: the register-staged round-1 conv / wgrad kernels everywhere (reference schedules)")       \
-    X(CONV_HALO, "MPU_CONV_HALO", ENV_ON, 1, "0: no LDS-resident-patch kernels (conv_c8 / conv_ws / conv_halo*): everything on conv_glds / conv_pipe") \
-    X(CONV_C8, "MPU_CONV_C8", ENV_ON, 1, "0: first layer (8 padded channels) not on conv_c8")                                        \
-    X(CONV_WS, "MPU_CONV_WS", ENV_ON, 1, "0: 64-channel level-0 layers not on the weight-stationary conv_ws")                        \
-    X(CONV_PIPE, "MPU_CONV_PIPE", ENV_ON, 1, "0: deep layers on conv_glds instead of the 8-wave split-K conv_pipe")                  \
-    X(CONV_DEEPK, "MPU_CONV_DEEPK", ENV_ON, 1, "0: no conv_deepk (3x3 on 16-pixel maps with K split over the waves of a workgroup, no split-K partials)") \
     X(PIPE_DEBUG, "MPU_PIPE_DEBUG", ENV_NUM, 0, "dev aid: 32 = s_memtime stamps in conv_pipe")                                       \
-    X(HALO8, "MPU_HALO8", ENV_ON, 1, "0: 192-400-workgroup grids on the 4-wave conv_halo instead of the 8-wave conv_halo8")          \
     X(HALO8_SCHED, "MPU_HALO8_SCHED", ENV_NUM, 1, "0: conv_halo8 with lockstep halves (round-3 A/B); 1: halves one phase apart")      \
-    X(XCD_TILES, "MPU_XCD_TILES", ENV_ON, 1, "0: conv_halo / conv_halo8 / conv_ws tiles dealt to workgroups in launch order instead of XCD-contiguous ranges (round-6 A/B)") \
-    X(HALO_UPCONV, "MPU_HALO_UPCONV", ENV_ON, 1, "0: up-convolutions not on the low-resolution-patch conv_halo variant")             \
     X(HALO_UP8_MIN, "MPU_HALO_UP8_MIN", ENV_NUM, 2048, "grid size from which up-convolutions take 8-row tiles")                      \
     X(HALO_KNOCKOUT, "MPU_HALO_KNOCKOUT", ENV_NUM, 0, "dev aid (-DMPU_HALO_KNOCKOUT_BUILD only): knock-out mask of the predict conv kernel") \
     X(HALO16P, "MPU_HALO16P", ENV_ON, 1, "0: large inference grids not on the persistent conv_halo16p (round-3 schedules instead)")  \
@@ -43,8 +33,6 @@ enum EnvKind {
     X(POOL_BWD_RECOMPUTE, "MPU_POOL_BWD_RECOMPUTE", ENV_NUM, 1, "0: encoder levels' backward step with the post-BatchNorm tensor read and the summed gradient (skip + un-pooled) written between max-pool backward and BatchNorm backward, instead of both passes recomputing them (round-6 A/B); 1: recompute from 4 M elements per level; 2: at every level (tests)") \
     X(POOL_BWD_BLOCKS, "MPU_POOL_BWD_BLOCKS", ENV_NUM, 0, "dev aid: cap on the workgroups of the two pool-backward recompute passes (0 = the default)") \
     X(HEAD_RS, "MPU_HEAD_RS", ENV_ON, 1, "0: head forward without the reduce-scatter variant")                                       \
-    X(WGRAD_C8, "MPU_WGRAD_C8", ENV_ON, 1, "0: first-layer weight gradient not on wgrad_c8")                                         \
-    X(WGRAD_TAPS, "MPU_WGRAD_TAPS", ENV_ON, 1, "0: no wgrad_taps (strip-resident weight gradients): wgrad_glds everywhere")          \
     X(WGRAD_TAPS_STAG, "MPU_WGRAD_TAPS_STAG", ENV_ON, 1, "0: wgrad_taps with lockstep wave groups (round-3 A/B)")                    \
     X(WGRAD_GROUP, "MPU_WGRAD_GROUP", ENV_ON, 1, "0: every weight-gradient kernel as its own launch instead of the grouped launches") \
     X(WGRAD_BATCHED_REDUCE, "MPU_WGRAD_BATCHED_REDUCE", ENV_ON, 1, "0: the K-split reduction right behind every weight-gradient kernel") \

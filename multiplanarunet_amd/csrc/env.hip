@@ -21,7 +21,6 @@ void read_all() {
         switch (g_tab[i].kind) {
             case ENV_ON: g_val[i] = (e && e[0] == '0') ? 0 : 1; break;
             case ENV_OFF: g_val[i] = (e && e[0] == '1') ? 1 : 0; break;
-            case ENV_IMPL: g_val[i] = (e && strcmp(e, "regs") == 0) ? 0 : 1; break;
             default: g_val[i] = e ? atol(e) : g_tab[i].dflt; break;
         }
     }

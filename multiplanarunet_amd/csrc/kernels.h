@@ -7,6 +7,35 @@ namespace mpu {
 
 enum { CONV3 = 0, UPCONV2 = 1, CONV3S2 = 2, CONV1 = 3 };
 
+template <int MODE> struct ModeTraits;
+template <> struct ModeTraits<CONV3>   { static constexpr int NTAPS = 9, KW = 3; };
+template <> struct ModeTraits<UPCONV2> { static constexpr int NTAPS = 4, KW = 2; };
+template <> struct ModeTraits<CONV3S2> { static constexpr int NTAPS = 9, KW = 3; };
+template <> struct ModeTraits<CONV1>   { static constexpr int NTAPS = 1, KW = 1; };
+
+// input pixel (iy,ix) read by output pixel (oy,ox) at tap (ky,kx); false = zero padding
+template <int MODE>
+__device__ __forceinline__ bool tap_src(int oy, int ox, int ky, int kx, int Ho, int Wo, int& iy, int& ix) {
+    if (MODE == CONV3) {
+        iy = oy + ky - 1; ix = ox + kx - 1;
+        return (unsigned)iy < (unsigned)Ho && (unsigned)ix < (unsigned)Wo;
+    } else if (MODE == UPCONV2) {
+        const int uy = oy + ky, ux = ox + kx;
+        iy = uy >> 1; ix = ux >> 1;
+        return uy < Ho && ux < Wo;
+    } else if (MODE == CONV3S2) {
+        iy = 2 * oy + ky - 1; ix = 2 * ox + kx - 1;
+        return (unsigned)iy < (unsigned)(2 * Ho) && (unsigned)ix < (unsigned)(2 * Wo);
+    } else {
+        iy = oy; ix = ox;
+        return true;
+    }
+}
+// input rows (columns) of a MODE layer with Ho output rows (columns)
+template <int MODE> __device__ __forceinline__ int in_h(int Ho) {
+    return MODE == UPCONV2 ? Ho / 2 : (MODE == CONV3S2 ? Ho * 2 : Ho);
+}
+
 struct ConvArgs {
     const void* in0; const void* in1; int C0, C1;
     const void* w; long w_tap_stride; int w_row_stride;
@@ -44,7 +73,7 @@ struct ConvArgs {
     // softmax. Otherwise the caller runs launch_head_forward on the stored output.
     const float* head_w = nullptr; int head_k = 0, head_ldw = 0; float* head_partial = nullptr; int* head_done = nullptr;
     int x3 = 0;                  // f32 storage only: split-bf16 products (three bf16 MFMAs, common.h x3_mma) instead of exact-f32 MFMAs
-    int xcd = 0;                 // set by the launchers of conv_halo / conv_halo8 / conv_ws (MPU_XCD_TILES): workgroup -> tile through
+    int xcd = 0;                 // set by the launchers of conv_halo / conv_halo8 / conv_ws: workgroup -> tile through
                                  //   xcd_contiguous() below, so that the tiles one XCD works on are neighbours (shared halo rows and,
                                  //   with several filter tiles, the shared patch hit in that XCD's L2 instead of being fetched per XCD)
     int dbg = 0;                 // profiling switches of conv_pipe_kernel (MPU_PIPE_DEBUG: 1 no stores, 2 no MFMAs, 4 no DMA,
@@ -134,7 +163,7 @@ inline void launch_k(void (*kern)(KA...), dim3 grid, dim3 block, unsigned shmem,
 bool sched_log_on();                            // schedule log (mpu_schedule_log_*): one line per conv / wgrad launch
 void sched_note(const char* fmt, ...);
 
-int  launch_conv(int dtype, int mode, const ConvArgs& a, hipStream_t st);       // dispatches on MPU_CONV_IMPL
+int  launch_conv(int dtype, int mode, const ConvArgs& a, hipStream_t st);       // picks the schedule by shape
 int  launch_conv_glds(int dtype, int mode, const ConvArgs& a, hipStream_t st);  // LDS-DMA variant (conv_glds.hip)
 const char* last_glds_schedule();               // "glds" or "pipe": what the last launch_conv_glds of this thread ran
 int  try_conv_deepk(int dtype, int mode, const ConvArgs& a, hipStream_t st);   // 3x3 on 16-pixel maps, K split over the waves of a workgroup (conv_deepk.hip)

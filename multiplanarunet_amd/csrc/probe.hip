@@ -5,9 +5,6 @@
 namespace mpu {
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-
 // every wave issues `iters` x 8 independent v_mfma_f32_32x32x16_bf16 (4 accumulators x 2): the matrix pipe's
 // back-to-back rate, no memory traffic. FLOPs = waves * iters * 8 * 2*32*32*16.
 __global__ __launch_bounds__(256) void probe_mfma_kernel(int iters, float* sink) {

@@ -904,12 +904,7 @@ mpu_unet* mpu_unet_create(const mpu_unet_config* cfg) {
     }
     mpu_unet* m = new mpu_unet();
     m->cfg = *cfg;
-    if (cfg->dtype == MPU_F32X3) {
-        if (env(ENV_CONV_IMPL) == 0) {      // (the packed operands of this mode are hi | lo words: only the LDS-DMA kernels read them)
-            delete m; fail(MPU_EUNSUPPORTED, "%s", "mpu_unet_create: dtype f32x3 is not available under MPU_CONV_IMPL=regs"); return nullptr;
-        }
-        m->cfg.dtype = MPU_F32; m->x3 = 1;
-    }
+    if (cfg->dtype == MPU_F32X3) { m->cfg.dtype = MPU_F32; m->x3 = 1; }
     m->cin_pad = pad8(cfg->n_channels);
     for (int l = 0; l <= D; ++l) {
         const int fl = cfg->filters[l];

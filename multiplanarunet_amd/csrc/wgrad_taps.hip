@@ -30,11 +30,6 @@
 
 namespace mpu {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
 namespace {
 
 constexpr int XPX = 40;                  // pixels per staged X row (34 used: 32 + halo; 5 DMA pieces of 8)
@@ -43,16 +38,6 @@ constexpr int NXR = 5;                   // X row ring: rows t..t+2 in use, t+3 
 constexpr int ZROWB = 32 * 128;          // bytes per staged dZ row
 constexpr int NZR = 3;
 
-__device__ __forceinline__ i32x4 t_make_rsrc(const void* p, long bytes) {
-    const unsigned long long pa = (unsigned long long)p;
-    i32x4 r;
-    r.x = (int)(unsigned)pa; r.y = (int)((unsigned)(pa >> 32) & 0xffffu); r.z = (int)bytes; r.w = 0x00020000;
-    return r;
-}
-__device__ __forceinline__ void t_dma16(const i32x4& rsrc, unsigned voff, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                 :: "v"(voff), "s"(lds_addr), "s"(rsrc) : "memory");
-}
 __device__ __forceinline__ s16x8 t_frag(const unsigned char* p_lo, const unsigned char* p_hi) {
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p_lo));
     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p_hi));
@@ -170,8 +155,8 @@ __device__ __forceinline__ void wgrad_taps_body(const WgradArgs& a, const TapsPl
     const int Cs = s1 ? a.C1 : a.C0, cs0 = s1 ? ci0 - a.C0 : ci0;
     const long npix = (long)a.B * H * W;
     const int Hi = MODE == UPCONV2 ? H / 2 : H, Wi = MODE == UPCONV2 ? W / 2 : W;
-    const i32x4 rsx = t_make_rsrc(s1 ? a.x1 : a.x0, (long)a.B * Hi * Wi * Cs * 2L);
-    const i32x4 rsz = t_make_rsrc(a.dz, npix * a.Cout * 2L);
+    const i32x4 rsx = make_rsrc(s1 ? a.x1 : a.x0, (long)a.B * Hi * Wi * Cs * 2L);
+    const i32x4 rsz = make_rsrc(a.dz, npix * a.Cout * 2L);
     const unsigned lds0 = (unsigned)(uintptr_t)smem;
     const unsigned ldsZ = lds0 + NXR * XROWB;
 
@@ -214,7 +199,7 @@ __device__ __forceinline__ void wgrad_taps_body(const WgradArgs& a, const TapsPl
             const int q = wave + 4 * k;
             if (q < NXP) {                                       // wave-uniform
                 const unsigned off = (rowok && xlane[k] != OOB) ? rowoff + xlane[k] : OOB;
-                t_dma16(rsx, off, base + q * 1024);
+                dma16(rsx, off, base + q * 1024);
             }
         }
     };
@@ -223,7 +208,7 @@ __device__ __forceinline__ void wgrad_taps_body(const WgradArgs& a, const TapsPl
         const unsigned base = __builtin_amdgcn_readfirstlane(ldsZ + (t % NZRT) * ZROWB);
         const unsigned rowoff = (unsigned)(((bZ * H + y) * W) * a.Cout * 2);
         const unsigned off = (y < H && zlane != OOB) ? rowoff + zlane : OOB;
-        t_dma16(rsz, off, base + wave * 1024);
+        dma16(rsz, off, base + wave * 1024);
     };
     // DMAs per wave in one step group (X row pieces wave, wave+4, ... < NXP, plus one dZ piece): wait until only the
     // group issued last is outstanding
@@ -345,7 +330,7 @@ __device__ __forceinline__ void wgrad_taps_body(const WgradArgs& a, const TapsPl
                 const int q = wave + 4 * k;
                 if (q < NXP) {
                     const unsigned off = (rowok && xlane[k] != OOB) ? rowoff + xlane[k] : OOB;
-                    t_dma16(rsx, off, lds0 + xslot + q * 1024);
+                    dma16(rsx, off, lds0 + xslot + q * 1024);
                 }
             }
             ++rx; ++iy_next;
@@ -356,7 +341,7 @@ __device__ __forceinline__ void wgrad_taps_body(const WgradArgs& a, const TapsPl
             const int y = y0 + rz;
             const unsigned rowoff = (unsigned)((bZ * H + y) * zrow_b);
             const unsigned off = (y < H && zlane != OOB) ? rowoff + zlane : OOB;
-            t_dma16(rsz, off, ldsZ + zslot + wave * 1024);
+            dma16(rsz, off, ldsZ + zslot + wave * 1024);
             ++rz;
             zslot += ZROWB; if (zslot == NZR * ZROWB) zslot = 0;
         };
@@ -518,9 +503,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_taps_group_kernel(TapsGroupTable
 // the number of fp32 partial copies (one per strip) small: their write + re-read is the kernel's HBM traffic.
 TapsPlan wgrad_taps_plan(int dtype, int mode, int B, int H, int W, int C0, int C1, int Cout, bool grouped) {
     TapsPlan p; p.use = 0; p.RH = 0; p.sx = 0; p.sy = 0; p.nstrips = 0; p.split = 0;
-    const bool on = env(ENV_WGRAD_TAPS) != 0; constexpr int target = 512; constexpr long max_cico = TAPS_MAX_CICO;
+    constexpr int target = 512; constexpr long max_cico = TAPS_MAX_CICO;
     const int Cin = C0 + C1;
-    if (!on || dtype != MPU_BF16 || (mode != CONV3 && mode != UPCONV2) || W < 32 || H < 8) return p;
+    if (dtype != MPU_BF16 || (mode != CONV3 && mode != UPCONV2) || W < 32 || H < 8) return p;
     if (mode == UPCONV2 && ((H | W) & 1)) return p;
     if (C1 > 0 && C0 % 64 != 0) return p;
     if ((long)Cin * Cout > max_cico) return p;

@@ -149,9 +149,7 @@ def test_cfg1_bf16_train_step_per_tensor_and_dispatch():
     assert set(scheds(conv)) >= {"c8", "ws", "halo", "pipe"} and set(scheds(wg)) >= {"c8", "taps", "glds"}
     deep = scheds(conv).get("pipe", 0) + scheds(conv).get("deepk", 0) + scheds(conv).get("deep", 0)
     assert deep >= 14, scheds(conv)                                     # the deep levels: conv_pipe, and since round 5 ...
-    import os
-    if os.environ.get("MPU_CONV_DEEPK") != "0":
-        assert scheds(conv).get("deepk", 0) >= 6, scheds(conv)          # ... conv_deepk for the 3x3 layers on the 16 x 16 maps
+    assert scheds(conv).get("deepk", 0) >= 6, scheds(conv)              # ... conv_deepk for the 3x3 layers on the 16 x 16 maps
 
     # --- inference mode (well conditioned: BatchNorm with moving statistics): tight bound against the matched model
     m.flatten_output = False

@@ -241,14 +241,12 @@ DEEPK_CASES = [
 def test_k_split_over_the_waves_schedule_of_the_16_pixel_maps(case):
     """conv_deepk: the forward launch of every case takes it (schedule log) and matches the fp64 layer, as does every
     eligible data gradient (ReLU mask in the kernel's epilogue)."""
-    import os
     conv = _conv_schedules_of(lambda: _run_case(case, torch.bfloat16, workspace=True))
-    if os.environ.get("MPU_CONV_DEEPK") != "0":
-        assert conv and conv[0] == "deepk", conv
-        mode, B, H, W, C0, C1, Cout = case
-        tiles_d = (B * 2) * ((C0 + C1) // 64)
-        if 192 <= tiles_d <= 512 and (Cout // 64) % 2 == 0 and Cout <= 512:
-            assert conv.count("deepk") >= 2, conv
+    assert conv and conv[0] == "deepk", conv
+    mode, B, H, W, C0, C1, Cout = case
+    tiles_d = (B * 2) * ((C0 + C1) // 64)
+    if 192 <= tiles_d <= 512 and (Cout // 64) % 2 == 0 and Cout <= 512:
+        assert conv.count("deepk") >= 2, conv
 
 
 @pytest.mark.parametrize("case", DEEP_CASES)
