@@ -54,7 +54,7 @@ struct ConvArgs {
     // (0: the schedule chosen for this shape does not produce them; the caller runs the column reduction instead).
     float* stats; int* stats_rows; long stats_cap;              // capacity of `stats` in floats
     // Round 6: with stats_acc set the column sums are NOT written as partial rows but ADDED, as fixed-point integers, to
-    // stats_acc[8 XCDs][2][Cout] (int64, zeroed by the caller; stats_emit below) and the launcher reports *stats_rows = -1: the
+    // stats_acc (bn_acc_elems(Cout) int64, zeroed by the caller; stats_acc_add below) and the launcher reports *stats_rows = -1: the
     // consumer then needs no finalize launch at all -- it sums eight integers per (statistic, channel). Integer sums are exact,
     // so the result does not depend on the order in which workgroups arrive (deterministic, as the fixed-order rows were).
     long long* stats_acc = nullptr; float stats_scale[2] = {0.f, 0.f};   // units per 1.0 of statistic 0 / 1 (powers of two)
@@ -87,15 +87,32 @@ __device__ __forceinline__ int xcd_contiguous(int bid, int nwg) {
     const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
+// Fixed-point accumulator of C channels (stats_acc, DbAccJob.acc): two int64 words per (XCD, statistic, channel), the low words
+// [8 XCDs][2][C] first, then the high words in the same layout. A sum is hi * 2^44 + lo: an addend q below 2^44 units goes into lo
+// whole (the only atomic at the ranges of the benchmarked step), a larger one puts trunc(q / 2^44) into hi and the remainder into
+// lo. lo cannot wrap while a channel gets fewer than 2^19 addends in a launch (one per workgroup; make_run keeps the accumulator
+// mode to steps of at most 2^25 pixels), and a total is exact up to 2^94 units. The loss is a SUM over pixels times a free
+// per-image weight, so the backward sums grow with B * H * W * w and pass 2^63 units at shapes this project trains.
+constexpr int BN_ACC_ROWS = 8;                   // XCDs
+constexpr int BN_ACC_SPLIT = 44;                 // bits of a sum below the high word
+inline long bn_acc_elems(int C) { return 2L * BN_ACC_ROWS * 2 * C; }        // int64 elements of one accumulator (both words)
 // One column sum of a producer's tile: a partial row (the fixed-order scheme), or -- stats_acc mode -- a fixed-point atomic add
 // into the row of THIS workgroup's XCD (hardware register XCC_ID, so the eight per-XCD L2 caches never share an address; inside an
 // XCD the L2 is the point of coherence of every compute unit, which is where a scope-less global atomic executes).
 __device__ __forceinline__ void stats_acc_add(long long* acc, int C, int st2, int ch, float v, float scale) {
     const unsigned xcc = __builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20) & 7u;       // HW_REG_XCC_ID[3:0]
     double d = (double)v * (double)scale;
-    d = d > 9.0e18 ? 9.0e18 : (d < -9.0e18 ? -9.0e18 : d);       // (saturate: an overflowing sum must not wrap)
-    const long long q = __double2ll_rn(d);
-    __hip_atomic_fetch_add(acc + ((long)xcc * 2 + st2) * C + ch, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    long long q_lo = 0, q_hi = 0;
+    if (!(fabs(d) >= 0x1p44)) {                  // (NaN takes this branch, as it did before the high word existed)
+        q_lo = __double2ll_rn(d);
+    } else {                                     // saturate at 2^94 units; h * 2^44 is an even integer and d - h * 2^44 is exact,
+        d = fmin(fmax(d, -0x1p94), 0x1p94);      // so q_hi * 2^44 + q_lo is the rounding of d to the nearest integer, as above
+        const double h = trunc(d * 0x1p-44);
+        q_hi = (long long)h; q_lo = __double2ll_rn(d - h * 0x1p44);
+    }
+    long long* p = acc + ((long)xcc * 2 + st2) * C + ch;
+    __hip_atomic_fetch_add(p, q_lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (q_hi) __hip_atomic_fetch_add(p + (long)BN_ACC_ROWS * 2 * C, q_hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 __device__ __forceinline__ void stats_emit(const ConvArgs& a, int st2, int ch, long nrows, long row, float v) {
     if (a.stats_acc) stats_acc_add(a.stats_acc, a.Cout, st2, ch, v, a.stats_scale[st2]);
@@ -105,8 +122,6 @@ __device__ __forceinline__ void stats_emit(const ConvArgs& a, int st2, int ch, l
 struct DbAccJob { const long long* acc; float* db; int C; };
 constexpr int DB_ACC_MAX_JOBS = 32;
 struct DbAccTable { DbAccJob job[DB_ACC_MAX_JOBS]; int n = 0; float inv_scale = 0.f; };
-constexpr int BN_ACC_ROWS = 8;                   // XCDs
-inline long bn_acc_elems(int C) { return (long)BN_ACC_ROWS * 2 * C; }      // int64 elements of one accumulator
 
 struct WgradArgs {
     const void* x0; const void* x1; int C0, C1;

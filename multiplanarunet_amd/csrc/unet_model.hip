@@ -13,9 +13,10 @@ using namespace mpu;
 namespace {
 
 constexpr float BN_EPS = 1e-3f, BN_MOM = 0.99f;      // Keras BatchNormalization defaults
-// fixed-point units of the accumulator mode (ConvArgs.stats_acc; powers of two): forward sum x in 2^-24, sum x^2 in 2^-16 (a
-// mean-square activation up to 6e4 per XCD share of a 128^2 x 16 batch before the int64 saturates; their errors, <= 2^-17 / 256
-// per pixel, are far below epsilon = 1e-3); the backward sums (gradients: small numbers) in 2^-40
+// fixed-point units of the accumulator mode (ConvArgs.stats_acc; powers of two): forward sum x in 2^-24, sum x^2 in 2^-16 (their
+// errors, <= 2^-17 / 256 per pixel, are far below epsilon = 1e-3); the backward sums in 2^-40. A sum holds 2^94 units
+// (kernels.h: stats_acc_add): the backward sums grow with B * H * W times the sample weight and pass 2^63 units at shapes trained
+// here (tests/test_gpu_accumulator_range.py)
 constexpr float BN_ACC_F[2] = {16777216.f, 65536.f}, BN_ACC_B[2] = {1099511627776.f, 1099511627776.f};
 
 inline int pad8(int c) { return (c + 7) / 8 * 8; }
@@ -116,7 +117,7 @@ struct Plan {
     std::vector<long> dz;                           // per conv: its own dz (gradient at the conv's pre-activation output): the weight
                                                     // gradients of a whole backward pass run as grouped launches at its end
     std::vector<long> bnacc_f, bnacc_b;             // per BatchNorm: its fixed-point accumulators of the forward statistics / backward sums
-    long bnacc, bnacc_elems;                        //   (ConvArgs.stats_acc: int64 [8 XCDs][2][C]); one region: forward half first
+    long bnacc, bnacc_elems;                        //   (ConvArgs.stats_acc: int64 [2 words][8 XCDs][2][C]); one region: forward half first
     std::vector<long> x3x0, x3x1, x3dz;             // dtype "bf16x3": per conv the bf16 plane triples of its input source(s) and its dz
     std::vector<long> dbacc;                        //   and, in the accumulator region, the fixed-point sums of its bias gradient
                                                     // (launch_split3), read by the grouped bf16 weight-gradient launches at the pass's end
@@ -394,7 +395,9 @@ int x3_presplit_inputs(const Run& r) {
 }
 
 // dtype "bf16x3": the bias gradients queued by conv_wgrad, out of their accumulators (one launch for all of them)
-constexpr float DB_ACC_SCALE = 17592186044416.f;                 // 2^44: |sum dz| < 2^19, quantum 6e-14 per workgroup sum
+constexpr float DB_ACC_SCALE = 17592186044416.f;                 // 2^44: quantum 6e-14 per workgroup sum; |sum dz| up to 2^50 (a sum of
+                                                                 //   the loss over pixels: 0.1-0.2 * B * H * W * w at most, past 2^19 at
+                                                                 //   B = 16, 128^2 from w ~ 10)
 int flush_db(const Run& r) {
     if (r.dbq.n == 0) return MPU_OK;
     r.dbq.inv_scale = 1.f / DB_ACC_SCALE;
@@ -885,7 +888,10 @@ int make_run(Run& r, const mpu_unet* m, int batch, const float* params, const vo
     r.group = env(ENV_WGRAD_GROUP) != 0;      // 0: every weight-gradient kernel as its own launch, in place (A/B)
     // bf16 storage only: a fixed-point unit of 2^-16 on a tile's sum of squares is far below the rounding of the stored bf16 values,
     // but it is visible at the f32 parity mode's level (train-mode logits 1.3e-4 against 4e-5 with the rows: gpurun R6v)
-    r.acc_mode = env(ENV_BN_ATOMIC) != 0 && env(ENV_BN_FOLD) != 0 && env(ENV_FUSED_BN_STATS) != 0 && (m->cfg.dtype == MPU_BF16 || m->x3);
+    // (at most 2^25 pixels: a channel's low accumulator word takes < 2^19 addends of < 2^44 units, one per producing workgroup of
+    //  >= 64 pixels; kernels.h: stats_acc_add)
+    r.acc_mode = env(ENV_BN_ATOMIC) != 0 && env(ENV_BN_FOLD) != 0 && env(ENV_FUSED_BN_STATS) != 0 && (m->cfg.dtype == MPU_BF16 || m->x3) &&
+                 (long)batch * m->cfg.H * m->cfg.W <= (1L << 25);
     return MPU_OK;
 }
 

@@ -552,15 +552,25 @@ __device__ __forceinline__ double bn_fold_rowsum(const float* __restrict__ p, in
     return s;
 }
 
-// accumulator mode (round 6, ConvArgs.stats_acc): the eight per-XCD fixed-point sums of one (statistic, channel); exact
+// accumulator mode (round 6, ConvArgs.stats_acc): the eight per-XCD fixed-point sums of one (statistic, channel), low and high words
+// (kernels.h: stats_acc_add). A total that fits in int64 converts exactly as the one-word sum did; a larger one is rounded once
+// (exact below 2^97 units, so a result scales exactly with a power-of-two sample weight)
 __device__ __forceinline__ double bn_acc_sum(const long long* __restrict__ acc, int C, int st, int c, float inv_scale) {
-    long long v[BN_ACC_ROWS];
+    long long v[BN_ACC_ROWS], u[BN_ACC_ROWS];
 #pragma unroll
-    for (int r = 0; r < BN_ACC_ROWS; ++r) v[r] = acc[((long)r * 2 + st) * C + c];          // all eight loads in flight
-    long long t = 0;
+    for (int r = 0; r < BN_ACC_ROWS; ++r) {                                                   // all sixteen loads in flight
+        v[r] = acc[((long)r * 2 + st) * C + c];
+        u[r] = acc[((long)(BN_ACC_ROWS + r) * 2 + st) * C + c];
+    }
+    long long lo = 0, hi = 0;
 #pragma unroll
-    for (int r = 0; r < BN_ACC_ROWS; ++r) t += v[r];
-    return (double)t * (double)inv_scale;
+    for (int r = 0; r < BN_ACC_ROWS; ++r) { lo += v[r]; hi += u[r]; }           // (|lo| <= 2^44 per addend, < 2^19 addends: no wrap)
+    constexpr int S = BN_ACC_SPLIT;
+    hi += lo >> S;                                                               // total = hi * 2^S + l, 0 <= l < 2^S
+    const long long l = lo & ((1LL << S) - 1);
+    const double t = (hi >= -(1LL << (63 - S)) && hi < (1LL << (63 - S))) ? (double)(long long)(((unsigned long long)hi << S) | l)
+                                                                        : ldexp((double)hi, S) + (double)l;
+    return t * (double)inv_scale;
 }
 
 template <typename T, bool POOL>

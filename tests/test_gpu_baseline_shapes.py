@@ -431,8 +431,9 @@ def test_cfg4_predict_fuse_512_cubed_two_channels_properties():
 
 def test_cfg3_train_step_batch32_256_properties():
     """configs[3] (global batch 32 of 256x256) as one GPU's workload: the loss on a fixed batch is finite and
-    decreasing over the steps, two identically seeded models stay bitwise identical (deterministic kernels,
-    no atomics), BN moving statistics move."""
+    decreasing over the steps, two identically seeded models stay bitwise identical (deterministic kernels: the
+    BatchNorm sums are integer atomics, exact in any order), BN moving statistics move. Sums past 2^63 fixed-point
+    units at this shape: tests/test_gpu_accumulator_range.py."""
     from multiplanarunet_amd.unet import UNet
     g = torch.Generator(device="cuda"); g.manual_seed(0)
     B, H = 32, 256

@@ -21,27 +21,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _devcopy import hip as _hip, d2h_bf16 as _d2h_bf16, d2h_f32 as _d2h_f32, d2h_u8 as _d2h_u8
+
 pytestmark = pytest.mark.gpu
 quiet = lambda *a, **k: None
 CMP = 2
-
-
-def _hip():
-    for name in ("libamdhip64.so", "libamdhip64.so.7", "libamdhip64.so.6"):
-        try:
-            return C.CDLL(name)
-        except OSError:
-            pass
-    raise RuntimeError("libamdhip64 not found")
-
-
-def _d2h_bf16(hip, dptr, shape):
-    """device bf16 tensor -> float64 numpy (exact)."""
-    n = int(np.prod(shape))
-    host = np.empty(n, np.uint16)
-    rc = hip.hipMemcpy(host.ctypes.data_as(C.c_void_p), C.c_void_p(dptr), C.c_size_t(2 * n), C.c_int(2))
-    assert rc == 0, rc
-    return (host.astype(np.uint32) << 16).view(np.float32).reshape(shape).astype(np.float64)
 
 
 def _bf16_round(a):
@@ -217,22 +201,6 @@ def _replay_conv_launches(B, dim, cf, dtype="bf16", tol_act=1.2e-2, tol_w=2e-3):
         worst_w = max(worst_w, e, eb)
         assert e <= tol_w and eb <= tol_w, ("wgrad", ci, e, eb)
     print("replay: weight / bias gradients of the 22 layers: worst rel-to-max error %.3g" % worst_w)
-
-
-def _d2h_f32(hip, dptr, shape):
-    n = int(np.prod(shape))
-    host = np.empty(n, np.float32)
-    rc = hip.hipMemcpy(host.ctypes.data_as(C.c_void_p), C.c_void_p(dptr), C.c_size_t(4 * n), C.c_int(2))
-    assert rc == 0, rc
-    return host.reshape(shape).astype(np.float64)
-
-
-def _d2h_u8(hip, dptr, shape):
-    n = int(np.prod(shape))
-    host = np.empty(n, np.uint8)
-    rc = hip.hipMemcpy(host.ctypes.data_as(C.c_void_p), C.c_void_p(dptr), C.c_size_t(n), C.c_int(2))
-    assert rc == 0, rc
-    return host.reshape(shape)
 
 
 def test_cfg1_bf16_step_every_non_conv_launch_against_fp64_on_its_own_inputs():
