@@ -221,7 +221,8 @@ int mpu_unet_prepare_inference(const mpu_unet* m, const float* d_params, const f
  * mpu_unet_workspace_probs_offset(m, batch) (f32 [B,H,W,n_classes]; valid until the next forward on that workspace). */
 int64_t mpu_unet_workspace_probs_offset(const mpu_unet* m, int32_t batch);
 /* Byte offset (inside the workspace of `batch`) of ONE float: the mean over the B*H*W pixels of the weighted per-pixel loss of the
- * last backward pass (= mean of the d_loss tensor mpu_unet_backward fills; written by the pass whether d_loss is NULL or not).
+ * last backward pass (= mean of the d_loss tensor mpu_unet_backward fills; written by the pass whether d_loss is NULL or not;
+ * with a per-image loss the mean over the batch of w_b * L_b).
  * It is what a training loop accumulates per step without a reduction of its own (reference: the `loss` Keras logs per batch,
  * mpunet/train/trainer.py:246-257). Valid until the next backward pass on that workspace. */
 int64_t mpu_unet_workspace_loss_mean_offset(const mpu_unet* m, int32_t batch);
@@ -233,7 +234,7 @@ int mpu_unet_forward(const mpu_unet* m, int32_t batch, const float* d_x, const f
  * (SparseCategoricalCrossentropy(reduction=NONE) on clipped probabilities,
  * per-image sample weights, gradient of the SUM over batch and pixels).
  *   d_y u8 [B,H*W] ; d_sample_weight f32 [B] ; d_grads f32 [param_floats]
- *   d_loss f32 [B,H*W] per-pixel weighted loss or NULL.
+ *   d_loss f32 [B,H*W] per-pixel weighted loss or NULL (with a per-image loss attached by mpu_unet_set_loss: f32 [B]).
  * Must follow mpu_unet_forward(training=1) on the same workspace -- ONE backward pass per training forward: the forward's first
  * launch zeroes the fixed-point BatchNorm accumulators of both passes (round 6, bf16 / bf16x3), a second backward pass on the same
  * forward would add to the first one's sums. The handle remembers which form of the head the last training forward ran (with a
@@ -243,6 +244,34 @@ int mpu_unet_backward(const mpu_unet* m, int32_t batch, const uint8_t* d_y,
                       const float* d_sample_weight, const float* d_params, const void* d_packed,
                       float* d_bn_state, void* d_workspace, float* d_grads, float* d_loss,
                       void* stream);
+
+/* The loss of the train step (mpunet/train/trainer.py:51-53,79-82: `fit.loss` / `fit.loss_kwargs` resolved in tf.keras.losses and
+ * then in mpunet/evaluate/loss_functions.py). A handle trains with MPU_LOSS_SPARSE_CE until mpu_unet_set_loss attaches another
+ * kind; call it before the handle's first training step (the workspace plan of a handle with a region loss is a little larger:
+ * query mpu_unet_workspace_bytes and the offsets again afterwards). The five losses of loss_functions.py are compiled with
+ * reduction=NONE on the flattened output (bin/train.py:288,357): ONE value per image, L_b, times the per-image sample weight;
+ * the gradient is that of the sum over the batch. With such a loss the d_loss argument of mpu_unet_backward / _backward_events /
+ * _backward_adam receives B floats (w_b * L_b) instead of B*H*W, and the float at mpu_unet_workspace_loss_mean_offset is their
+ * mean over the batch (what Keras logs). Fields a kind does not use are ignored.
+ *   MPU_LOSS_DICE / MPU_LOSS_JACCARD : smooth >= 0                                   loss_functions.py:80-112 / :33-77
+ *   MPU_LOSS_GENERALIZED_DICE        : type_weight (mpu_gdl_weight)                  :207-266
+ *   MPU_LOSS_FOCAL                   : gamma, class_weights[n_class_weights] (0 or n_classes entries)   :166-204
+ *   MPU_LOSS_EXP_LOG                 : gamma_dice, gamma_cross, weight_dice, weight_cross               :115-163 */
+typedef enum { MPU_LOSS_SPARSE_CE = 0, MPU_LOSS_DICE = 1, MPU_LOSS_JACCARD = 2, MPU_LOSS_GENERALIZED_DICE = 3,
+               MPU_LOSS_FOCAL = 4, MPU_LOSS_EXP_LOG = 5 } mpu_loss_kind;
+typedef enum { MPU_GDL_SQUARE = 0, MPU_GDL_SIMPLE = 1, MPU_GDL_UNIFORM = 2 } mpu_gdl_weight;
+typedef struct {
+    int32_t kind;              /* mpu_loss_kind                                        */
+    int32_t type_weight;       /* mpu_gdl_weight                                       */
+    float   smooth;
+    float   gamma;
+    float   gamma_dice, gamma_cross, weight_dice, weight_cross;
+    int32_t n_class_weights;   /* 0: none (all ones)                                   */
+    float   class_weights[8];
+} mpu_loss_config;
+/* MPU_EINVAL + mpu_last_error() on an unknown kind or type_weight, a negative smooth, a class-weight count that is neither 0 nor
+ * n_classes, or a handle created with softmax == 0. */
+int mpu_unet_set_loss(mpu_unet* m, const mpu_loss_config* cfg);
 
 /* Accept / reject statistics of one sampled training slice (mpunet/sequences/isotrophic_live_view_sequence.py:91-128:
  * np.isin(fg_classes, lab), np.any(~np.isclose(im, bg))): d_out2[0] = OR of (1 << label) over the labels (< 32),

@@ -17,6 +17,11 @@ c_p = C.c_void_p
 i32, i64, f32, f64, u8 = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_uint8
 
 MPU_F32, MPU_BF16, MPU_F32X3 = 0, 1, 2
+ABI_VERSION = 2                         # mpu_abi_version() this binding was written against (2: mpu_loss_config, mpu_unet_set_loss)
+# mpu_loss_kind / mpu_gdl_weight
+(MPU_LOSS_SPARSE_CE, MPU_LOSS_DICE, MPU_LOSS_JACCARD, MPU_LOSS_GENERALIZED_DICE, MPU_LOSS_FOCAL,
+ MPU_LOSS_EXP_LOG) = range(6)
+MPU_GDL_SQUARE, MPU_GDL_SIMPLE, MPU_GDL_UNIFORM = 0, 1, 2
 
 
 class Axis(C.Structure):                # mpu_axis
@@ -72,6 +77,12 @@ class UNetConfig(C.Structure):         # mpu_unet_config
                 ("dtype", i32), ("softmax", i32), ("filters", i32 * 8)]
 
 
+class LossConfig(C.Structure):         # mpu_loss_config
+    _fields_ = [("kind", i32), ("type_weight", i32), ("smooth", f32), ("gamma", f32), ("gamma_dice", f32),
+                ("gamma_cross", f32), ("weight_dice", f32), ("weight_cross", f32), ("n_class_weights", i32),
+                ("class_weights", f32 * 8)]
+
+
 class MpuError(RuntimeError):
     pass
 
@@ -92,6 +103,7 @@ _SIGS = {
     "mpu_fusion_finalize": (C.c_int, [c_p, i64, i32, c_p, i32, c_p, c_p, c_p]),
     "mpu_unet_create": (c_p, [C.POINTER(UNetConfig)]),
     "mpu_unet_destroy": (None, [c_p]),
+    "mpu_unet_set_loss": (C.c_int, [c_p, C.POINTER(LossConfig)]),
     "mpu_unet_param_floats": (i64, [c_p]),
     "mpu_unet_bn_state_floats": (i64, [c_p]),
     "mpu_unet_packed_bytes": (i64, [c_p]),
@@ -190,6 +202,9 @@ def load():
             fn.restype = res
             fn.argtypes = args
         _check_build_hash(lib)
+        if lib.mpu_abi_version() != ABI_VERSION:
+            raise MpuError("libmpunet_hip.so at %s has ABI version %d, this package was written against %d"
+                           % (LIB_PATH, lib.mpu_abi_version(), ABI_VERSION))
         _lib = lib
     return _lib
 

@@ -15,7 +15,7 @@ DEFAULT_HPARAMS = {
               "complexity_factor": 2, "out_activation": "softmax", "l1_reg": False, "l2_reg": False,
               "biased_output_layer": True, "depth": 4},
     "fit": {"views": 6, "noise_sd": 0.1, "real_space_span": None, "intrp_style": "iso_live",
-            "loss": "SparseCategoricalCrossentropy", "metrics": ["sparse_categorical_accuracy"],
+            "loss": "SparseCategoricalCrossentropy", "loss_kwargs": {}, "metrics": ["sparse_categorical_accuracy"],
             "batch_size": 16, "n_epochs": 500, "optimizer": "Adam",
             "optimizer_kwargs": {"lr": 5.0e-05, "decay": 0.0, "beta_1": 0.9, "beta_2": 0.999, "epsilon": 1.0e-8},
             "fg_batch_fraction": 0.50, "bg_value": "1pct", "scaler": "RobustScaler"},

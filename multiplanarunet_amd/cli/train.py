@@ -68,6 +68,21 @@ def validate_args(args):
                                   "computations only!', mpunet/utils/system.py:80-81)")
 
 
+def loss_kwargs_of(fit):
+    """fit.loss_kwargs as Trainer.compile_model receives them (mpunet/train/trainer.py:51-53,82), after validate_hparams'
+    class-weight rule (bin/train.py:120-125). Class weights counted from the training data are not built here: with
+    fit.class_weights: True the weights are listed explicitly in loss_kwargs.class_weights."""
+    name = fit["loss"][0] if isinstance(fit["loss"], (list, tuple)) and len(fit["loss"]) == 1 else fit["loss"]
+    kw = dict(fit.get("loss_kwargs") or {})
+    if fit.get("class_weights"):
+        if name not in ("SparseFocalLoss",):
+            raise ValueError("Invalid loss function '{}' used with the 'class_weights' parameter".format(name))
+        if kw.get("class_weights") is None:
+            raise ValueError("fit.class_weights: True asks for class weights counted from the training data, which this build "
+                             "does not compute: list them in fit.loss_kwargs.class_weights (one weight per class)")
+    return kw
+
+
 def run(args):
     from .. import distributed as D
     from ..unet import UNet
@@ -130,7 +145,8 @@ def run(args):
     # loads the same volumes, so the replicas start from identical weights.
     if not args.continue_training and build.get("biased_output_layer"):
         set_bias_weights_on_all_outputs(model, train_all, hp, log)
-    model.compile(fit["optimizer"], fit["loss"], fit.get("metrics"), optimizer_kwargs=fit.get("optimizer_kwargs"))
+    model.compile(fit["optimizer"], fit["loss"], fit.get("metrics"), optimizer_kwargs=fit.get("optimizer_kwargs"),
+                  loss_kwargs=loss_kwargs_of(fit))
     if world > 1:
         D.DataParallelTrainer(model)
     B = int(fit["batch_size"])

@@ -1158,7 +1158,7 @@ static int launch_map_view(const MapArgs& a, int n_classes, bool accum, hipStrea
 
 extern "C" {
 
-int mpu_abi_version(void) { return 1; }
+int mpu_abi_version(void) { return 2; }
 
 /* test aid: 1 = closed-form fast paths with exact fall-back (default), 0 = exact search everywhere */
 int mpu_geometry_set_fast_path(int32_t on) {

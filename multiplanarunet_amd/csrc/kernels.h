@@ -323,13 +323,40 @@ int launch_head_forward(int dtype, const void* n, long M, int C, int K, const fl
                         const float* bh, int softmax, float* out, hipStream_t st);
 // second stage of the head fused into the last conv (ConvArgs.head_partial [2][M][K]): logits = p0 + p1 + bh, softmax / linear
 int launch_head_combine(const float* partial, long M, int K, const float* bh, int softmax, float* out, hipStream_t st);
-// Keras sparse CE (clipped probabilities, see oracle/unet_ref.py keras_sparse_ce), sum-gradient:
-// dn = dlogits @ Wh^T, dWh, dbh, per-pixel loss
+// The per-image losses of mpunet/evaluate/loss_functions.py (mpu_loss_config). Their gradient at the probabilities of pixel m
+// of image b is  g_mk = w_b * (a_bk + [y_m = k] * (c_bk + f(q_m,y))) * pass_mk  with a, c from the per-image sums
+// (launch_head_loss_coeffs) and f from the pixel's own clipped probability. Head-kernel form of the loss kind:
+enum { HL_CE = 0,         // Keras sparse CE: no table, per-pixel loss out of the head pass
+       HL_REGION = 1,     // Dice / Jaccard / generalized Dice: a, c only, no clip
+       HL_FOCAL = 2,      // f only: (cw_y / ppi) * (gamma (1-q)^(gamma-1) log q - (1-q)^gamma / q)
+       HL_EXPLOG = 3 };   // a, c on the clipped sums + f = -(weight_cross gamma_cross / ppi) (-log q)^(gamma_cross-1) / q
+struct HeadLoss { int kind; const float* coef /* [B][K][2] = a, c */; float inv_ppi, gamma, wcross; float cw[8]; };
+// x^e for x > 0 (1 - q and -log q of a probability clipped to [1e-7, 1 - 1e-7]). The statistics pass forms it in f64; the head
+// kernels (register budget: f64 exp / log spill there) as expf(e logf(x)) with the product's rounding error carried along --
+// a few 1e-7 relative with errors of either sign, where the device library's powf is a 16-ulp function with a bias
+__device__ __forceinline__ double head_pow_f64(double x, double e) { return exp(e * log(x)); }
+__device__ __forceinline__ float head_pow(float x, float e) {
+    const float l = logf(x), t = e * l, lo = fmaf(e, l, -t);
+    const float r = expf(t);
+    return fmaf(r, lo, r);
+}
+inline int head_loss_form(int loss_kind) {
+    return loss_kind == MPU_LOSS_SPARSE_CE ? HL_CE : loss_kind == MPU_LOSS_FOCAL ? HL_FOCAL : loss_kind == MPU_LOSS_EXP_LOG ? HL_EXPLOG : HL_REGION;
+}
+// Statistics pass + coefficient step of such a loss, two launches: per image and class I = sum [y=k] p, P = sum p, R = sum [y=k]
+// (exp-log: on the clipped p) and the image's sum of the per-pixel term (focal, exp-log), in fixed-order f64 partials whose
+// geometry depends on the image size alone; then `coef`, d_loss[b] = w_b * L_b (may be NULL) and *loss_mean = mean_b w_b L_b.
+long head_loss_scratch_doubles(int B, long ppi, int K);
+int launch_head_loss_coeffs(const mpu_loss_config& cfg, const float* probs, const uint8_t* y, const float* sw, int B, long ppi, int K,
+                            double* scratch, float* coef, float* d_loss, float* loss_mean, hipStream_t st);
+// Loss gradient at the logits (Keras sparse CE on clipped probabilities, see oracle/unet_ref.py keras_sparse_ce, or `hl`), sum-gradient:
+// dn = dlogits @ Wh^T, dWh, dbh, per-pixel loss (CE only)
 int launch_head_backward(int dtype, const void* n, const float* probs, const uint8_t* y,
                          const float* sample_w, long M, long pix_per_image, int C, int K,
                          const float* Wh, int ldw, float* partial, void* dn, float* dWh, float* dbh,
                          float* loss, hipStream_t st, long long* step_incr = nullptr /* device counter to advance by one */,
-                         float* loss_mean = nullptr /* device scalar: mean of the weighted per-pixel loss */);
+                         float* loss_mean = nullptr /* device scalar: mean of the weighted per-pixel loss */,
+                         const HeadLoss* hl = nullptr /* null: sparse CE */);
 // Round 6: max-pool backward + skip add + BatchNorm backward of an encoder level WITHOUT the dn tensor between them (two passes that
 // both recompute it; accumulator mode). 1 = launched, 0 = not suited, < 0 = error
 int launch_maxpool_bwd_bn(int dtype, const void* dskip, const void* dp, int B, int H, int W, int C, const void* x,
@@ -342,11 +369,11 @@ int launch_head_bn_forward(int dtype, const void* x, long M, const long long* ac
                            int K, const float* Wh, int ldw, const float* bh, int softmax, float* out, hipStream_t st);
 int launch_head_bn_backward(int dtype, const void* x, const float* probs, const uint8_t* y, const float* sw, long M, long ppi, int K,
                             const float* mean, const float* invstd, float* partial, float* tsum, float* dbh, float* loss,
-                            hipStream_t st, long long* step_incr, float* loss_mean);
+                            hipStream_t st, long long* step_incr, float* loss_mean, const HeadLoss* hl = nullptr);
 int launch_head_bn_bwd_apply(int dtype, const void* x, const float* probs, const uint8_t* y, const float* sw, long M, long ppi, int K,
                              const float* Wh, int ldw, const float* tsum, const float* dbh, const float* gamma, const float* beta,
                              const float* mean, const float* invstd, float* dgamma, float* dbeta, float* dWh, float* coeffs, void* dz,
-                             hipStream_t st);
+                             hipStream_t st, const HeadLoss* hl = nullptr);
 
 // l2 kernel regulariser: grads += 2*l2*W over the listed tensors; reg_loss (optional) = l2 * sum W^2
 struct L2Table { int njobs, _pad; long off[PACK_MAX_JOBS]; long n[PACK_MAX_JOBS]; };

@@ -51,6 +51,7 @@ struct mpu_unet {
     // Round 6: the last training forward ran the fused head (head_bn_forward: no post-BatchNorm tensor of the last block exists);
     // its backward pass must take head_bn_backward / head_bn_bwd_apply. A backward pass belongs to exactly one training forward.
     mutable int head_fused_fwd = 0;
+    mpu_loss_config loss{};                  // mpu_unet_set_loss; kind 0 = MPU_LOSS_SPARSE_CE: everything as without one
 
     // indices into conv / bn
     int enc_c1(int i) const { return 2 * i; }
@@ -112,6 +113,7 @@ struct Plan {
     std::vector<long> c1, c2, n, p, dskip;          // encoder levels
     long c1b, c2b, nb;
     std::vector<long> u1, n1, c2u, c3u, n2;         // up levels
+    long loss_scratch = -1, loss_coef = -1;         // a per-image loss (mpu_unet_set_loss): f64 sums / the (a, c) table; else absent
     long probs, loss_mean, gA, gB, partial, partial_floats, partial2, wpartial, wpartial_floats, cpartial, cpartial_floats, coeffs, stats, total;
     std::vector<long> wscratch;                     // per conv: float offset of its weight-gradient scratch inside wpartial
     std::vector<long> dz;                           // per conv: its own dz (gradient at the conv's pre-activation output): the weight
@@ -229,6 +231,10 @@ Plan make_plan(const mpu_unet* m, int B) {
     }
     P.coeffs = take(3L * m->cmax * 4);
     P.stats = take(m->n_stats * 4);
+    if (m->loss.kind != MPU_LOSS_SPARSE_CE) {       // (at the end: every other offset is the cross-entropy plan's)
+        P.loss_scratch = take(head_loss_scratch_doubles(B, (long)m->cfg.H * m->cfg.W, m->cfg.n_classes) * 8);
+        P.loss_coef = take((long)B * m->cfg.n_classes * 2 * 4);
+    }
     P.total = off;
     return P;
 }
@@ -668,6 +674,19 @@ int run_backward(const Run& r, const uint8_t* d_y, const float* d_sw, float* d_l
     void* gA = r.at(P.gA); void* gB = r.at(P.gB);
     const void* last = D > 0 ? r.at(P.n2[D - 1]) : r.at(P.nb);
     const bool head_fused = m->head_fused_fwd != 0;
+    // A per-image loss (mpu_unet_set_loss): statistics pass + coefficient step first -- they write d_loss [B] and the logged mean --
+    // then the same head kernels in that loss's form, which produce neither
+    HeadLoss hlv{}; const HeadLoss* hl = nullptr;
+    float* loss_mean = (float*)r.at(P.loss_mean);
+    if (m->loss.kind != MPU_LOSS_SPARSE_CE) {
+        const long ppi = (long)m->cfg.H * m->cfg.W;
+        hlv.kind = head_loss_form(m->loss.kind); hlv.coef = (const float*)r.at(P.loss_coef); hlv.inv_ppi = (float)(1.0 / (double)ppi);
+        hlv.gamma = m->loss.kind == MPU_LOSS_FOCAL ? m->loss.gamma : m->loss.gamma_cross; hlv.wcross = m->loss.weight_cross;
+        for (int k = 0; k < 8; ++k) hlv.cw[k] = k < m->loss.n_class_weights ? m->loss.class_weights[k] : 1.f;
+        RC(launch_head_loss_coeffs(m->loss, (const float*)r.at(P.probs), d_y, d_sw, r.B, ppi, m->cfg.n_classes,
+                                   (double*)r.at(P.loss_scratch), (float*)r.at(P.loss_coef), d_loss, loss_mean, r.st));
+        hl = &hlv; d_loss = nullptr; loss_mean = nullptr;
+    }
     if (head_fused) {           // (the forward pass left no n2 of the last block: head_bn_* passes over c3 instead)
         const BN& b = m->bn[m->up_bn(D - 1, 1)];
         const void* c3 = r.at(P.c3u[D - 1]);
@@ -675,16 +694,16 @@ int run_backward(const Run& r, const uint8_t* d_y, const float* d_sw, float* d_l
         const long ppi = (long)m->cfg.H * m->cfg.W;
         RC(launch_head_bn_backward(dt, c3, (const float*)r.at(P.probs), d_y, d_sw, M0, ppi, m->cfg.n_classes, r.stat(b, 0), r.stat(b, 1),
                                    (float*)r.at(P.partial), tsum, r.grads + m->head_b, d_loss, r.st,
-                                   (opt && opt->step && tail_overlap_wanted(r)) ? opt->step : nullptr, (float*)r.at(P.loss_mean)));
+                                   (opt && opt->step && tail_overlap_wanted(r)) ? opt->step : nullptr, loss_mean, hl));
         RC(launch_head_bn_bwd_apply(dt, c3, (const float*)r.at(P.probs), d_y, d_sw, M0, ppi, m->cfg.n_classes, r.params + m->head_w,
                                     m->cfg.n_classes, tsum, r.grads + m->head_b, r.params + b.g, r.params + b.b, r.stat(b, 0), r.stat(b, 1),
                                     r.grads + b.g, r.grads + b.b, r.grads + m->head_w, (float*)r.at(P.coeffs),
-                                    r.at(P.dz[m->up_c(D - 1, 2)]), r.st));
+                                    r.at(P.dz[m->up_c(D - 1, 2)]), r.st, hl));
     } else {
         RC(launch_head_backward(dt, last, (const float*)r.at(P.probs), d_y, d_sw, M0, (long)m->cfg.H * m->cfg.W,
                                 m->head_C, m->cfg.n_classes, r.params + m->head_w, m->cfg.n_classes,
                                 (float*)r.at(P.partial), gA, r.grads + m->head_w, r.grads + m->head_b, d_loss, r.st,
-                                (opt && opt->step && tail_overlap_wanted(r)) ? opt->step : nullptr, (float*)r.at(P.loss_mean)));
+                                (opt && opt->step && tail_overlap_wanted(r)) ? opt->step : nullptr, loss_mean, hl));
         tap_aux(r, 7, -1, 0, m->head_C, m->cfg.n_classes, last, r.at(P.probs), d_y, d_sw, gA, m->head_w, m->head_b);
     }
     if (m->x3) RC(x3_presplit_inputs(r));
@@ -953,6 +972,22 @@ mpu_unet* mpu_unet_create(const mpu_unet_config* cfg) {
 void mpu_unet_destroy(mpu_unet* m) {
     if (!m) return;
     delete m;
+}
+
+int mpu_unet_set_loss(mpu_unet* m, const mpu_loss_config* cfg) {
+    MPU_REQUIRE(m && cfg, "mpu_unet_set_loss: null argument");
+    MPU_REQUIRE(m->cfg.softmax, "mpu_unet_set_loss: the losses are defined on probabilities (out_activation='softmax')");
+    MPU_REQUIRE(cfg->kind >= MPU_LOSS_SPARSE_CE && cfg->kind <= MPU_LOSS_EXP_LOG, "mpu_unet_set_loss: unknown loss kind");
+    if (cfg->kind == MPU_LOSS_DICE || cfg->kind == MPU_LOSS_JACCARD)
+        MPU_REQUIRE(cfg->smooth >= 0.f, "mpu_unet_set_loss: smooth must not be negative");      // (a NaN fails this too)
+    if (cfg->kind == MPU_LOSS_GENERALIZED_DICE)
+        MPU_REQUIRE(cfg->type_weight >= MPU_GDL_SQUARE && cfg->type_weight <= MPU_GDL_UNIFORM, "mpu_unet_set_loss: unknown type_weight");
+    if (cfg->kind == MPU_LOSS_FOCAL)
+        MPU_REQUIRE(cfg->n_class_weights == 0 || cfg->n_class_weights == m->cfg.n_classes,
+                    "mpu_unet_set_loss: class_weights needs one entry per class (or none)");
+    m->loss = *cfg;
+    if (cfg->kind != MPU_LOSS_FOCAL) m->loss.n_class_weights = 0;
+    return MPU_OK;
 }
 
 int mpu_unet_set_launch_tap(mpu_unet* m, mpu_launch_tap_fn fn, void* user) {

@@ -1405,6 +1405,15 @@ __global__ __launch_bounds__(256) void head_forward_kernel(const T* __restrict__
         case 8: { constexpr int KK = 8; CALL; } break;                      \
         default: return fail(MPU_EUNSUPPORTED, "%s", "U-Net head supports 1..8 classes"); \
     }
+// ... and over the head-kernel form of the loss (kernels.h HL_*): BODY sees constexpr int LL
+#define MPU_HEAD_DISPATCH_LK(LK_, BODY)                                     \
+    switch (LK_) {                                                          \
+        case HL_CE: { constexpr int LL = HL_CE; BODY } break;               \
+        case HL_REGION: { constexpr int LL = HL_REGION; BODY } break;       \
+        case HL_FOCAL: { constexpr int LL = HL_FOCAL; BODY } break;         \
+        case HL_EXPLOG: { constexpr int LL = HL_EXPLOG; BODY } break;       \
+        default: return fail(MPU_EINVAL, "%s", "head: unknown loss form");  \
+    }
 
 // head_forward_rs_kernel: same result for C / N == GS lanes per pixel (GS = 8 or 16: a 64-channel last block in bf16 /
 // f32) and GS * K <= 64. A group of GS lanes works on GS consecutive pixels per pass: every lane multiplies its 16-byte
@@ -1538,6 +1547,76 @@ int launch_head_combine(const float* partial, long M, int K, const float* bh, in
     return launch_ok();
 }
 
+// Loss gradient at the logits of one pixel, shared by head_backward_kernel and the two head_bn_* backward passes (which both
+// recompute it: same function, same inputs, same bits). LK = HL_CE: the Keras sparse CE on clipped probabilities, *lv = the weighted
+// per-pixel loss. Every other kind (kernels.h HeadLoss; mpunet/evaluate/loss_functions.py) is a per-image loss whose value comes out
+// of launch_head_loss_coeffs:  g_k = w_b * (a_bk + [y = k] * (c_bk + f(q_y))) * pass_k,  a, c from hl.coef[b][k][2], pass_k the clip
+// mask of focal / exp-log (loss_functions.py:130-131,179-180: clip_by_value(p, 1e-7, 1 - 1e-7)), *lv = 0. logf / expf only where the
+// loss has a per-pixel term (x^e is head_pow, kernels.h, not the device library's powf). No FMA contraction in the new kinds: the
+// three kernels must form the same bits.
+template <int LK, int K>
+__device__ __forceinline__ void head_loss_grad(const HeadLoss& hl, const float* __restrict__ probs, const uint8_t* __restrict__ y,
+                                               const float* __restrict__ sw, long mm, long ppi, float (&dzv)[K], float* lv) {
+    constexpr float EPS = 1e-7f;
+    float p[K], g[K];
+    const int yy = y[mm];
+    if constexpr (LK == HL_CE) {
+        const float wt = sw[mm / ppi];
+        float S = 0.f, qy = 1.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            p[k] = probs[mm * K + k];
+            const float q = fminf(fmaxf(p[k], EPS), 1.f - EPS);
+            S += q;
+            if (k == yy) qy = q;
+        }
+        float dot = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const bool pass = p[k] >= EPS && p[k] <= 1.f - EPS;
+            g[k] = pass ? ((k == yy ? -1.f / qy : 0.f) + 1.f / S) * wt : 0.f;
+            dot += g[k] * p[k];
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) dzv[k] = p[k] * (g[k] - dot);
+        if (lv) *lv = (-logf(qy) + logf(S)) * wt;
+    } else {
+#pragma clang fp contract(off)
+        const long b = mm / ppi;
+        const float wt = sw[b];
+        float qy = 1.f, cwy = 1.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            p[k] = probs[mm * K + k];
+            if (k == yy) { qy = fminf(fmaxf(p[k], EPS), 1.f - EPS); cwy = hl.cw[k]; }
+        }
+        float fy = 0.f;                                          // the per-pixel term's derivative at q_y
+        if constexpr (LK == HL_FOCAL) {
+            const float om = 1.f - qy, pw1 = head_pow(om, hl.gamma - 1.f);
+            fy = (cwy * hl.inv_ppi) * (hl.gamma * pw1 * logf(qy) - (pw1 * om) / qy);
+        } else if constexpr (LK == HL_EXPLOG) {
+            fy = -(hl.wcross * hl.gamma * hl.inv_ppi) * head_pow(-logf(qy), hl.gamma - 1.f) / qy;
+        }
+        float dot = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            float t;
+            if constexpr (LK == HL_FOCAL) {
+                t = k == yy ? fy : 0.f;
+            } else {
+                const float2 ac = *reinterpret_cast<const float2*>(hl.coef + (b * K + k) * 2);
+                t = ac.x + (k == yy ? ac.y + fy : 0.f);
+            }
+            const bool pass = LK == HL_REGION || (p[k] >= EPS && p[k] <= 1.f - EPS);
+            g[k] = pass ? t * wt : 0.f;
+            dot += g[k] * p[k];
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) dzv[k] = p[k] * (g[k] - dot);
+        if (lv) *lv = 0.f;
+    }
+}
+
 // Gradient of the Keras sparse CE on clipped probabilities through the softmax
 // (oracle/unet_ref.py keras_sparse_ce). Per pixel:
 //   q = clip(p, eps, 1-eps); S = sum q; L = (-log q_y + log S) * w
@@ -1547,14 +1626,13 @@ int launch_head_combine(const float* partial, long M, int K, const float* bh, in
 // per-pixel loss -- head_bwd_finalize_kernel turns the last column into the step's MEAN loss (a device scalar in the workspace:
 // what `mp train` accumulates per step; a torch reduction of the 1-MB loss tensor inside the captured graph went stale for
 // stretches of replays in the bf16x3 graph -- its cross-block semaphore logic, gpurun R6al -- and costs three more launches)
-template <typename T, int K>
+template <typename T, int K, int LK>
 __global__ __launch_bounds__(256, (K <= 3 ? 4 : 2)) void head_backward_kernel(const T* __restrict__ n, const float* __restrict__ probs,
                                                             const uint8_t* __restrict__ y, const float* __restrict__ sw,
                                                             long M, long ppi, int C, const float* __restrict__ Wh, int ldw,
                                                             float* __restrict__ partial, T* __restrict__ dn,
-                                                            float* __restrict__ loss) {
+                                                            float* __restrict__ loss, const HeadLoss hl) {
     constexpr int N = Vec<T>::N;
-    constexpr float EPS = 1e-7f;
     __shared__ float w[HEAD_MAXC * K];
     __shared__ float red[HEAD_MAXC * K + K + 1];
     for (int i = threadIdx.x; i < C * K; i += 256) w[i] = Wh[(i / K) * ldw + (i % K)];
@@ -1590,29 +1668,14 @@ __global__ __launch_bounds__(256, (K <= 3 ? 4 : 2)) void head_backward_kernel(co
 #pragma unroll
         for (int k = 0; k < K; ++k) dzv[k] = 0.f;
         if (mm < M) {
-            float p[K], g[K];
-            const int yy = y[mm];
-            const float wt = sw[mm / ppi];
-            float S = 0.f, qy = 1.f;
+            float lv;
+            head_loss_grad<LK, K>(hl, probs, y, sw, mm, ppi, dzv, &lv);
 #pragma unroll
-            for (int k = 0; k < K; ++k) {
-                p[k] = probs[mm * K + k];
-                const float q = fminf(fmaxf(p[k], EPS), 1.f - EPS);
-                S += q;
-                if (k == yy) qy = q;
+            for (int k = 0; k < K; ++k) ab[k] += dzv[k];
+            if constexpr (LK == HL_CE) {                         // (the per-image losses: value and mean from launch_head_loss_coeffs)
+                lsum += lv;
+                if (loss) loss[mm] = lv;
             }
-            float dot = 0.f;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const bool pass = p[k] >= EPS && p[k] <= 1.f - EPS;
-                g[k] = pass ? ((k == yy ? -1.f / qy : 0.f) + 1.f / S) * wt : 0.f;
-                dot += g[k] * p[k];
-            }
-#pragma unroll
-            for (int k = 0; k < K; ++k) { dzv[k] = p[k] * (g[k] - dot); ab[k] += dzv[k]; }
-            const float lv = (-logf(qy) + logf(S)) * wt;
-            lsum += lv;
-            if (loss) loss[mm] = lv;
         }
         const long left = M - m0;
         const int nv = left < G ? (int)left : G;                 // pixels of this pass (uniform over the group)
@@ -1701,7 +1764,8 @@ __global__ __launch_bounds__(256) void head_bwd_finalize_kernel(const float* __r
 
 int launch_head_backward(int dtype, const void* n, const float* probs, const uint8_t* y, const float* sw, long M,
                          long ppi, int C, int K, const float* Wh, int ldw, float* partial, void* dn, float* dWh,
-                         float* dbh, float* loss, hipStream_t st, long long* step_incr, float* loss_mean) {
+                         float* dbh, float* loss, hipStream_t st, long long* step_incr, float* loss_mean, const HeadLoss* hlp) {
+    const HeadLoss hl = hlp ? *hlp : HeadLoss{};                 // (kind 0 = HL_CE)
     const int N = dtype == MPU_BF16 ? 8 : 4;
     const int cpr = C / N;
     if (C > HEAD_MAXC || cpr > 64 || C % N != 0)
@@ -1710,9 +1774,9 @@ int launch_head_backward(int dtype, const void* n, const float* probs, const uin
     const long ppb = 256;                        // pixels per block and pass (256 / G groups of G pixels)
     long blocks = (M + ppb - 1) / ppb; if (blocks > HEAD_BWD_MAX_BLOCKS) blocks = HEAD_BWD_MAX_BLOCKS;
     if (dtype == MPU_BF16) {
-        MPU_HEAD_DISPATCH_K(K, (head_backward_kernel<bf16_t, KK><<<(unsigned)blocks, 256, 0, st>>>((const bf16_t*)n, probs, y, sw, M, ppi, C, Wh, ldw, partial, (bf16_t*)dn, loss)))
+        MPU_HEAD_DISPATCH_LK(hl.kind, MPU_HEAD_DISPATCH_K(K, (head_backward_kernel<bf16_t, KK, LL><<<(unsigned)blocks, 256, 0, st>>>((const bf16_t*)n, probs, y, sw, M, ppi, C, Wh, ldw, partial, (bf16_t*)dn, loss, hl))))
     } else {
-        MPU_HEAD_DISPATCH_K(K, (head_backward_kernel<float, KK><<<(unsigned)blocks, 256, 0, st>>>((const float*)n, probs, y, sw, M, ppi, C, Wh, ldw, partial, (float*)dn, loss)))
+        MPU_HEAD_DISPATCH_LK(hl.kind, MPU_HEAD_DISPATCH_K(K, (head_backward_kernel<float, KK, LL><<<(unsigned)blocks, 256, 0, st>>>((const float*)n, probs, y, sw, M, ppi, C, Wh, ldw, partial, (float*)dn, loss, hl))))
     }
     int rc = launch_ok();
     if (rc) return rc;
@@ -1738,34 +1802,6 @@ int launch_head_backward(int dtype, const void* n, const float* probs, const uin
 // both closer to the fp64 oracle. Switch MPU_HEAD_TRAIN_FUSED=0; not taken while a launch tap is installed (the replay tests
 // check the unfused kernels launch by launch).
 // ------------------------------------------------------------------------------------------------------------------- //
-// CE gradient at the logits of one pixel (head_backward_kernel's per-pixel part, expression for expression)
-template <int K>
-__device__ __forceinline__ void head_ce_grad(const float* __restrict__ probs, const uint8_t* __restrict__ y, const float* __restrict__ sw,
-                                             long mm, long ppi, float (&dzv)[K], float* lv) {
-    constexpr float EPS = 1e-7f;
-    float p[K], g[K];
-    const int yy = y[mm];
-    const float wt = sw[mm / ppi];
-    float S = 0.f, qy = 1.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        p[k] = probs[mm * K + k];
-        const float q = fminf(fmaxf(p[k], EPS), 1.f - EPS);
-        S += q;
-        if (k == yy) qy = q;
-    }
-    float dot = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const bool pass = p[k] >= EPS && p[k] <= 1.f - EPS;
-        g[k] = pass ? ((k == yy ? -1.f / qy : 0.f) + 1.f / S) * wt : 0.f;
-        dot += g[k] * p[k];
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) dzv[k] = p[k] * (g[k] - dot);
-    if (lv) *lv = (-logf(qy) + logf(S)) * wt;
-}
-
 template <typename T, int K>
 __global__ __launch_bounds__(256) void head_bn_forward_kernel(const T* __restrict__ x, long M, const long long* __restrict__ acc,
                                                               float inv0, float inv1, const float* __restrict__ gamma,
@@ -1868,12 +1904,12 @@ __global__ __launch_bounds__(256) void head_bn_forward_kernel(const T* __restric
 }
 
 // partial layout as head_backward_kernel's: [nblk][64 * K + K + 1] = T, dbh, sum of the weighted per-pixel loss
-template <typename T, int K>
+template <typename T, int K, int LK>
 __global__ __launch_bounds__(256, (K <= 4 ? 4 : 2)) void head_bn_backward_kernel(const T* __restrict__ x, const float* __restrict__ probs,
                                                                   const uint8_t* __restrict__ y, const float* __restrict__ sw, long M,
                                                                   long ppi, const float* __restrict__ mean,
                                                                   const float* __restrict__ invstd, float* __restrict__ partial,
-                                                                  float* __restrict__ loss) {
+                                                                  float* __restrict__ loss, const HeadLoss hl) {
     constexpr int N = Vec<T>::N, G = 64 / N, C = 64, JR = 2;
     __shared__ float red[C * K + K + 1];
     for (int i = threadIdx.x; i < C * K + K + 1; i += 256) red[i] = 0.f;
@@ -1899,11 +1935,13 @@ __global__ __launch_bounds__(256, (K <= 4 ? 4 : 2)) void head_bn_backward_kernel
         for (int k = 0; k < K; ++k) dzv[k] = 0.f;
         if (mm < M) {
             float lv;
-            head_ce_grad<K>(probs, y, sw, mm, ppi, dzv, &lv);
+            head_loss_grad<LK, K>(hl, probs, y, sw, mm, ppi, dzv, &lv);
 #pragma unroll
             for (int k = 0; k < K; ++k) ab[k] += dzv[k];
-            lsum += lv;
-            if (loss) loss[mm] = lv;
+            if constexpr (LK == HL_CE) {
+                lsum += lv;
+                if (loss) loss[mm] = lv;
+            }
         }
         const long left = M - m0;
         const int nv = left < G ? (int)left : G;
@@ -1960,7 +1998,7 @@ __global__ __launch_bounds__(256, (K <= 4 ? 4 : 2)) void head_bn_backward_kernel
     for (int i = threadIdx.x; i < C * K + K + 1; i += 256) partial[(long)blockIdx.x * (C * K + K + 1) + i] = red[i];
 }
 
-template <typename T, int K>
+template <typename T, int K, int LK>
 __global__ __launch_bounds__(256, (K <= 4 ? 4 : 2)) void head_bn_bwd_apply_kernel(const T* __restrict__ x, const float* __restrict__ probs,
                                                                    const uint8_t* __restrict__ y, const float* __restrict__ sw, long M,
                                                                    long ppi, const float* __restrict__ Wh, int ldw,
@@ -1968,7 +2006,7 @@ __global__ __launch_bounds__(256, (K <= 4 ? 4 : 2)) void head_bn_bwd_apply_kerne
                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                    const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                    float* dgamma, float* dbeta, float* dWh, float* coeffs,
-                                                                   T* __restrict__ dz) {
+                                                                   T* __restrict__ dz, const HeadLoss hl) {
     constexpr int N = Vec<T>::N, G = 64 / N, C = 64, JR = 2;
     __shared__ __attribute__((aligned(16))) float coef[3][64];
     __shared__ float w[C * K];
@@ -2009,7 +2047,7 @@ __global__ __launch_bounds__(256, (K <= 4 ? 4 : 2)) void head_bn_bwd_apply_kerne
         float dzv[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) dzv[k] = 0.f;
-        if (mm < M) head_ce_grad<K>(probs, y, sw, mm, ppi, dzv, nullptr);
+        if (mm < M) head_loss_grad<LK, K>(hl, probs, y, sw, mm, ppi, dzv, nullptr);
         const long left = M - m0;
         const int nv = left < G ? (int)left : G;
         for (int j0 = 0; j0 < nv; j0 += JR) {
@@ -2069,12 +2107,13 @@ int launch_head_bn_forward(int dtype, const void* x, long M, const long long* ac
 // T (-> tsum [64][K]), dbh, mean loss; the device step counter moves in the finalizer as in launch_head_backward
 int launch_head_bn_backward(int dtype, const void* x, const float* probs, const uint8_t* y, const float* sw, long M, long ppi, int K,
                             const float* mean, const float* invstd, float* partial, float* tsum, float* dbh, float* loss,
-                            hipStream_t st, long long* step_incr, float* loss_mean) {
+                            hipStream_t st, long long* step_incr, float* loss_mean, const HeadLoss* hlp) {
+    const HeadLoss hl = hlp ? *hlp : HeadLoss{};
     long blocks = (M + 255) / 256; if (blocks > HEAD_BWD_MAX_BLOCKS) blocks = HEAD_BWD_MAX_BLOCKS;
     if (dtype == MPU_BF16) {
-        MPU_HEAD_DISPATCH_K(K, (head_bn_backward_kernel<bf16_t, KK><<<(unsigned)blocks, 256, 0, st>>>((const bf16_t*)x, probs, y, sw, M, ppi, mean, invstd, partial, loss)))
+        MPU_HEAD_DISPATCH_LK(hl.kind, MPU_HEAD_DISPATCH_K(K, (head_bn_backward_kernel<bf16_t, KK, LL><<<(unsigned)blocks, 256, 0, st>>>((const bf16_t*)x, probs, y, sw, M, ppi, mean, invstd, partial, loss, hl))))
     } else {
-        MPU_HEAD_DISPATCH_K4(K, (head_bn_backward_kernel<float, KK><<<(unsigned)blocks, 256, 0, st>>>((const float*)x, probs, y, sw, M, ppi, mean, invstd, partial, loss)))
+        MPU_HEAD_DISPATCH_LK(hl.kind, MPU_HEAD_DISPATCH_K4(K, (head_bn_backward_kernel<float, KK, LL><<<(unsigned)blocks, 256, 0, st>>>((const float*)x, probs, y, sw, M, ppi, mean, invstd, partial, loss, hl))))
     }
     int rc = launch_ok();
     if (rc) return rc;
@@ -2086,14 +2125,15 @@ int launch_head_bn_backward(int dtype, const void* x, const float* probs, const 
 int launch_head_bn_bwd_apply(int dtype, const void* x, const float* probs, const uint8_t* y, const float* sw, long M, long ppi, int K,
                              const float* Wh, int ldw, const float* tsum, const float* dbh, const float* gamma, const float* beta,
                              const float* mean, const float* invstd, float* dgamma, float* dbeta, float* dWh, float* coeffs, void* dz,
-                             hipStream_t st) {
+                             hipStream_t st, const HeadLoss* hlp) {
+    const HeadLoss hl = hlp ? *hlp : HeadLoss{};
     long blocks = (M + 255) / 256; if (blocks > 4096) blocks = 4096;
     if (dtype == MPU_BF16) {
-        MPU_HEAD_DISPATCH_K(K, (head_bn_bwd_apply_kernel<bf16_t, KK><<<(unsigned)blocks, 256, 0, st>>>((const bf16_t*)x, probs, y, sw, M, ppi, Wh, ldw, tsum, dbh, gamma,
-                                                                                                       beta, mean, invstd, dgamma, dbeta, dWh, coeffs, (bf16_t*)dz)))
+        MPU_HEAD_DISPATCH_LK(hl.kind, MPU_HEAD_DISPATCH_K(K, (head_bn_bwd_apply_kernel<bf16_t, KK, LL><<<(unsigned)blocks, 256, 0, st>>>((const bf16_t*)x, probs, y, sw, M, ppi, Wh, ldw, tsum, dbh, gamma,
+                                                                                                       beta, mean, invstd, dgamma, dbeta, dWh, coeffs, (bf16_t*)dz, hl))))
     } else {
-        MPU_HEAD_DISPATCH_K4(K, (head_bn_bwd_apply_kernel<float, KK><<<(unsigned)blocks, 256, 0, st>>>((const float*)x, probs, y, sw, M, ppi, Wh, ldw, tsum, dbh, gamma,
-                                                                                                       beta, mean, invstd, dgamma, dbeta, dWh, coeffs, (float*)dz)))
+        MPU_HEAD_DISPATCH_LK(hl.kind, MPU_HEAD_DISPATCH_K4(K, (head_bn_bwd_apply_kernel<float, KK, LL><<<(unsigned)blocks, 256, 0, st>>>((const float*)x, probs, y, sw, M, ppi, Wh, ldw, tsum, dbh, gamma,
+                                                                                                       beta, mean, invstd, dgamma, dbeta, dWh, coeffs, (float*)dz, hl))))
     }
     if (sched_log_on()) sched_note("bn_fold bwd C=64 rows=-1 head=1 grid=%ld", blocks);
     return launch_ok();

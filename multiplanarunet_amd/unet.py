@@ -16,6 +16,19 @@ import torch
 from . import _lib
 
 
+# mpunet/evaluate/loss_functions.py: class name -> (mpu_loss_kind, constructor keywords with their defaults, takes **kwargs)
+_CUSTOM_LOSSES = {
+    "SparseDiceLoss": (_lib.MPU_LOSS_DICE, {"smooth": 1}, True),                                   # :100-112
+    "SparseJaccardDistanceLoss": (_lib.MPU_LOSS_JACCARD, {"smooth": 1}, True),                     # :65-77
+    "SparseGeneralizedDiceLoss": (_lib.MPU_LOSS_GENERALIZED_DICE, {"type_weight": "Square"}, False),   # :249-266
+    "SparseFocalLoss": (_lib.MPU_LOSS_FOCAL, {"gamma": 2, "class_weights": None}, False),          # :192-204
+    "SparseExponentialLogarithmicLoss": (_lib.MPU_LOSS_EXP_LOG, {"gamma_dice": 0.3, "gamma_cross": 0.3, "weight_dice": 1,
+                                                                 "weight_cross": 1}, False),       # :148-163
+}
+_CUSTOM_LOSSES["SparseExpLogDice"] = _CUSTOM_LOSSES["SparseExponentialLogarithmicLoss"]          # :270
+_GDL_WEIGHTS = {"square": _lib.MPU_GDL_SQUARE, "simple": _lib.MPU_GDL_SIMPLE, "uniform": _lib.MPU_GDL_UNIFORM}
+
+
 class _ScreenLogger:
     def __call__(self, *args, **kwargs):
         print(*args)
@@ -134,6 +147,8 @@ class UNet:
         self._l2_ws = None
         self.reg_loss = None
         self._grad_hook = None         # e.g. an all-reduce over RCCL (multiplanarunet_amd.distributed)
+        self.loss_name = "SparseCategoricalCrossentropy"
+        self._per_image_loss = False   # compile() with a loss of mpunet/evaluate/loss_functions.py: one value per image
         self._init_weights(seed)
 
         # receptive field of the contracting path (unet.py:104-109, utils/conv_arithmetics.py:57)
@@ -430,10 +445,13 @@ class UNet:
     __call__ = predict_on_batch
 
     # ---- training ------------------------------------------------------ #
-    def compile(self, optimizer="Adam", loss=None, metrics=None, optimizer_kwargs=None, **kwargs):
+    def compile(self, optimizer="Adam", loss=None, metrics=None, optimizer_kwargs=None, loss_kwargs=None, **kwargs):
         """
-        Trainer.compile_model (mpunet/train/trainer.py:51-97): only the reference
-        default is on the path -- Adam + SparseCategoricalCrossentropy(reduction=NONE).
+        Trainer.compile_model (mpunet/train/trainer.py:51-97): Adam with SparseCategoricalCrossentropy(reduction=NONE)
+        (the reference default) or one of the losses of mpunet/evaluate/loss_functions.py -- SparseDiceLoss,
+        SparseJaccardDistanceLoss, SparseGeneralizedDiceLoss, SparseFocalLoss, SparseExponentialLogarithmicLoss
+        (alias SparseExpLogDice) -- with `loss_kwargs` as their constructors take them (trainer.py:82). Those five give ONE
+        loss value per image (reduction=NONE over the flattened output): forward_backward / train_step return [B, 1].
         """
         name = optimizer if isinstance(optimizer, str) else type(optimizer).__name__
         if name.lower() != "adam":
@@ -441,9 +459,16 @@ class UNet:
         if loss is not None:
             lname = loss if isinstance(loss, str) else getattr(loss, "__name__", type(loss).__name__)
             if isinstance(loss, (list, tuple)):
+                if len(loss) != 1:
+                    raise NotImplementedError("one loss per model (the reference's U-Net has one output)")
                 lname = loss[0] if isinstance(loss[0], str) else type(loss[0]).__name__
-            if "sparsecategoricalcrossentropy" not in lname.lower().replace("_", ""):
-                raise NotImplementedError("only SparseCategoricalCrossentropy is supported")
+            if lname in _CUSTOM_LOSSES:
+                self._set_loss(lname, dict(loss_kwargs or {}))
+            elif "sparsecategoricalcrossentropy" in lname.lower().replace("_", ""):
+                self._set_loss(None, {})
+            else:
+                raise NotImplementedError("loss %r is not supported: SparseCategoricalCrossentropy or one of %s"
+                                          % (lname, ", ".join(sorted(_CUSTOM_LOSSES))))
         if optimizer_kwargs:
             kw = dict(optimizer_kwargs)
             if "learning_rate" in kw:
@@ -453,6 +478,52 @@ class UNet:
             kw.pop("decay", None)
             self.optimizer_kwargs.update(kw)
         return self
+
+    def _set_loss(self, lname, kw):
+        """Validate `kw` against the constructor of loss_functions.<lname> and attach the loss to the library handle
+        (mpu_unet_set_loss). lname None: back to the sparse cross-entropy."""
+        cfg = _lib.LossConfig()
+        if lname is None:
+            if not self._per_image_loss:   # nothing attached: the handle is as mpu_unet_create made it
+                return
+            cfg.kind = _lib.MPU_LOSS_SPARSE_CE
+        else:
+            kind, defaults, var_kw = _CUSTOM_LOSSES[lname]
+            if self.out_activation != "softmax":
+                raise ValueError("%s is defined on class probabilities: it needs out_activation='softmax'" % lname)
+            if "reduction" in kw:        # trainer.py:82 passes it itself
+                raise TypeError("%s() got multiple values for keyword argument 'reduction'" % lname)
+            kw.pop("name", None)
+            unknown = [k for k in kw if k not in defaults]
+            if unknown and not var_kw:   # (SparseDiceLoss / SparseJaccardDistanceLoss take and drop **kwargs, :71,106)
+                raise TypeError("%s() got an unexpected keyword argument %r" % (lname, unknown[0]))
+            a = dict(defaults)
+            a.update({k: v for k, v in kw.items() if k in defaults})
+            cfg.kind = kind
+            cfg.smooth = float(a.get("smooth", 1))
+            if kind in (_lib.MPU_LOSS_DICE, _lib.MPU_LOSS_JACCARD) and not cfg.smooth >= 0:
+                raise ValueError("%s: smooth must not be negative" % lname)
+            if kind == _lib.MPU_LOSS_GENERALIZED_DICE:
+                tw = str(a["type_weight"]).lower()
+                if tw not in _GDL_WEIGHTS:                         # loss_functions.py:226-228
+                    raise ValueError('The variable type_weight "%s" is not defined.' % a["type_weight"])
+                cfg.type_weight = _GDL_WEIGHTS[tw]
+            cfg.gamma = float(a.get("gamma", 2))
+            cfg.gamma_dice, cfg.gamma_cross = float(a.get("gamma_dice", .3)), float(a.get("gamma_cross", .3))
+            cfg.weight_dice, cfg.weight_cross = float(a.get("weight_dice", 1)), float(a.get("weight_cross", 1))
+            cw = a.get("class_weights")
+            if cw is not None:
+                cw = [float(v) for v in np.asarray(cw, np.float64).ravel()]
+                if len(cw) != self.n_classes:
+                    raise ValueError("%s: class_weights needs %d entries, got %d" % (lname, self.n_classes, len(cw)))
+                cfg.n_class_weights = len(cw)
+                for i, v in enumerate(cw):
+                    cfg.class_weights[i] = v
+        _lib.call("mpu_unet_set_loss", self._h, C.byref(cfg))
+        self.loss_name = lname or "SparseCategoricalCrossentropy"
+        self._per_image_loss = lname is not None
+        self._ws = None                    # the workspace plan of a handle with a per-image loss is larger
+        self._ws_batch = 0
 
     def _ensure_adam(self):
         if self._adam_m is None:
@@ -468,7 +539,8 @@ class UNet:
         return [int(buf[i]) for i in range(n)]
 
     def forward_backward(self, x, y, sample_weight=None, want_loss=True, ready_events=None, adam=None):
-        """Train-mode forward + backward; fills self.grads (sum-gradient). Returns (probs, loss[B,H*W] or None).
+        """Train-mode forward + backward; fills self.grads (sum-gradient). Returns (probs, loss[B,H*W] or None); with a per-image
+        loss (compile) the loss is [B,1]: sample_weight[b] * L_b.
         ready_events: optional list (one entry per grad_ready_points(), None = skip) of torch.cuda.Event recorded
         on the current stream when that part of the gradient buffer is final (data-parallel overlap).
         adam: (t, step_dev) -- ALSO apply the optimizer inside the same library call (mpu_unet_backward_adam: the
@@ -486,7 +558,8 @@ class UNet:
             sw = torch.as_tensor(np.asarray(sample_weight, np.float32) if not torch.is_tensor(sample_weight)
                                  else sample_weight).to(device=self.device, dtype=torch.float32).contiguous()
         probs = self._forward(X, training=True)
-        loss = torch.empty((B, y.shape[1]), dtype=torch.float32, device=self.device) if want_loss else None
+        loss = torch.empty((B, 1 if self._per_image_loss else y.shape[1]), dtype=torch.float32,
+                           device=self.device) if want_loss else None
         if adam is not None:
             if ready_events is not None:
                 raise ValueError("forward_backward: adam= and ready_events= exclude each other")
@@ -513,8 +586,8 @@ class UNet:
 
     def loss_mean(self):
         """Device scalar (a [1] f32 VIEW into the workspace, valid until the next backward pass): the mean over all pixels of the
-        weighted per-pixel loss of the last forward_backward / train_step -- what Keras logs per batch. Produced by the backward
-        pass itself (mpu_unet_workspace_loss_mean_offset), so a training loop needs no reduction of the 1-MB loss tensor; inside a
+        weighted per-pixel loss (a per-image loss: the mean over the batch of w_b * L_b) of the last forward_backward / train_step
+        -- what Keras logs per batch. Produced by the backward pass itself (mpu_unet_workspace_loss_mean_offset), so a training loop needs no reduction of the 1-MB loss tensor; inside a
         captured HIP graph that torch reduction (several blocks per output, semaphores) went stale for stretches of replays."""
         off = int(_lib.load().mpu_unet_workspace_loss_mean_offset(self._h, self._last_batch))
         return self._ws[off:off + 4].view(torch.float32)
