@@ -50,6 +50,36 @@ template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return f32_to_bf16(v); }
 
+template <typename T> struct Vec;   // one 16-byte chunk of T as floats
+template <> struct Vec<float> {
+    static constexpr int N = 4;
+    static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
+        const float4 t = *(const float4*)p; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    }
+    static __device__ __forceinline__ void store(float* p, const float (&v)[4]) {
+        *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
+    }
+};
+template <> struct Vec<bf16_t> {
+    static constexpr int N = 8;
+    static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[8]) {
+        const uint4 t = *(const uint4*)p;
+        const uint32_t w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[2 * i] = __uint_as_float(w[i] << 16);
+            v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+        }
+    }
+    static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[8]) {
+        uint32_t w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            w[i] = f32x2_to_bf16x2(v[2 * i], v[2 * i + 1]);
+        *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+};
+
 // ---- device primitives of the MFMA convolution kernels (conv_*.hip, wgrad_*.hip) -----------------------------------------------
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -173,5 +203,10 @@ inline int device_cu_count() {
 }
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// grid of a grid-stride element-wise kernel, 256 threads per workgroup
+inline int ew_grid(long work) {
+    long b = (work + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
+}
 
 }  // namespace mpu

@@ -244,26 +244,6 @@ bool wgrad_glds_supported(int dtype, int mode, const WgradArgs& a);
 constexpr int RED_MAX_BLOCKS = 256;
 constexpr int HEAD_BWD_MAX_BLOCKS = 1024;      // partial rows of the head weight and bias gradient (4 workgroups per CU; 2048: slower)
 
-// fp32 master [taps][Cin][Cout] -> packed operands in T
-// one launch for every 3x3 / up-conv layer of a model (offsets in ELEMENTS of params / the packed buffer)
-struct PackJob { int mode, Cin, Cout, unit_begin, fwd_units, _pad; long w, wf, wd; };
-constexpr int PACK_MAX_JOBS = 40;
-struct PackTable { int njobs, _pad; PackJob job[PACK_MAX_JOBS]; };
-int launch_pack_all(int dtype, PackTable& tab, const float* params, void* packed, hipStream_t st);
-// Adam on the whole flat buffer + both packed operand copies of the listed kernels in ONE launch (unet_ops.hip);
-// step != NULL: device-resident step counter (graph replay; incremented afterwards), else t_host (1-based)
-int launch_adam_pack_all(int dtype, PackTable& jobs, float* params, const float* grads, float* am, float* av, long n_params,
-                         void* packed, long long* step, long long t_host, double lr, double b1, double b2, float eps,
-                         hipStream_t st);
-// ... of the parameters in nr (<= 2) ascending ranges [p_lo[k], p_hi[k]) only; lean: the register- and LDS-lean kernel that is
-// co-resident with wgrad_taps (bf16); a device step counter must already hold this step's number (see launch_head_backward)
-int launch_adam_pack_ranges(int dtype, PackTable& jobs, float* params, const float* grads, float* am, float* av, const long* p_lo,
-                            const long* p_hi, int nr, void* packed, long long* step, long long t_host, double lr, double b1,
-                            double b2, float eps, bool lean, hipStream_t st);
-int launch_pack_weights(int dtype, int mode, const float* W, int Cin, int Cout,
-                        void* w_fwd, void* w_dgrad, hipStream_t st);
-// dtype "bf16x3": n packed f32 words -> (bf16 hi | bf16 lo << 16) in place (after every refresh of the packed operand copies)
-int launch_x3_words(void* buf, long n, hipStream_t st);
 int launch_cast_pad(int dtype, const float* x, long M, int Cin, int Cpad, void* out, hipStream_t st, long long* zero_p = nullptr,
                     long zero_n = 0);       // zero_p: int64 words zeroed by the same launch (the BatchNorm accumulators of a training step)
 
@@ -375,14 +355,32 @@ int launch_head_bn_bwd_apply(int dtype, const void* x, const float* probs, const
                              const float* mean, const float* invstd, float* dgamma, float* dbeta, float* dWh, float* coeffs, void* dz,
                              hipStream_t st, const HeadLoss* hl = nullptr);
 
+// ---- optimizer.hip --------------------------------------------------------
+// fp32 master [taps][Cin][Cout] -> packed operands in T
+// one launch for every 3x3 / up-conv layer of a model (offsets in ELEMENTS of params / the packed buffer)
+struct PackJob { int mode, Cin, Cout, unit_begin, fwd_units, _pad; long w, wf, wd; };
+constexpr int PACK_MAX_JOBS = 40;
+struct PackTable { int njobs, _pad; PackJob job[PACK_MAX_JOBS]; };
+int launch_pack_all(int dtype, PackTable& tab, const float* params, void* packed, hipStream_t st);
+// Adam + both packed operand copies of the listed kernels in ONE launch, over the parameters in nr ascending ranges
+// [p_lo[k], p_hi[k]). step != NULL: device-resident step counter (graph replay) that holds this step's number already
+// (step_is_t, see launch_head_backward) or is incremented afterwards; else t_host (1-based). lean: the register- and LDS-lean
+// kernel that is co-resident with wgrad_taps (bf16)
+int launch_adam_pack(int dtype, const PackTable& jobs, float* params, const float* grads, float* am, float* av, const long* p_lo,
+                     const long* p_hi, int nr, void* packed, long long* step, bool step_is_t, long long t_host, double lr, double b1,
+                     double b2, float eps, bool lean, hipStream_t st);
+// one layer (mode CONV3 / UPCONV2 / CONV1); w_dgrad may be NULL
+int launch_pack_weights(int dtype, int mode, const float* W, int Cin, int Cout,
+                        void* w_fwd, void* w_dgrad, hipStream_t st);
+// dtype "bf16x3": n packed f32 words -> (bf16 hi | bf16 lo << 16) in place (after every refresh of the packed operand copies)
+int launch_x3_words(void* buf, long n, hipStream_t st);
 // l2 kernel regulariser: grads += 2*l2*W over the listed tensors; reg_loss (optional) = l2 * sum W^2
 struct L2Table { int njobs, _pad; long off[PACK_MAX_JOBS]; long n[PACK_MAX_JOBS]; };
 constexpr int L2_PARTIAL_DOUBLES = PACK_MAX_JOBS * 64;
 int launch_l2_regularizer(const L2Table& tab, const float* params, float* grads, float l2, double* partial,
                           float* reg_loss, hipStream_t st);
-int launch_adam_dev(float* p, const float* g, float* m, float* v, long n, long long* step, double lr, double b1,
-                    double b2, float eps, hipStream_t st);
-int launch_adam(float* p, const float* g, float* m, float* v, long n, float alpha, float b1, float b2,
-                float eps, hipStream_t st);
+// element-wise Adam on a flat buffer; step as in launch_adam_pack (a device counter is incremented afterwards)
+int launch_adam(float* p, const float* g, float* m, float* v, long n, long long* step, long long t_host, double lr, double b1,
+                double b2, float eps, hipStream_t st);
 
 }  // namespace mpu

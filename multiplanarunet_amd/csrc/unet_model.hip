@@ -817,14 +817,17 @@ bool g_tail_events_on = false;
 hipEvent_t g_tail_ev[TAIL_EVENTS] = {nullptr};
 inline void tail_stamp(int k, hipStream_t st) { if (g_tail_events_on && g_tail_ev[k]) (void)hipEventRecord(g_tail_ev[k], st); }
 
-void pack_jobs_of(const mpu_unet* m, PackTable& tab) {
+// every 3x3 / 2x2 conv of the model as a PackJob, in parameter order
+int pack_jobs_of(const mpu_unet* m, PackTable& tab) {
     tab.njobs = 0; tab._pad = 0;
     for (const Conv& c : m->conv) {
-        if (c.mode == CONV1 || tab.njobs >= PACK_MAX_JOBS) continue;
+        if (c.mode == CONV1) continue;
+        MPU_REQUIRE(tab.njobs < PACK_MAX_JOBS, "unet: too many packed layers");
         PackJob& j = tab.job[tab.njobs++];
         j.mode = c.mode; j.Cin = c.Cin; j.Cout = c.Cout; j.unit_begin = j.fwd_units = j._pad = 0;
         j.w = c.w; j.wf = c.wf; j.wd = c.wd;
     }
+    return MPU_OK;
 }
 
 // Round 6. The weight gradients of the high-resolution levels (wgrad_taps_group, ~13 % of a configs[1] step) are bound by
@@ -843,12 +846,14 @@ int finish_backward(const Run& r, const AdamOpt* opt) {
         RC(flush_wgrad_group(wdt, r.grp, r.st));
         return flush_wgrad_reduces(r.rq, r.st);
     }
-    PackTable jobs; pack_jobs_of(m, jobs);
+    PackTable jobs;
+    RC(pack_jobs_of(m, jobs));
+    const long all_lo[1] = {0}, all_hi[1] = {m->n_params};
     if (!tail_overlap_wanted(r)) {                               // the serial order: the step counter moves behind the update
         RC(flush_wgrad_group(wdt, r.grp, r.st));
         RC(flush_wgrad_reduces(r.rq, r.st));
-        return launch_adam_pack_all(m->x3 ? MPU_F32X3 : dt, jobs, opt->params, r.grads, opt->am, opt->av, m->n_params, opt->packed,
-                                    opt->step, opt->t, opt->lr, opt->b1, opt->b2, opt->eps, r.st);   // (x3: operand words written here)
+        return launch_adam_pack(m->x3 ? MPU_F32X3 : dt, jobs, opt->params, r.grads, opt->am, opt->av, all_lo, all_hi, 1, opt->packed,
+                                opt->step, false, opt->t, opt->lr, opt->b1, opt->b2, opt->eps, false, r.st);   // (x3: operand words written here)
     }
     // (from here on a device step counter already holds this step's number: launch_head_backward advanced it)
     long lo = 0, hi = 0;                                         // the early range: longest run of convs outside the taps group
@@ -863,12 +868,11 @@ int finish_backward(const Run& r, const AdamOpt* opt) {
             i = j + 1;
         }
     }
-    const long all_lo[1] = {0}, all_hi[1] = {m->n_params};
     if (hi - lo < (1L << 20)) {                                  // nothing worth a second stream
         RC(flush_wgrad_group(dt, r.grp, r.st));
         RC(flush_wgrad_reduces(r.rq, r.st));
-        return launch_adam_pack_ranges(dt, jobs, opt->params, r.grads, opt->am, opt->av, all_lo, all_hi, 1, opt->packed, opt->step,
-                                       opt->t, opt->lr, opt->b1, opt->b2, opt->eps, false, r.st);
+        return launch_adam_pack(dt, jobs, opt->params, r.grads, opt->am, opt->av, all_lo, all_hi, 1, opt->packed, opt->step, true,
+                                opt->t, opt->lr, opt->b1, opt->b2, opt->eps, false, r.st);
     }
     SideStream* sd = nullptr;
     RC(side_stream(&sd));
@@ -879,8 +883,8 @@ int finish_backward(const Run& r, const AdamOpt* opt) {
     MPU_CHECK_HIP(hipEventRecord(sd->fork, r.st));
     MPU_CHECK_HIP(hipStreamWaitEvent(sd->s, sd->fork, 0));
     tail_stamp(2, sd->s);
-    RC(launch_adam_pack_ranges(dt, jobs, opt->params, r.grads, opt->am, opt->av, &lo, &hi, 1, opt->packed, opt->step, opt->t, opt->lr,
-                               opt->b1, opt->b2, opt->eps, true, sd->s));
+    RC(launch_adam_pack(dt, jobs, opt->params, r.grads, opt->am, opt->av, &lo, &hi, 1, opt->packed, opt->step, true, opt->t, opt->lr,
+                        opt->b1, opt->b2, opt->eps, true, sd->s));
     tail_stamp(3, sd->s);
     MPU_CHECK_HIP(hipEventRecord(sd->join, sd->s));
     if (sched_log_on()) sched_note("tail-overlap adam range=[%ld,%ld) of %ld", lo, hi, m->n_params);
@@ -889,8 +893,8 @@ int finish_backward(const Run& r, const AdamOpt* opt) {
     RC(flush_wgrad_reduces(r.rq, r.st, WG_ALL));
     tail_stamp(5, r.st);
     const long rest_lo[2] = {0, hi}, rest_hi[2] = {lo, m->n_params};       // everything else in ONE launch
-    RC(launch_adam_pack_ranges(dt, jobs, opt->params, r.grads, opt->am, opt->av, rest_lo, rest_hi, 2, opt->packed, opt->step, opt->t,
-                               opt->lr, opt->b1, opt->b2, opt->eps, false, r.st));
+    RC(launch_adam_pack(dt, jobs, opt->params, r.grads, opt->am, opt->av, rest_lo, rest_hi, 2, opt->packed, opt->step, true, opt->t,
+                        opt->lr, opt->b1, opt->b2, opt->eps, false, r.st));
     tail_stamp(6, r.st);
     MPU_CHECK_HIP(hipStreamWaitEvent(r.st, sd->join, 0));           // the side branch joins at the very end
     tail_stamp(7, r.st);
@@ -1031,14 +1035,8 @@ int64_t mpu_unet_workspace_loss_mean_offset(const mpu_unet* m, int32_t batch) {
 
 int mpu_unet_pack_weights(const mpu_unet* m, const float* d_params, void* d_packed, void* stream) {
     MPU_REQUIRE(m && d_params && d_packed, "mpu_unet_pack_weights: null argument");
-    PackTable tab; tab.njobs = 0; tab._pad = 0;
-    for (const Conv& c : m->conv) {
-        if (c.mode == CONV1) continue;
-        MPU_REQUIRE(tab.njobs < PACK_MAX_JOBS, "mpu_unet_pack_weights: too many layers");
-        PackJob& j = tab.job[tab.njobs++];
-        j.mode = c.mode; j.Cin = c.Cin; j.Cout = c.Cout; j.unit_begin = j.fwd_units = j._pad = 0;
-        j.w = c.w; j.wf = c.wf; j.wd = c.wd;
-    }
+    PackTable tab;
+    RC(pack_jobs_of(m, tab));
     RC(launch_pack_all(m->cfg.dtype, tab, d_params, d_packed, (hipStream_t)stream));
     return m->x3 ? launch_x3_words(d_packed, m->n_packed, (hipStream_t)stream) : MPU_OK;
 }
@@ -1047,16 +1045,11 @@ int mpu_unet_adam_pack(const mpu_unet* m, float* d_params, const float* d_grads,
                        int64_t* d_step, double lr, double beta1, double beta2, double eps, void* d_packed, void* stream) {
     MPU_REQUIRE(m && d_params && d_grads && d_m && d_v && d_packed, "mpu_unet_adam_pack: null argument");
     MPU_REQUIRE(d_step || t >= 1, "mpu_unet_adam_pack: need a device step counter or a 1-based step number");
-    PackTable tab; tab.njobs = 0; tab._pad = 0;
-    for (const Conv& c : m->conv) {
-        if (c.mode == CONV1) continue;
-        MPU_REQUIRE(tab.njobs < PACK_MAX_JOBS, "mpu_unet_adam_pack: too many layers");
-        PackJob& j = tab.job[tab.njobs++];
-        j.mode = c.mode; j.Cin = c.Cin; j.Cout = c.Cout; j.unit_begin = j.fwd_units = j._pad = 0;
-        j.w = c.w; j.wf = c.wf; j.wd = c.wd;
-    }
-    return launch_adam_pack_all(m->x3 ? MPU_F32X3 : m->cfg.dtype, tab, d_params, d_grads, d_m, d_v, m->n_params, d_packed,
-                                (long long*)d_step, (long long)t, lr, beta1, beta2, (float)eps, (hipStream_t)stream);
+    PackTable tab;
+    RC(pack_jobs_of(m, tab));
+    const long lo = 0, hi = m->n_params;
+    return launch_adam_pack(m->x3 ? MPU_F32X3 : m->cfg.dtype, tab, d_params, d_grads, d_m, d_v, &lo, &hi, 1, d_packed,
+                            (long long*)d_step, false, (long long)t, lr, beta1, beta2, (float)eps, false, (hipStream_t)stream);
 }
 
 int mpu_unet_prepare_inference(const mpu_unet* m, const float* d_params, const float* d_bn_state, void* d_packed,
@@ -1160,15 +1153,13 @@ int64_t mpu_unet_l2_workspace_doubles(void) { return L2_PARTIAL_DOUBLES; }
 int mpu_adam_step(float* d_params, const float* d_grads, float* d_m, float* d_v, int64_t n, int64_t t,
                   double lr, double beta1, double beta2, double eps, void* stream) {
     MPU_REQUIRE(d_params && d_grads && d_m && d_v && n >= 0 && t >= 1, "mpu_adam_step: bad argument");
-    const double alpha = lr * std::sqrt(1.0 - std::pow(beta2, (double)t)) / (1.0 - std::pow(beta1, (double)t));
-    return launch_adam(d_params, d_grads, d_m, d_v, n, (float)alpha, (float)beta1, (float)beta2, (float)eps,
-                       (hipStream_t)stream);
+    return launch_adam(d_params, d_grads, d_m, d_v, n, nullptr, (long long)t, lr, beta1, beta2, (float)eps, (hipStream_t)stream);
 }
 
 int mpu_adam_step_device_counter(float* d_params, const float* d_grads, float* d_m, float* d_v, int64_t n,
                                  int64_t* d_step, double lr, double beta1, double beta2, double eps, void* stream) {
     MPU_REQUIRE(d_params && d_grads && d_m && d_v && d_step && n >= 0, "mpu_adam_step_device_counter: bad argument");
-    return launch_adam_dev(d_params, d_grads, d_m, d_v, n, (long long*)d_step, lr, beta1, beta2, (float)eps, (hipStream_t)stream);
+    return launch_adam(d_params, d_grads, d_m, d_v, n, (long long*)d_step, 0, lr, beta1, beta2, (float)eps, (hipStream_t)stream);
 }
 
 // ---- op-level entry points (unit tests, integration of single layers) ------

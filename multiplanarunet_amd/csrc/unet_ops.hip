@@ -1,8 +1,8 @@
-// Memory-bound U-Net kernels around the MFMA convolutions: weight packing,
+// Memory-bound U-Net kernels around the MFMA convolutions: input cast / pad,
 // BatchNormalization (train statistics / apply / backward), 2x2 max-pool and its
 // gradient, bias-gradient column sums, the 1x1 softmax head with the Keras
-// sparse-CE gradient, and Adam. All activations are [M][C] (NHWC flattened),
-// C a multiple of 8; every kernel moves 16 B per lane.
+// sparse-CE gradient (weight packing and Adam: optimizer.hip). All activations are
+// [M][C] (NHWC flattened), C a multiple of 8; every kernel moves 16 B per lane.
 //
 // Reference semantics: mpunet/models/unet.py:114-216 (layer order), Keras
 // defaults restated in SURVEY.md section 8a rows a6/a7, oracle/unet_ref.py.
@@ -11,36 +11,6 @@
 #include "reduce.h"
 
 namespace mpu {
-
-template <typename T> struct Vec;   // one 16-byte chunk of T as floats
-template <> struct Vec<float> {
-    static constexpr int N = 4;
-    static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-        const float4 t = *(const float4*)p; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-    static __device__ __forceinline__ void store(float* p, const float (&v)[4]) {
-        *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
-    }
-};
-template <> struct Vec<bf16_t> {
-    static constexpr int N = 8;
-    static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[8]) {
-        const uint4 t = *(const uint4*)p;
-        const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = __uint_as_float(w[i] << 16);
-            v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    }
-    static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[8]) {
-        uint32_t w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            w[i] = f32x2_to_bf16x2(v[2 * i], v[2 * i + 1]);
-        *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-};
 
 constexpr int COEF_LDS_C = 1024;      // per-channel coefficient tables up to this many channels are staged in LDS
 template <int NTAB>
@@ -59,214 +29,6 @@ __device__ __forceinline__ void coef_load(const float* lds, const float* __restr
 #pragma unroll
         for (int i = 0; i < N; i += 4) *reinterpret_cast<float4*>(out + i) = *reinterpret_cast<const float4*>(glob + off + i);
     }
-}
-
-static inline int ew_grid(long work) {
-    long b = (work + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
-
-// ------------------------------------------------------------------------- //
-// weight packing: fp32 master (Keras HWIO = [tap][ci][co]) -> MFMA operands
-// ------------------------------------------------------------------------- //
-// forward operand [tap][co][ci]: 32x32 tiles transposed through LDS (coalesced reads along co,
-// coalesced writes along ci)
-template <typename T>
-__global__ __launch_bounds__(256) void pack_fwd_kernel(int ntaps, const float* __restrict__ W, int Cin, int Cout,
-                                                       T* __restrict__ wf) {
-    __shared__ float tile[32][33];
-    const int tci = (Cin + 31) / 32, tco = (Cout + 31) / 32;
-    const long ntiles = (long)ntaps * tci * tco;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
-    for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const int tap = (int)(t / (tci * tco)); const int r = (int)(t % (tci * tco));
-        const int ci0 = (r / tco) * 32, co0 = (r % tco) * 32;
-        const float* src = W + (long)tap * Cin * Cout;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int ci = ci0 + ty + 8 * k, co = co0 + tx;
-            tile[ty + 8 * k][tx] = (ci < Cin && co < Cout) ? src[(long)ci * Cout + co] : 0.f;
-        }
-        __syncthreads();
-        T* dst = wf + (long)tap * Cin * Cout;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int co = co0 + ty + 8 * k, ci = ci0 + tx;
-            if (ci < Cin && co < Cout) dst[(long)co * Cin + ci] = from_f32<T>(tile[tx][ty + 8 * k]);
-        }
-        __syncthreads();
-    }
-}
-
-// data-gradient operand [tap'][ci][co] (same element order as the Keras kernel: coalesced)
-template <typename T>
-__global__ void pack_dgrad_kernel(int mode, const float* __restrict__ W, int Cin, int Cout, T* __restrict__ wd) {
-    const long per_tap = (long)Cin * Cout;
-    if (mode == CONV1) {
-        for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < per_tap; e += (long)gridDim.x * blockDim.x)
-            wd[e] = from_f32<T>(W[e]);
-        return;
-    }
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < 9 * per_tap;
-         e += (long)gridDim.x * blockDim.x) {
-        const int tp = (int)(e / per_tap); const long r = e % per_tap;
-        float v;
-        if (mode == CONV3) {
-            v = W[(long)(8 - tp) * per_tap + r];                 // 180-degree rotated taps
-        } else {                                                  // UPCONV2 -> 3x3 stride-2 combined taps
-            const int dy = tp / 3 - 1, dx = tp % 3 - 1;           // S(-1)={1}, S(0)={0,1}, S(1)={0}
-            v = 0.f;
-            for (int ky = 0; ky < 2; ++ky) {
-                if ((dy == -1 && ky != 1) || (dy == 1 && ky != 0)) continue;
-                for (int kx = 0; kx < 2; ++kx) {
-                    if ((dx == -1 && kx != 1) || (dx == 1 && kx != 0)) continue;
-                    v += W[(long)(ky * 2 + kx) * per_tap + r];
-                }
-            }
-        }
-        wd[e] = from_f32<T>(v);
-    }
-}
-
-// ---- all layers of a model in ONE launch ------------------------------------------------------
-// unit = one 32x32 forward tile, or one 1024-element chunk of the data-gradient operand; the job
-// table travels in the kernel arguments (no device-side table to keep in sync).
-template <typename T>
-__device__ __forceinline__ void pack_fwd_tile(const PackJob& j, int t, const float* __restrict__ params, T* packed,
-                                              float (*tile)[65]) {
-    // 64x64 tile: 16-byte reads along co, transpose through LDS, 16-byte writes along ci
-    constexpr int N = Vec<T>::N;
-    const int Cin = j.Cin, Cout = j.Cout;
-    const int tci = (Cin + 63) / 64, tco = (Cout + 63) / 64;
-    const int tap = t / (tci * tco); const int r = t % (tci * tco);
-    const int ci0 = (r / tco) * 64, co0 = (r % tco) * 64;
-    const float* src = params + j.w + (long)tap * Cin * Cout;
-    {
-        const int ty = threadIdx.x >> 4, tx4 = (threadIdx.x & 15) * 4;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int cil = ty + 16 * k, ci = ci0 + cil, co = co0 + tx4;
-            // clamped, unconditional load + select (Cout % 8 == 0): the four loads of a thread are in flight together
-            const bool in = ci < Cin && co < Cout;
-            float4 v = *reinterpret_cast<const float4*>(src + (long)(ci < Cin ? ci : Cin - 1) * Cout + (co < Cout ? co : Cout - 4));
-            if (!in) v = make_float4(0.f, 0.f, 0.f, 0.f);
-            tile[cil][tx4] = v.x; tile[cil][tx4 + 1] = v.y; tile[cil][tx4 + 2] = v.z; tile[cil][tx4 + 3] = v.w;
-        }
-    }
-    __syncthreads();
-    T* dst = packed + j.wf + (long)tap * Cin * Cout;
-    constexpr int GPR = 64 / N, RPP = 256 / GPR;                  // 16-byte groups per co row, co rows per pass
-#pragma unroll
-    for (int pass = 0; pass < 64 / RPP; ++pass) {
-        const int col = threadIdx.x / GPR + pass * RPP, cil = (threadIdx.x % GPR) * N;
-        const int co = co0 + col, ci = ci0 + cil;
-        if (ci < Cin && co < Cout) {                              // Cin % 8 == 0: the whole vector is in range
-            float v[N];
-#pragma unroll
-            for (int e = 0; e < N; ++e) v[e] = tile[cil + e][col];
-            Vec<T>::store(dst + (long)co * Cin + ci, v);
-        }
-    }
-}
-
-template <typename T>
-__device__ __forceinline__ void pack_dgrad_chunk(const PackJob& j, int chunk, const float* __restrict__ params, T* packed) {
-    const long per_tap = (long)j.Cin * j.Cout;                 // multiple of 64: 8 consecutive elements never straddle taps
-    const long e = (long)chunk * 2048 + threadIdx.x * 8;
-    if (e >= 9 * per_tap) return;
-    const int tp = (int)(e / per_tap); const long r = e % per_tap;
-    const float* W = params + j.w;
-    float v[8];
-    auto load8 = [&](const float* p, float* o) {
-        const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-    };
-    if (j.mode == CONV3) {
-        load8(W + (long)(8 - tp) * per_tap + r, v);            // 180-degree rotated taps
-    } else {                                                    // UPCONV2 -> 3x3 stride-2 combined taps
-        const int dy = tp / 3 - 1, dx = tp % 3 - 1;             // S(-1)={1}, S(0)={0,1}, S(1)={0}
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = 0.f;
-        for (int ky = 0; ky < 2; ++ky) {
-            if ((dy == -1 && ky != 1) || (dy == 1 && ky != 0)) continue;
-            for (int kx = 0; kx < 2; ++kx) {
-                if ((dx == -1 && kx != 1) || (dx == 1 && kx != 0)) continue;
-                float u[8];
-                load8(W + (long)(ky * 2 + kx) * per_tap + r, u);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] += u[i];
-            }
-        }
-    }
-    T* dst = packed + j.wd + e;
-    constexpr int N = Vec<T>::N;
-#pragma unroll
-    for (int h = 0; h < 8 / N; ++h) {
-        float w[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) w[i] = v[h * N + i];
-        Vec<T>::store(dst + h * N, w);
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void pack_all_kernel(PackTable tab, const float* __restrict__ params, T* packed) {
-    __shared__ float tile[64][65];
-    int ji = 0;
-    while (ji + 1 < tab.njobs && (int)blockIdx.x >= tab.job[ji + 1].unit_begin) ++ji;
-    const PackJob& j = tab.job[ji];
-    const int u = (int)blockIdx.x - j.unit_begin;
-    if (u < j.fwd_units) pack_fwd_tile<T>(j, u, params, packed, tile);
-    else pack_dgrad_chunk<T>(j, u - j.fwd_units, params, packed);
-}
-
-int launch_pack_all(int dtype, PackTable& tab, const float* params, void* packed, hipStream_t st) {
-    int units = 0;
-    for (int i = 0; i < tab.njobs; ++i) {
-        PackJob& j = tab.job[i];
-        const int ntaps = j.mode == UPCONV2 ? 4 : 9;
-        j.unit_begin = units;
-        j.fwd_units = ntaps * cdiv(j.Cin, 64) * cdiv(j.Cout, 64);
-        units += j.fwd_units + (int)cdiv(9L * j.Cin * j.Cout, 2048L);
-    }
-    if (units == 0) return MPU_OK;
-    if (dtype == MPU_BF16) pack_all_kernel<bf16_t><<<units, 256, 0, st>>>(tab, params, (bf16_t*)packed);
-    else pack_all_kernel<float><<<units, 256, 0, st>>>(tab, params, (float*)packed);
-    return launch_ok();
-}
-
-// dtype "bf16x3": packed f32 operands -> (bf16 hi | bf16 lo << 16) words, in place, after every refresh of the packed copies
-// (common.h: x3_word / x3_unpack). n = 32-bit words.
-__global__ __launch_bounds__(256) void x3_words_kernel(uint32_t* __restrict__ buf, long n) {
-    const long i4 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i4 + 4 <= n) {
-        uint4 v = *reinterpret_cast<uint4*>(buf + i4);
-        v.x = x3_word(__uint_as_float(v.x)); v.y = x3_word(__uint_as_float(v.y));
-        v.z = x3_word(__uint_as_float(v.z)); v.w = x3_word(__uint_as_float(v.w));
-        *reinterpret_cast<uint4*>(buf + i4) = v;
-    } else {
-        for (long i = i4; i < n; ++i) buf[i] = x3_word(__uint_as_float(buf[i]));
-    }
-}
-int launch_x3_words(void* buf, long n, hipStream_t st) {
-    if (n <= 0) return MPU_OK;
-    x3_words_kernel<<<(unsigned)((n + 1023) / 1024), 256, 0, st>>>((uint32_t*)buf, n);
-    return launch_ok();
-}
-
-int launch_pack_weights(int dtype, int mode, const float* W, int Cin, int Cout, void* wf, void* wd, hipStream_t st) {
-    const int ntaps = mode == UPCONV2 ? 4 : (mode == CONV1 ? 1 : 9);
-    long tiles = (long)ntaps * cdiv(Cin, 32) * cdiv(Cout, 32);
-    if (tiles > 4096) tiles = 4096;
-    const long n = 9L * Cin * Cout;
-    if (dtype == MPU_BF16) {
-        pack_fwd_kernel<bf16_t><<<(unsigned)tiles, 256, 0, st>>>(ntaps, W, Cin, Cout, (bf16_t*)wf);
-        if (wd) pack_dgrad_kernel<bf16_t><<<ew_grid(n), 256, 0, st>>>(mode, W, Cin, Cout, (bf16_t*)wd);
-    } else {
-        pack_fwd_kernel<float><<<(unsigned)tiles, 256, 0, st>>>(ntaps, W, Cin, Cout, (float*)wf);
-        if (wd) pack_dgrad_kernel<float><<<ew_grid(n), 256, 0, st>>>(mode, W, Cin, Cout, (float*)wd);
-    }
-    return launch_ok();
 }
 
 // one thread = one group of 8 output channels of one pixel (Cpad % 8 == 0): clamped unconditional loads (a predicated
@@ -2136,594 +1898,6 @@ int launch_head_bn_bwd_apply(int dtype, const void* x, const float* probs, const
                                                                                                        beta, mean, invstd, dgamma, dbeta, dWh, coeffs, (float*)dz, hl))))
     }
     if (sched_log_on()) sched_note("bn_fold bwd C=64 rows=-1 head=1 grid=%ld", blocks);
-    return launch_ok();
-}
-
-// TF ApplyAdam: m += (g-m)(1-b1); v += (g*g-v)(1-b2); p -= m*alpha/(sqrt(v)+eps)
-// (one definition for the plain and the fused kernels: the same instruction sequence, bit-identical results)
-// No FMA contraction inside (pragma): the compiler contracted the multiply-adds in one kernel and not in the other, and
-// the fused and the plain path differed by one ulp in 1.4 % of the first moments (HIP's __fadd_rn & co. are plain
-// operators and contract just the same).
-__device__ __forceinline__ void adam_update(float gg, float& m, float& v, float& p, float alpha, float b1, float b2, float eps) {
-#pragma clang fp contract(off)
-    const float d1 = gg - m, o1 = 1.f - b1;
-    const float mm = m + d1 * o1;
-    const float g2 = gg * gg;
-    const float d2 = g2 - v, o2 = 1.f - b2;
-    const float vv = v + d2 * o2;
-    m = mm; v = vv;
-    const float num = mm * alpha, den = sqrtf(vv) + eps;
-    p = p - num / den;
-}
-// step_bias: 1 = the counter holds t - 1 (the caller increments it after the update), 0 = it already holds t
-__device__ __forceinline__ float adam_alpha_dev(const long long* step, double lr, double b1d, double b2d, int step_bias = 1) {
-    const double t = (double)(*step + step_bias);
-    return (float)(lr * sqrt(1.0 - pow(b2d, t)) / (1.0 - pow(b1d, t)));
-}
-
-// ---- Adam + weight packing in ONE pass (round 3) ---------------------------------------------------------------
-// The separate chain read the gradients and wrote the parameters (adam_kernel), then read the parameters twice more
-// to write the two bf16 operand copies (pack_all_kernel). Here a unit loads g, m, v, p of one kernel tile, updates
-// them, and writes m, v, p AND both packed copies from the tile: 0.25 GB less traffic per step and one launch less.
-//   CONV3 job  : unit = (tap, 64 ci, 64 co) tile; forward copy [tap][co][ci] transposed through LDS, data-gradient
-//                copy [8 - tap][ci][co] from the same tile (16-byte stores).
-//   UPCONV2 job: unit = (32 ci, 32 co) x the four taps (the data-gradient copy is the 3x3 stride-2 combination
-//                W_eff[dy][dx] = sum of the taps S(dy) x S(dx), which needs all four updated taps of an element).
-//   plain units: everything that is not a 3x3 / 2x2 kernel (biases, BatchNorm gamma / beta, the 1x1 head): Adam only,
-//                1024 floats per unit, ranges in the table.
-// dtype "bf16x3": the packed f32 operand words hold bf16 hi | bf16 lo << 16 (common.h: x3_word) -- written by the optimizer pass itself
-template <int N> __device__ __forceinline__ void x3_words_of(float (&v)[N]) {
-#pragma unroll
-    for (int e = 0; e < N; ++e) v[e] = __uint_as_float(x3_word(v[e]));
-}
-struct AdamRange { long off, n; int unit_begin, _pad; };
-constexpr int ADAM_MAX_RANGES = 48;
-struct AdamPackTable { int njobs, nranges, plain_begin, _pad; PackJob job[PACK_MAX_JOBS]; AdamRange range[ADAM_MAX_RANGES]; };
-
-template <typename T, bool X3 = false>
-__device__ __forceinline__ void adam_pack_conv3_tile(const PackJob& j, int t, float* __restrict__ params,
-                                                     const float* __restrict__ grads, float* __restrict__ am,
-                                                     float* __restrict__ av, T* packed, float (*tile)[65], float alpha,
-                                                     float b1, float b2, float eps) {
-    constexpr int N = Vec<T>::N;
-    const int Cin = j.Cin, Cout = j.Cout;
-    const int tci = (Cin + 63) / 64, tco = (Cout + 63) / 64;
-    const int tap = t / (tci * tco); const int r = t % (tci * tco);
-    const int ci0 = (r / tco) * 64, co0 = (r % tco) * 64;
-    const long base = j.w + (long)tap * Cin * Cout;
-    {
-        const int ty = threadIdx.x >> 4, tx4 = (threadIdx.x & 15) * 4;
-        float4 g4[4], m4[4], v4[4], p4[4];
-        long off[4]; bool in[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {                            // all 16 loads of the thread in flight together
-            const int ci = ci0 + ty + 16 * k, co = co0 + tx4;
-            in[k] = ci < Cin && co < Cout;
-            off[k] = base + (long)(ci < Cin ? ci : Cin - 1) * Cout + (co < Cout ? co : Cout - 4);
-            g4[k] = *reinterpret_cast<const float4*>(grads + off[k]); m4[k] = *reinterpret_cast<const float4*>(am + off[k]);
-            v4[k] = *reinterpret_cast<const float4*>(av + off[k]); p4[k] = *reinterpret_cast<const float4*>(params + off[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            adam_update(g4[k].x, m4[k].x, v4[k].x, p4[k].x, alpha, b1, b2, eps);
-            adam_update(g4[k].y, m4[k].y, v4[k].y, p4[k].y, alpha, b1, b2, eps);
-            adam_update(g4[k].z, m4[k].z, v4[k].z, p4[k].z, alpha, b1, b2, eps);
-            adam_update(g4[k].w, m4[k].w, v4[k].w, p4[k].w, alpha, b1, b2, eps);
-            if (in[k]) {                                         // (a clamped duplicate would be updated twice: in-range only)
-                *reinterpret_cast<float4*>(am + off[k]) = m4[k]; *reinterpret_cast<float4*>(av + off[k]) = v4[k];
-                *reinterpret_cast<float4*>(params + off[k]) = p4[k];
-            }
-            const int cil = ty + 16 * k;
-            const float4 q = in[k] ? p4[k] : make_float4(0.f, 0.f, 0.f, 0.f);
-            tile[cil][tx4] = q.x; tile[cil][tx4 + 1] = q.y; tile[cil][tx4 + 2] = q.z; tile[cil][tx4 + 3] = q.w;
-        }
-    }
-    __syncthreads();
-    T* dstf = packed + j.wf + (long)tap * Cin * Cout;
-    constexpr int GPR = 64 / N, RPP = 256 / GPR;
-#pragma unroll
-    for (int pass = 0; pass < 64 / RPP; ++pass) {                // forward copy [co][ci]: columns of the tile
-        const int col = threadIdx.x / GPR + pass * RPP, cil = (threadIdx.x % GPR) * N;
-        const int co = co0 + col, ci = ci0 + cil;
-        if (ci < Cin && co < Cout) {
-            float v[N];
-#pragma unroll
-            for (int e = 0; e < N; ++e) v[e] = tile[cil + e][col];
-            if (X3) x3_words_of<N>(v);
-            Vec<T>::store(dstf + (long)co * Cin + ci, v);
-        }
-    }
-    T* dstd = packed + j.wd + (long)(8 - tap) * Cin * Cout;      // data-gradient copy: 180-degree rotated taps, rows of the tile
-#pragma unroll
-    for (int pass = 0; pass < 64 / RPP; ++pass) {
-        const int row = threadIdx.x / GPR + pass * RPP, col = (threadIdx.x % GPR) * N;
-        const int ci = ci0 + row, co = co0 + col;
-        if (ci < Cin && co < Cout) {
-            float v[N];
-#pragma unroll
-            for (int e = 0; e < N; ++e) v[e] = tile[row][col + e];
-            if (X3) x3_words_of<N>(v);
-            Vec<T>::store(dstd + (long)ci * Cout + co, v);
-        }
-    }
-}
-
-template <typename T, bool X3 = false>
-__device__ __forceinline__ void adam_pack_upconv_tile(const PackJob& j, int t, float* __restrict__ params,
-                                                      const float* __restrict__ grads, float* __restrict__ am,
-                                                      float* __restrict__ av, T* packed, float (*tile64)[65], float alpha,
-                                                      float b1, float b2, float eps) {
-    constexpr int N = Vec<T>::N;
-    float (*tile)[32][33] = reinterpret_cast<float (*)[32][33]>(&tile64[0][0]);       // [4 taps][32 ci][33] (the kernel's LDS array is sized for it)
-    const int Cin = j.Cin, Cout = j.Cout;
-    const int tco = (Cout + 31) / 32;
-    const int ci0 = (t / tco) * 32, co0 = (t % tco) * 32;
-    const long per_tap = (long)Cin * Cout;
-    {
-        const int cil = threadIdx.x >> 3, tx4 = (threadIdx.x & 7) * 4;
-        const int ci = ci0 + cil, co = co0 + tx4;
-        const bool in = ci < Cin && co < Cout;
-        const long o0 = j.w + (long)(ci < Cin ? ci : Cin - 1) * Cout + (co < Cout ? co : Cout - 4);
-        float4 g4[4], m4[4], v4[4], p4[4];
-#pragma unroll
-        for (int tp = 0; tp < 4; ++tp) {
-            const long o = o0 + tp * per_tap;
-            g4[tp] = *reinterpret_cast<const float4*>(grads + o); m4[tp] = *reinterpret_cast<const float4*>(am + o);
-            v4[tp] = *reinterpret_cast<const float4*>(av + o); p4[tp] = *reinterpret_cast<const float4*>(params + o);
-        }
-#pragma unroll
-        for (int tp = 0; tp < 4; ++tp) {
-            adam_update(g4[tp].x, m4[tp].x, v4[tp].x, p4[tp].x, alpha, b1, b2, eps);
-            adam_update(g4[tp].y, m4[tp].y, v4[tp].y, p4[tp].y, alpha, b1, b2, eps);
-            adam_update(g4[tp].z, m4[tp].z, v4[tp].z, p4[tp].z, alpha, b1, b2, eps);
-            adam_update(g4[tp].w, m4[tp].w, v4[tp].w, p4[tp].w, alpha, b1, b2, eps);
-            const long o = o0 + tp * per_tap;
-            if (in) {
-                *reinterpret_cast<float4*>(am + o) = m4[tp]; *reinterpret_cast<float4*>(av + o) = v4[tp];
-                *reinterpret_cast<float4*>(params + o) = p4[tp];
-            }
-            const float4 q = in ? p4[tp] : make_float4(0.f, 0.f, 0.f, 0.f);
-            tile[tp][cil][tx4] = q.x; tile[tp][cil][tx4 + 1] = q.y; tile[tp][cil][tx4 + 2] = q.z; tile[tp][cil][tx4 + 3] = q.w;
-        }
-    }
-    __syncthreads();
-    constexpr int GPR = 32 / N;                                  // 16-byte groups per 32-element row
-    // forward copy [tap][co][ci]
-    for (int idx = threadIdx.x; idx < 4 * 32 * GPR; idx += 256) {
-        const int tp = idx / (32 * GPR), rem = idx % (32 * GPR);
-        const int col = rem / GPR, cil = (rem % GPR) * N;
-        const int co = co0 + col, ci = ci0 + cil;
-        if (ci < Cin && co < Cout) {
-            float v[N];
-#pragma unroll
-            for (int e = 0; e < N; ++e) v[e] = tile[tp][cil + e][col];
-            if (X3) x3_words_of<N>(v);
-            Vec<T>::store(packed + j.wf + tp * per_tap + (long)co * Cin + ci, v);
-        }
-    }
-    // data-gradient copy [tap'][ci][co], tap' = (dy+1)*3 + (dx+1): S(-1) = {1}, S(0) = {0, 1}, S(1) = {0} per axis
-    // (same summation order as pack_dgrad_chunk: ky outer, kx inner)
-    for (int idx = threadIdx.x; idx < 9 * 32 * GPR; idx += 256) {
-        const int tp = idx / (32 * GPR), rem = idx % (32 * GPR);
-        const int row = rem / GPR, col = (rem % GPR) * N;
-        const int ci = ci0 + row, co = co0 + col;
-        if (ci < Cin && co < Cout) {
-            const int dy = tp / 3 - 1, dx = tp % 3 - 1;
-            float v[N];
-#pragma unroll
-            for (int e = 0; e < N; ++e) v[e] = 0.f;
-            for (int ky = 0; ky < 2; ++ky) {
-                if ((dy == -1 && ky != 1) || (dy == 1 && ky != 0)) continue;
-                for (int kx = 0; kx < 2; ++kx) {
-                    if ((dx == -1 && kx != 1) || (dx == 1 && kx != 0)) continue;
-#pragma unroll
-                    for (int e = 0; e < N; ++e) v[e] += tile[ky * 2 + kx][row][col + e];
-                }
-            }
-            if (X3) x3_words_of<N>(v);
-            Vec<T>::store(packed + j.wd + tp * per_tap + (long)ci * Cout + co, v);
-        }
-    }
-}
-
-template <typename T, bool X3 = false>
-__global__ __launch_bounds__(256) void adam_pack_all_kernel(AdamPackTable tab, float* __restrict__ params,
-                                                            const float* __restrict__ grads, float* __restrict__ am,
-                                                            float* __restrict__ av, T* packed, const long long* __restrict__ step,
-                                                            double lr, double b1d, double b2d, float alpha_host, float eps, int step_bias) {
-    __shared__ float tile_raw[4 * 32 * 33];                      // >= 64 x 65: both tile views live here
-    float (*tile)[65] = reinterpret_cast<float (*)[65]>(tile_raw);
-    const float alpha = step ? adam_alpha_dev(step, lr, b1d, b2d, step_bias) : alpha_host;
-    const float b1 = (float)b1d, b2 = (float)b2d;
-    const int u0 = (int)blockIdx.x;
-    if (u0 >= tab.plain_begin) {                                 // biases, BatchNorm parameters, 1x1 head
-        int ri = 0;
-        while (ri + 1 < tab.nranges && u0 >= tab.range[ri + 1].unit_begin) ++ri;
-        const AdamRange& r = tab.range[ri];
-        const long e = (long)(u0 - r.unit_begin) * 1024 + threadIdx.x * 4;
-        if (e >= r.n) return;
-        const long o = r.off + e;
-        if (e + 4 <= r.n && (o & 3) == 0) {
-            float4 g4 = *reinterpret_cast<const float4*>(grads + o), m4 = *reinterpret_cast<float4*>(am + o),
-                   v4 = *reinterpret_cast<float4*>(av + o), p4 = *reinterpret_cast<float4*>(params + o);
-            adam_update(g4.x, m4.x, v4.x, p4.x, alpha, b1, b2, eps); adam_update(g4.y, m4.y, v4.y, p4.y, alpha, b1, b2, eps);
-            adam_update(g4.z, m4.z, v4.z, p4.z, alpha, b1, b2, eps); adam_update(g4.w, m4.w, v4.w, p4.w, alpha, b1, b2, eps);
-            *reinterpret_cast<float4*>(am + o) = m4; *reinterpret_cast<float4*>(av + o) = v4; *reinterpret_cast<float4*>(params + o) = p4;
-        } else {
-            for (int i = 0; i < 4 && e + i < r.n; ++i) {
-                float mm = am[o + i], vv = av[o + i], pp = params[o + i];
-                adam_update(grads[o + i], mm, vv, pp, alpha, b1, b2, eps);
-                am[o + i] = mm; av[o + i] = vv; params[o + i] = pp;
-            }
-        }
-        return;
-    }
-    int ji = 0;
-    while (ji + 1 < tab.njobs && u0 >= tab.job[ji + 1].unit_begin) ++ji;
-    const PackJob& j = tab.job[ji];
-    const int u = u0 - j.unit_begin;
-    if (j.mode == UPCONV2) adam_pack_upconv_tile<T, X3>(j, u, params, grads, am, av, packed, tile, alpha, b1, b2, eps);
-    else adam_pack_conv3_tile<T, X3>(j, u, params, grads, am, av, packed, tile, alpha, b1, b2, eps);
-}
-
-__global__ void incr_step_kernel(long long* step);
-
-// jobs: the 3x3 / 2x2 conv kernels (PackTable fields w, wf, wd, mode, Cin, Cout set); n_params = length of the flat buffers.
-int launch_adam_pack_all(int dtype, PackTable& jobs, float* params, const float* grads, float* am, float* av, long n_params,
-                         void* packed, long long* step, long long t_host, double lr, double b1, double b2, float eps,
-                         hipStream_t st) {
-    AdamPackTable tab; tab.njobs = jobs.njobs; tab.nranges = 0; tab._pad = 0;
-    int units = 0;
-    for (int i = 0; i < jobs.njobs; ++i) {
-        PackJob& j = jobs.job[i];
-        if (i > 0 && jobs.job[i - 1].w > j.w) return fail(MPU_EINVAL, "%s", "adam_pack: jobs must be ordered by parameter offset");
-        j.unit_begin = units;
-        j.fwd_units = j.mode == UPCONV2 ? cdiv(j.Cin, 32) * cdiv(j.Cout, 32) : 9 * cdiv(j.Cin, 64) * cdiv(j.Cout, 64);
-        units += j.fwd_units;
-        tab.job[i] = j;
-    }
-    tab.plain_begin = units;
-    long cur = 0;                                                // the complement of the packed kernels inside [0, n_params)
-    for (int i = 0; i <= jobs.njobs; ++i) {
-        const long lo = i < jobs.njobs ? jobs.job[i].w : n_params;
-        if (lo > cur) {
-            if (tab.nranges >= ADAM_MAX_RANGES) return fail(MPU_EINVAL, "%s", "adam_pack: too many parameter ranges");
-            AdamRange& r = tab.range[tab.nranges++];
-            r.off = cur; r.n = lo - cur; r.unit_begin = units; r._pad = 0;
-            units += (int)cdiv(r.n, 1024L);
-        }
-        if (i < jobs.njobs) {
-            const PackJob& j = jobs.job[i];
-            cur = j.w + (long)(j.mode == UPCONV2 ? 4 : 9) * j.Cin * j.Cout;
-        }
-    }
-    if (units == 0) return MPU_OK;
-    float alpha_host = 0.f;
-    if (!step) alpha_host = (float)(lr * std::sqrt(1.0 - std::pow(b2, (double)t_host)) / (1.0 - std::pow(b1, (double)t_host)));
-    if (dtype == MPU_BF16)
-        adam_pack_all_kernel<bf16_t><<<units, 256, 0, st>>>(tab, params, grads, am, av, (bf16_t*)packed, step, lr, b1, b2, alpha_host, eps, 1);
-    else if (dtype == MPU_F32X3)                                 // (f32 storage, operand words = bf16 hi | lo: no x3_words pass afterwards)
-        adam_pack_all_kernel<float, true><<<units, 256, 0, st>>>(tab, params, grads, am, av, (float*)packed, step, lr, b1, b2, alpha_host, eps, 1);
-    else
-        adam_pack_all_kernel<float><<<units, 256, 0, st>>>(tab, params, grads, am, av, (float*)packed, step, lr, b1, b2, alpha_host, eps, 1);
-    if (step) incr_step_kernel<<<1, 1, 0, st>>>(step);
-    return launch_ok();
-}
-
-// ---- round 6: the optimizer beside the weight gradients -----------------------------------------------------------
-// adam_pack_lean_kernel (bf16 operands): the same update and the same two packed copies as adam_pack_all_kernel, but small
-// enough -- <= 64 registers, 8.5 KB of LDS -- to be CO-RESIDENT with a wgrad_taps workgroup (448 of a SIMD's 512 registers,
-// 148 of a CU's 160 KB): the grouped weight-gradient launch is bound by MFMA issue and LDS reads, this kernel by HBM, so the
-// optimizer of the parameters whose gradients are already final (the deep levels: 90 % of the bytes) runs on a second stream
-// UNDER the weight gradients of the high-resolution levels instead of behind them (run_backward_adam, unet_model.hip).
-//   CONV3 job  : unit = (tap, 64 ci, 64 co) tile as in adam_pack_all_kernel, loaded in two halves of 32 ci (8 instead of 16
-//                16-byte loads per thread in flight), the tile held in LDS as bf16 -- the values both copies store.
-//   UPCONV2 job: unit = (16 ci, 32 co) x the four taps, fp32 in LDS (the data-gradient copy sums taps in fp32 before rounding).
-//   plain units: as adam_pack_all_kernel.
-// Bit-identical to adam_pack_all_kernel (tests/test_gpu_unet.py).
-constexpr int LEAN_TP = 68;                      // bf16 tile pitch (elements): rows 8-byte aligned
-__global__ __launch_bounds__(256, 8) void adam_pack_lean_kernel(AdamPackTable tab, float* __restrict__ params,
-                                                                const float* __restrict__ grads, float* __restrict__ am,
-                                                                float* __restrict__ av, bf16_t* packed, const long long* __restrict__ step,
-                                                                double lr, double b1d, double b2d, float alpha_host, float eps, int step_bias) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[64 * LEAN_TP * 2];          // 8704 B >= 4 x 16 x 33 floats (8448)
-    const float alpha = step ? adam_alpha_dev(step, lr, b1d, b2d, step_bias) : alpha_host;
-    const float b1 = (float)b1d, b2 = (float)b2d;
-    const int u0 = (int)blockIdx.x;
-    if (u0 >= tab.plain_begin) {                                 // biases, BatchNorm parameters, 1x1 head
-        int ri = 0;
-        while (ri + 1 < tab.nranges && u0 >= tab.range[ri + 1].unit_begin) ++ri;
-        const AdamRange& r = tab.range[ri];
-        const long e = (long)(u0 - r.unit_begin) * 1024 + threadIdx.x * 4;
-        if (e >= r.n) return;
-        const long o = r.off + e;
-        if (e + 4 <= r.n && (o & 3) == 0) {
-            float4 g4 = *reinterpret_cast<const float4*>(grads + o), m4 = *reinterpret_cast<float4*>(am + o),
-                   v4 = *reinterpret_cast<float4*>(av + o), p4 = *reinterpret_cast<float4*>(params + o);
-            adam_update(g4.x, m4.x, v4.x, p4.x, alpha, b1, b2, eps); adam_update(g4.y, m4.y, v4.y, p4.y, alpha, b1, b2, eps);
-            adam_update(g4.z, m4.z, v4.z, p4.z, alpha, b1, b2, eps); adam_update(g4.w, m4.w, v4.w, p4.w, alpha, b1, b2, eps);
-            *reinterpret_cast<float4*>(am + o) = m4; *reinterpret_cast<float4*>(av + o) = v4; *reinterpret_cast<float4*>(params + o) = p4;
-        } else {
-            for (int i = 0; i < 4 && e + i < r.n; ++i) {
-                float mm = am[o + i], vv = av[o + i], pp = params[o + i];
-                adam_update(grads[o + i], mm, vv, pp, alpha, b1, b2, eps);
-                am[o + i] = mm; av[o + i] = vv; params[o + i] = pp;
-            }
-        }
-        return;
-    }
-    int ji = 0;
-    while (ji + 1 < tab.njobs && u0 >= tab.job[ji + 1].unit_begin) ++ji;
-    const PackJob& j = tab.job[ji];
-    const int t = u0 - j.unit_begin;
-    const int Cin = j.Cin, Cout = j.Cout;
-    if (j.mode != UPCONV2) {
-        bf16_t (*tile)[LEAN_TP] = reinterpret_cast<bf16_t (*)[LEAN_TP]>(lds_raw);
-        const int tci = (Cin + 63) / 64, tco = (Cout + 63) / 64;
-        const int tap = t / (tci * tco); const int r = t % (tci * tco);
-        const int ci0 = (r / tco) * 64, co0 = (r % tco) * 64;
-        const long base = j.w + (long)tap * Cin * Cout;
-        const int ty = threadIdx.x >> 4, tx4 = (threadIdx.x & 15) * 4;
-#pragma unroll 1
-        for (int half = 0; half < 2; ++half) {
-            float4 g4[2], m4[2], v4[2], p4[2];
-            long off[2]; bool in[2];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int ci = ci0 + ty + 16 * (2 * half + k), co = co0 + tx4;
-                in[k] = ci < Cin && co < Cout;
-                off[k] = base + (long)(ci < Cin ? ci : Cin - 1) * Cout + (co < Cout ? co : Cout - 4);
-                g4[k] = *reinterpret_cast<const float4*>(grads + off[k]); m4[k] = *reinterpret_cast<const float4*>(am + off[k]);
-                v4[k] = *reinterpret_cast<const float4*>(av + off[k]); p4[k] = *reinterpret_cast<const float4*>(params + off[k]);
-            }
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                adam_update(g4[k].x, m4[k].x, v4[k].x, p4[k].x, alpha, b1, b2, eps);
-                adam_update(g4[k].y, m4[k].y, v4[k].y, p4[k].y, alpha, b1, b2, eps);
-                adam_update(g4[k].z, m4[k].z, v4[k].z, p4[k].z, alpha, b1, b2, eps);
-                adam_update(g4[k].w, m4[k].w, v4[k].w, p4[k].w, alpha, b1, b2, eps);
-                if (in[k]) {
-                    *reinterpret_cast<float4*>(am + off[k]) = m4[k]; *reinterpret_cast<float4*>(av + off[k]) = v4[k];
-                    *reinterpret_cast<float4*>(params + off[k]) = p4[k];
-                }
-                const int cil = ty + 16 * (2 * half + k);
-                const float4 q = in[k] ? p4[k] : make_float4(0.f, 0.f, 0.f, 0.f);
-                *reinterpret_cast<uint2*>(&tile[cil][tx4]) = make_uint2(f32x2_to_bf16x2(q.x, q.y), f32x2_to_bf16x2(q.z, q.w));
-            }
-        }
-        __syncthreads();
-        bf16_t* dstf = packed + j.wf + (long)tap * Cin * Cout;
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {                   // forward copy [co][ci]: columns of the tile
-            const int col = threadIdx.x / 8 + pass * 32, cil = (threadIdx.x % 8) * 8;
-            const int co = co0 + col, ci = ci0 + cil;
-            if (ci < Cin && co < Cout) {
-                uint32_t w[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) w[e] = (uint32_t)tile[cil + 2 * e][col] | ((uint32_t)tile[cil + 2 * e + 1][col] << 16);
-                *reinterpret_cast<uint4*>(dstf + (long)co * Cin + ci) = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-        }
-        bf16_t* dstd = packed + j.wd + (long)(8 - tap) * Cin * Cout;      // data-gradient copy: rotated taps, rows of the tile
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            const int row = threadIdx.x / 8 + pass * 32, col = (threadIdx.x % 8) * 8;
-            const int ci = ci0 + row, co = co0 + col;
-            if (ci < Cin && co < Cout) {
-                const uint2 a = *reinterpret_cast<const uint2*>(&tile[row][col]), b = *reinterpret_cast<const uint2*>(&tile[row][col + 4]);
-                *reinterpret_cast<uint4*>(dstd + (long)ci * Cout + co) = make_uint4(a.x, a.y, b.x, b.y);
-            }
-        }
-        return;
-    }
-    // UPCONV2: unit = (16 ci, 32 co) x four taps
-    float (*tile)[16][33] = reinterpret_cast<float (*)[16][33]>(lds_raw);
-    const int tco = (Cout + 31) / 32;
-    const int ci0 = (t / tco) * 16, co0 = (t % tco) * 32;
-    const long per_tap = (long)Cin * Cout;
-    {
-        const int th = threadIdx.x >> 7, cil = (threadIdx.x & 127) >> 3, tx4 = (threadIdx.x & 7) * 4;
-        const int ci = ci0 + cil, co = co0 + tx4;
-        const bool in = ci < Cin && co < Cout;
-        const long o0 = j.w + (long)(ci < Cin ? ci : Cin - 1) * Cout + (co < Cout ? co : Cout - 4);
-        float4 g4[2], m4[2], v4[2], p4[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const long o = o0 + (2 * th + k) * per_tap;
-            g4[k] = *reinterpret_cast<const float4*>(grads + o); m4[k] = *reinterpret_cast<const float4*>(am + o);
-            v4[k] = *reinterpret_cast<const float4*>(av + o); p4[k] = *reinterpret_cast<const float4*>(params + o);
-        }
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int tp = 2 * th + k;
-            adam_update(g4[k].x, m4[k].x, v4[k].x, p4[k].x, alpha, b1, b2, eps);
-            adam_update(g4[k].y, m4[k].y, v4[k].y, p4[k].y, alpha, b1, b2, eps);
-            adam_update(g4[k].z, m4[k].z, v4[k].z, p4[k].z, alpha, b1, b2, eps);
-            adam_update(g4[k].w, m4[k].w, v4[k].w, p4[k].w, alpha, b1, b2, eps);
-            const long o = o0 + tp * per_tap;
-            if (in) {
-                *reinterpret_cast<float4*>(am + o) = m4[k]; *reinterpret_cast<float4*>(av + o) = v4[k];
-                *reinterpret_cast<float4*>(params + o) = p4[k];
-            }
-            const float4 q = in ? p4[k] : make_float4(0.f, 0.f, 0.f, 0.f);
-            tile[tp][cil][tx4] = q.x; tile[tp][cil][tx4 + 1] = q.y; tile[tp][cil][tx4 + 2] = q.z; tile[tp][cil][tx4 + 3] = q.w;
-        }
-    }
-    __syncthreads();
-    // forward copy [tap][co][ci]: 16 ci = two 16-byte groups per (tap, co)
-    {
-        const int tp = threadIdx.x >> 6, col = (threadIdx.x & 63) >> 1, cil = (threadIdx.x & 1) * 8;
-        const int co = co0 + col, ci = ci0 + cil;
-        if (ci < Cin && co < Cout) {
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = tile[tp][cil + e][col];
-            Vec<bf16_t>::store(packed + j.wf + tp * per_tap + (long)co * Cin + ci, v);
-        }
-    }
-    // data-gradient copy [tap'][ci][co], tap' = (dy+1)*3 + (dx+1): S(-1) = {1}, S(0) = {0, 1}, S(1) = {0} per axis
-    // (same summation order as adam_pack_upconv_tile / pack_dgrad_chunk: ky outer, kx inner)
-    for (int idx = threadIdx.x; idx < 9 * 16 * 4; idx += 256) {
-        const int tp = idx / 64, rem = idx % 64;
-        const int row = rem / 4, col = (rem % 4) * 8;
-        const int ci = ci0 + row, co = co0 + col;
-        if (ci < Cin && co < Cout) {
-            const int dy = tp / 3 - 1, dx = tp % 3 - 1;
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = 0.f;
-            for (int ky = 0; ky < 2; ++ky) {
-                if ((dy == -1 && ky != 1) || (dy == 1 && ky != 0)) continue;
-                for (int kx = 0; kx < 2; ++kx) {
-                    if ((dx == -1 && kx != 1) || (dx == 1 && kx != 0)) continue;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] += tile[ky * 2 + kx][row][col + e];
-                }
-            }
-            Vec<bf16_t>::store(packed + j.wd + tp * per_tap + (long)ci * Cout + co, v);
-        }
-    }
-}
-
-// Adam + pack of the parameters in the nr (<= 2) ascending, disjoint ranges [p_lo[k], p_hi[k]) only (jobs: every packed kernel
-// of the model, ordered by offset; a job is taken when its kernel lies inside a range, which must not cut one). lean: the
-// co-resident kernel above (bf16 only). The device step counter (step != NULL) must already hold THIS step's number t
-// (step_bias 0): mpu_unet_backward_adam advances it at the start of the backward pass, so that no launch of the tail has to
-// wait for "every reader is done" before it moves.
-int launch_adam_pack_ranges(int dtype, PackTable& jobs, float* params, const float* grads, float* am, float* av, const long* p_lo,
-                            const long* p_hi, int nr, void* packed, long long* step, long long t_host, double lr, double b1,
-                            double b2, float eps, bool lean, hipStream_t st) {
-    AdamPackTable tab; tab.njobs = 0; tab.nranges = 0; tab._pad = 0;
-    const bool use_lean = lean && dtype == MPU_BF16;
-    int units = 0;
-    long prev_w = -1;
-    int job_range[PACK_MAX_JOBS];
-    for (int i = 0; i < jobs.njobs; ++i) {
-        PackJob j = jobs.job[i];
-        if (j.w < prev_w) return fail(MPU_EINVAL, "%s", "adam_pack: jobs must be ordered by parameter offset");
-        prev_w = j.w;
-        const long end = j.w + (long)(j.mode == UPCONV2 ? 4 : 9) * j.Cin * j.Cout;
-        int in = -1;
-        for (int k = 0; k < nr; ++k) {
-            if (end <= p_lo[k] || j.w >= p_hi[k]) continue;
-            if (j.w < p_lo[k] || end > p_hi[k]) return fail(MPU_EINVAL, "%s", "adam_pack: a parameter range cuts a kernel");
-            in = k;
-        }
-        if (in < 0) continue;
-        j.unit_begin = units;
-        j.fwd_units = j.mode == UPCONV2 ? cdiv(j.Cin, use_lean ? 16 : 32) * cdiv(j.Cout, 32) : 9 * cdiv(j.Cin, 64) * cdiv(j.Cout, 64);
-        units += j.fwd_units;
-        job_range[tab.njobs] = in;
-        tab.job[tab.njobs++] = j;
-    }
-    tab.plain_begin = units;
-    for (int k = 0; k < nr; ++k) {                               // the complement of the packed kernels inside each range
-        if (k > 0 && p_lo[k] < p_hi[k - 1]) return fail(MPU_EINVAL, "%s", "adam_pack: ranges must ascend and not overlap");
-        long cur = p_lo[k];
-        for (int i = 0; i <= tab.njobs; ++i) {
-            if (i < tab.njobs && job_range[i] != k) continue;
-            const long lo = i < tab.njobs ? tab.job[i].w : p_hi[k];
-            if (lo > cur) {
-                if (tab.nranges >= ADAM_MAX_RANGES) return fail(MPU_EINVAL, "%s", "adam_pack: too many parameter ranges");
-                AdamRange& r = tab.range[tab.nranges++];
-                r.off = cur; r.n = lo - cur; r.unit_begin = units; r._pad = 0;
-                units += (int)cdiv(r.n, 1024L);
-            }
-            if (i < tab.njobs) {
-                const PackJob& j = tab.job[i];
-                cur = j.w + (long)(j.mode == UPCONV2 ? 4 : 9) * j.Cin * j.Cout;
-            }
-        }
-    }
-    float alpha_host = 0.f;
-    if (!step) alpha_host = (float)(lr * std::sqrt(1.0 - std::pow(b2, (double)t_host)) / (1.0 - std::pow(b1, (double)t_host)));
-    if (units == 0) return MPU_OK;
-    if (use_lean) {
-        // ONE workgroup per compute unit, whatever arrives first: the launch claims 82 KB of LDS (8.5 KB used), so two of
-        // them never share a CU, and 82 + 74 KB (wgrad_taps) do. Without the cap the 7 k short workgroups of this kernel
-        // fill every CU eight deep and the weight-gradient workgroups (448 of 512 registers) wait for them to drain: the
-        // two launches then run one after the other (measured, gpurun R6c: 135 + 311 us instead of side by side).
-        constexpr int LEAN_CLAIM = 82 * 1024, LEAN_STATIC = 64 * LEAN_TP * 2;
-        static unsigned long long attr_set = 0;
-        if (first_use_on_device(attr_set)) {
-            MPU_CHECK_HIP(hipFuncSetAttribute((const void*)adam_pack_lean_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LEAN_CLAIM - LEAN_STATIC));
-            mark_used_on_device(attr_set);
-        }
-        adam_pack_lean_kernel<<<units, 256, LEAN_CLAIM - LEAN_STATIC, st>>>(tab, params, grads, am, av, (bf16_t*)packed, step, lr, b1, b2, alpha_host, eps, 0);
-    } else if (dtype == MPU_BF16)
-        adam_pack_all_kernel<bf16_t><<<units, 256, 0, st>>>(tab, params, grads, am, av, (bf16_t*)packed, step, lr, b1, b2, alpha_host, eps, 0);
-    else
-        adam_pack_all_kernel<float><<<units, 256, 0, st>>>(tab, params, grads, am, av, (float*)packed, step, lr, b1, b2, alpha_host, eps, 0);
-    return launch_ok();
-}
-
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, long n, float alpha, float b1, float b2, float eps) {
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-        float mm = m[e], vv = v[e], pp = p[e];
-        adam_update(g[e], mm, vv, pp, alpha, b1, b2, eps);
-        m[e] = mm; v[e] = vv; p[e] = pp;
-    }
-}
-// graph-replayable variant: the 1-based step count lives in device memory (a captured launch cannot take a
-// new host-computed step size on every replay)
-__global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                float* __restrict__ v, long n, const long long* __restrict__ step, double lr,
-                                double b1d, double b2d, float eps) {
-    const float alpha = adam_alpha_dev(step, lr, b1d, b2d);
-    const float b1 = (float)b1d, b2 = (float)b2d;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-        float mm = m[e], vv = v[e], pp = p[e];
-        adam_update(g[e], mm, vv, pp, alpha, b1, b2, eps);
-        m[e] = mm; v[e] = vv; p[e] = pp;
-    }
-}
-__global__ void incr_step_kernel(long long* step) { *step += 1; }
-int launch_adam_dev(float* p, const float* g, float* m, float* v, long n, long long* step, double lr, double b1,
-                    double b2, float eps, hipStream_t st) {
-    adam_dev_kernel<<<ew_grid(n), 256, 0, st>>>(p, g, m, v, n, step, lr, b1, b2, eps);
-    incr_step_kernel<<<1, 1, 0, st>>>(step);
-    return launch_ok();
-}
-
-// kernel_regularizer=l2(lambda) of the 3x3 / 2x2 conv kernels (reference unet.py:122-177,189): g += 2*lambda*W and,
-// when wanted, lambda * sum W^2 (fixed summation order: L2_BLOCKS partial sums per kernel tensor, combined by one block)
-constexpr int L2_BLOCKS = 64;
-__global__ __launch_bounds__(256) void l2_grad_kernel(L2Table tab, const float* __restrict__ p, float* __restrict__ g,
-                                                      float two_l2, double* __restrict__ partial) {
-    const long off = tab.off[blockIdx.y], n = tab.n[blockIdx.y];
-    double acc = 0.0;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)L2_BLOCKS * 256) {
-        const float w = p[off + e];
-        g[off + e] = g[off + e] + two_l2 * w;
-        acc += (double)w * (double)w;
-    }
-    if (!partial) return;
-    __shared__ double red[256];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[(long)blockIdx.y * L2_BLOCKS + blockIdx.x] = red[0];
-}
-__global__ void l2_loss_kernel(const double* __restrict__ partial, int n, float l2, float* __restrict__ out) {
-    double s = 0.0;
-    for (int i = 0; i < n; ++i) s += partial[i];
-    *out = (float)(s * (double)l2);
-}
-int launch_l2_regularizer(const L2Table& tab, const float* params, float* grads, float l2, double* partial,
-                          float* reg_loss, hipStream_t st) {
-    if (tab.njobs == 0) return MPU_OK;
-    l2_grad_kernel<<<dim3(L2_BLOCKS, tab.njobs), 256, 0, st>>>(tab, params, grads, 2.f * l2, reg_loss ? partial : nullptr);
-    if (reg_loss) l2_loss_kernel<<<1, 1, 0, st>>>(partial, tab.njobs * L2_BLOCKS, l2, reg_loss);
-    return launch_ok();
-}
-
-int launch_adam(float* p, const float* g, float* m, float* v, long n, float alpha, float b1, float b2, float eps,
-                hipStream_t st) {
-    adam_kernel<<<ew_grid(n), 256, 0, st>>>(p, g, m, v, n, alpha, b1, b2, eps);
     return launch_ok();
 }
 

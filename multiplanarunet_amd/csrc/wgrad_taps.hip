@@ -415,7 +415,7 @@ __device__ __forceinline__ void wgrad_taps_body(const WgradArgs& a, const TapsPl
     // bias sums, group 1 with taps 5-8; each stores its share of the pair's partial copy.
     // Round 6: in ROUNDS that fit the rings' own 74 KB (one pass needed 148 KB, which left a compute unit's LDS to this
     // workgroup alone): the kernel now leaves 84 KB of LDS and 64 registers per lane free, exactly the room of one
-    // workgroup of the optimizer kernel that runs beside it (adam_pack_lean_kernel, unet_ops.hip).
+    // workgroup of the optimizer kernel that runs beside it (adam_pack_lean_kernel, optimizer.hip).
     {
         constexpr int NA = (NT + 1) / 2;                                                     // taps kept by group 0
         if constexpr (NT == 9) {
