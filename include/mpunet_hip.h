@@ -386,6 +386,45 @@ int mpu_adam_step_device_counter(float* d_params, const float* d_grads, float* d
                                  int64_t* d_step, double lr, double beta1, double beta2, double eps,
                                  void* stream);
 
+/* The other optimizers `fit.optimizer` may name (mpunet/train/utils.py:100-111 resolves it in tf.keras.optimizers;
+ * `fit.optimizer_kwargs`, train_hparams.yaml:125-126) and learning-rate decay, as TF 2.3 computes them. k = steps applied
+ * before this one, t = k + 1; lr_t = lr / (1 + decay * k) (OptimizerV2._decayed_lr; decay == 0: lr itself). Arithmetic per
+ * element in f32, in the order written, no FMA contraction; the scalars are formed in f64 and rounded once.
+ *   MPU_OPT_ADAM     m += (g-m)(1-beta1); v += (g*g-v)(1-beta2); alpha = lr_t*sqrt(1-beta2^t)/(1-beta1^t);
+ *                    p -= m*alpha/(sqrt(v)+epsilon). MPU_OPT_AMSGRAD: vhat = max(vhat, v) in place of v in the root.
+ *                    Slots m, v[, vhat].                                    (ApplyAdam / ApplyAdamWithAmsgrad)
+ *   MPU_OPT_SGD      momentum == 0: p -= lr_t*g, no slot. Else a = a*momentum - lr_t*g; p += a, or with MPU_OPT_NESTEROV
+ *                    p += a*momentum - lr_t*g. Slot a.                      (ApplyGradientDescent / ApplyKerasMomentum)
+ *   MPU_OPT_RMSPROP  ms += (g*g-ms)(1-rho); MPU_OPT_CENTERED: mg += (g-mg)(1-rho), d = ms - mg*mg, else d = ms.
+ *                    momentum == 0: p -= lr_t*g/(sqrt(d)+epsilon)  (epsilon outside the root: the Python dense path);
+ *                    else mom = mom*momentum + lr_t*g/sqrt(d+epsilon); p -= mom  (inside: ApplyRMSProp /
+ *                    ApplyCenteredRMSProp). Slots ms[, mom][, mg].
+ *   MPU_OPT_ADAMAX   m += (g-m)(1-beta1); u = max(beta2*u, |g|); p -= (lr_t/(1-beta1^t))*m/(u+epsilon). Slots m, u.  (ApplyAdaMax)
+ * Fields a kind does not use are ignored; a flag of another kind is refused. */
+typedef enum { MPU_OPT_ADAM = 0, MPU_OPT_SGD = 1, MPU_OPT_RMSPROP = 2, MPU_OPT_ADAMAX = 3 } mpu_optimizer_kind;
+/* (flag value 8 is used inside the library for momentum > 0 and refused in `flags`: a new public flag starts at 16) */
+typedef enum { MPU_OPT_NESTEROV = 1, MPU_OPT_AMSGRAD = 2, MPU_OPT_CENTERED = 4 } mpu_optimizer_flag;
+typedef struct {
+    int32_t kind, flags;
+    double lr, decay, beta1, beta2, epsilon, momentum, rho;
+} mpu_optimizer_config;
+/* Number of slot buffers (0..3, each as long as the parameters, zero before the first step) of a configuration;
+ * < 0 + mpu_last_error() when it is invalid (replaces the checks of the tf.keras.optimizers constructors). */
+int mpu_optimizer_num_slots(const mpu_optimizer_config* cfg);
+/* One step on a flat buffer of n floats, element-wise (the two-pass reference form, as mpu_adam_step): replaces Keras'
+ * optimizer.apply_gradients inside Model.fit (mpunet/train/trainer.py:246). d_slots[i] for i >= mpu_optimizer_num_slots
+ * is not touched and may be NULL. d_step != NULL: step count t-1 in device memory, incremented by the call (graph replay);
+ * else t is the 1-based step. */
+int mpu_optimizer_step(const mpu_optimizer_config* cfg, float* d_params, const float* d_grads, float* const d_slots[3],
+                       int64_t n, int64_t t, int64_t* d_step, void* stream);
+/* mpu_unet_adam_pack for every configuration: the update of mpu_optimizer_step over the model's flat parameter buffer AND
+ * the refresh of the packed MFMA operands in ONE launch, bit-identical to mpu_optimizer_step followed by
+ * mpu_unet_pack_weights (tests/test_gpu_optimizers.py). A rule moves only the slots it has. t / d_step as above. Replaces
+ * optimizer.apply_gradients inside Model.fit (mpunet/train/trainer.py:246) for a project whose `fit.optimizer` is not plain
+ * Adam with decay 0; that one keeps mpu_unet_adam_pack / mpu_unet_backward_adam. */
+int mpu_unet_optimizer_pack(const mpu_unet* m, const mpu_optimizer_config* cfg, float* d_params, const float* d_grads,
+                            float* const d_slots[3], int64_t t, int64_t* d_step, void* d_packed, void* stream);
+
 /* Single-layer entry points (unit tests / layer-wise integration). Channels
  * must be multiples of 8. d_w is the fp32 Keras HWIO kernel; d_w_dgrad may be
  * NULL; sizes: fwd taps*Cin*Cout elements, dgrad 9*Cin*Cout elements.

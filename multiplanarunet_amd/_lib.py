@@ -22,6 +22,9 @@ ABI_VERSION = 2                         # mpu_abi_version() this binding was wri
 (MPU_LOSS_SPARSE_CE, MPU_LOSS_DICE, MPU_LOSS_JACCARD, MPU_LOSS_GENERALIZED_DICE, MPU_LOSS_FOCAL,
  MPU_LOSS_EXP_LOG) = range(6)
 MPU_GDL_SQUARE, MPU_GDL_SIMPLE, MPU_GDL_UNIFORM = 0, 1, 2
+# mpu_optimizer_kind / mpu_optimizer_flag
+MPU_OPT_ADAM, MPU_OPT_SGD, MPU_OPT_RMSPROP, MPU_OPT_ADAMAX = range(4)
+MPU_OPT_NESTEROV, MPU_OPT_AMSGRAD, MPU_OPT_CENTERED = 1, 2, 4
 
 
 class Axis(C.Structure):                # mpu_axis
@@ -81,6 +84,11 @@ class LossConfig(C.Structure):         # mpu_loss_config
     _fields_ = [("kind", i32), ("type_weight", i32), ("smooth", f32), ("gamma", f32), ("gamma_dice", f32),
                 ("gamma_cross", f32), ("weight_dice", f32), ("weight_cross", f32), ("n_class_weights", i32),
                 ("class_weights", f32 * 8)]
+
+
+class OptimizerConfig(C.Structure):    # mpu_optimizer_config
+    _fields_ = [("kind", i32), ("flags", i32), ("lr", f64), ("decay", f64), ("beta1", f64), ("beta2", f64),
+                ("epsilon", f64), ("momentum", f64), ("rho", f64)]
 
 
 class MpuError(RuntimeError):
@@ -166,6 +174,9 @@ _SIGS = {
     "mpu_sample_plane_stats": (C.c_int, [c_p, c_p, C.POINTER(i32), c_p, c_p, c_p, C.POINTER(ViewGeom), c_p, c_p, u8, c_p, c_p,
                                         c_p, c_p, c_p, c_p, c_p]),
     "mpu_unet_backward_adam": (C.c_int, [c_p, i32] + [c_p] * 10 + [i64, c_p, f64, f64, f64, f64, c_p]),
+    "mpu_optimizer_num_slots": (C.c_int, [C.POINTER(OptimizerConfig)]),
+    "mpu_optimizer_step": (C.c_int, [C.POINTER(OptimizerConfig), c_p, c_p, C.POINTER(c_p), i64, i64, c_p, c_p]),
+    "mpu_unet_optimizer_pack": (C.c_int, [c_p, C.POINTER(OptimizerConfig), c_p, c_p, C.POINTER(c_p), i64, c_p, c_p, c_p]),
 }
 
 

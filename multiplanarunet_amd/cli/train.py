@@ -147,6 +147,7 @@ def run(args):
         set_bias_weights_on_all_outputs(model, train_all, hp, log)
     model.compile(fit["optimizer"], fit["loss"], fit.get("metrics"), optimizer_kwargs=fit.get("optimizer_kwargs"),
                   loss_kwargs=loss_kwargs_of(fit))
+    log("Optimizer:   %s" % model.optimizer_description())              # trainer.py:98
     if world > 1:
         D.DataParallelTrainer(model)
     B = int(fit["batch_size"])

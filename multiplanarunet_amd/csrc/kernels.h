@@ -362,7 +362,7 @@ struct PackJob { int mode, Cin, Cout, unit_begin, fwd_units, _pad; long w, wf, w
 constexpr int PACK_MAX_JOBS = 40;
 struct PackTable { int njobs, _pad; PackJob job[PACK_MAX_JOBS]; };
 int launch_pack_all(int dtype, PackTable& tab, const float* params, void* packed, hipStream_t st);
-// Adam + both packed operand copies of the listed kernels in ONE launch, over the parameters in nr ascending ranges
+// plain Adam (decay == 0) + both packed operand copies of the listed kernels in ONE launch, over the parameters in nr ascending ranges
 // [p_lo[k], p_hi[k]). step != NULL: device-resident step counter (graph replay) that holds this step's number already
 // (step_is_t, see launch_head_backward) or is incremented afterwards; else t_host (1-based). lean: the register- and LDS-lean
 // kernel that is co-resident with wgrad_taps (bf16)
@@ -382,5 +382,14 @@ int launch_l2_regularizer(const L2Table& tab, const float* params, float* grads,
 // element-wise Adam on a flat buffer; step as in launch_adam_pack (a device counter is incremented afterwards)
 int launch_adam(float* p, const float* g, float* m, float* v, long n, long long* step, long long t_host, double lr, double b1,
                 double b2, float eps, hipStream_t st);
+// Every other configuration (mpu_optimizer_config: SGD, RMSprop, Adamax, AMSGrad, learning-rate decay). optimizer_num_slots
+// validates: 0..3, or MPU_EINVAL. s: the slot buffers, in the rule's order; step != NULL: device counter that holds t - 1 and
+// is incremented afterwards, else t_host (1-based). launch_optimizer_pack: the update over [0, n_params) and both packed
+// operand copies of the listed kernels in ONE launch (dtype as launch_adam_pack)
+int optimizer_num_slots(const mpu_optimizer_config& c);
+int launch_optimizer(const mpu_optimizer_config& c, float* p, const float* g, float* const s[3], long n, long long* step,
+                     long long t_host, hipStream_t st);
+int launch_optimizer_pack(int dtype, const PackTable& jobs, const mpu_optimizer_config& c, float* params, const float* grads,
+                          float* const s[3], long n_params, void* packed, long long* step, long long t_host, hipStream_t st);
 
 }  // namespace mpu

@@ -1,135 +1,17 @@
 // The optimizer and the packed MFMA operands of the U-Net: weight packing (fp32 master -> forward and data-gradient operand
-// copies), Keras Adam alone and fused with that packing, the l2 kernel regulariser. Every device unit is written once and
-// takes pointers and shapes; the kernels below only decide which unit a workgroup runs.
+// copies), the Keras optimizers (Adam / AMSGrad, Adamax, SGD, RMSprop, learning-rate decay) alone and fused with that packing, the
+// l2 kernel regulariser. Every device unit is written once and takes pointers and shapes; the kernels below only decide which
+// unit a workgroup runs, and which update rule is a compile-time parameter of theirs.
 //
-// Reference semantics: Keras Adam in the TF ApplyAdam form, kernel_regularizer=l2 (mpunet/models/unet.py:122-177,189).
-#include <cmath>
-#include "kernels.h"
+// Reference semantics: `fit.optimizer` resolved in tf.keras.optimizers (mpunet/train/utils.py:100-111), each in the form of
+// its TF ResourceApply* kernel; kernel_regularizer=l2 (mpunet/models/unet.py:122-177,189).
+#include "optimizer_units.h"
 
 namespace mpu {
-
-// index of the entry (PackJob / AdamRange, ascending unit_begin) that workgroup u belongs to
-template <typename E>
-__device__ __forceinline__ int find_unit(const E* e, int n, int u) {
-    int i = 0;
-    while (i + 1 < n && u >= e[i + 1].unit_begin) ++i;
-    return i;
-}
-
-// offset of the float4 at (ci, co) inside one [Cin][Cout] tap, clamped into it (Cout % 4 == 0): loads are unconditional and a
-// select follows, so that all loads of a thread are in flight together
-__device__ __forceinline__ long clamped_off(int ci, int co, int Cin, int Cout, bool& in) {
-    in = ci < Cin && co < Cout;
-    return (long)(ci < Cin ? ci : Cin - 1) * Cout + (co < Cout ? co : Cout - 4);
-}
-
-// unit t of a layer cut into (tap, 64 ci, 64 co) tiles
-struct Tile64 { int tap, ci0, co0; };
-__device__ __forceinline__ Tile64 tile64_of(int t, int Cin, int Cout) {
-    const int tci = (Cin + 63) / 64, tco = (Cout + 63) / 64;
-    const int tap = t / (tci * tco), r = t % (tci * tco);
-    return {tap, (r / tco) * 64, (r % tco) * 64};
-}
-
-// dtype "bf16x3": the packed f32 operand words hold bf16 hi | bf16 lo << 16 (common.h: x3_word)
-template <int N> __device__ __forceinline__ void x3_words_of(float (&v)[N]) {
-#pragma unroll
-    for (int e = 0; e < N; ++e) v[e] = __uint_as_float(x3_word(v[e]));
-}
 
 // ------------------------------------------------------------------------- //
 // weight packing: fp32 master (Keras HWIO = [tap][ci][co]) -> MFMA operands
 // ------------------------------------------------------------------------- //
-__device__ __forceinline__ void tile_put(float* row, const float4& v) { row[0] = v.x; row[1] = v.y; row[2] = v.z; row[3] = v.w; }
-
-// 64 x 64 fp32 tile [ci][co] -> forward operand [co][ci] of its tap: the tile's columns, 16-byte stores along ci
-template <typename T, bool X3>
-__device__ __forceinline__ void tile_store_fwd(const float (*tile)[65], T* dst, int Cin, int Cout, int ci0, int co0) {
-    constexpr int N = Vec<T>::N, GPR = 64 / N, RPP = 256 / GPR;   // 16-byte groups per row, rows per pass
-#pragma unroll
-    for (int pass = 0; pass < 64 / RPP; ++pass) {
-        const int col = threadIdx.x / GPR + pass * RPP, cil = (threadIdx.x % GPR) * N;
-        const int co = co0 + col, ci = ci0 + cil;
-        if (ci < Cin && co < Cout) {                              // Cin % 8 == 0: the whole vector is in range
-            float v[N];
-#pragma unroll
-            for (int e = 0; e < N; ++e) v[e] = tile[cil + e][col];
-            if (X3) x3_words_of<N>(v);
-            Vec<T>::store(dst + (long)co * Cin + ci, v);
-        }
-    }
-}
-// ... -> data-gradient operand [ci][co] of its (rotated) tap: the tile's rows
-template <typename T, bool X3>
-__device__ __forceinline__ void tile_store_dgrad(const float (*tile)[65], T* dst, int Cin, int Cout, int ci0, int co0) {
-    constexpr int N = Vec<T>::N, GPR = 64 / N, RPP = 256 / GPR;
-#pragma unroll
-    for (int pass = 0; pass < 64 / RPP; ++pass) {
-        const int row = threadIdx.x / GPR + pass * RPP, col = (threadIdx.x % GPR) * N;
-        const int ci = ci0 + row, co = co0 + col;
-        if (ci < Cin && co < Cout) {
-            float v[N];
-#pragma unroll
-            for (int e = 0; e < N; ++e) v[e] = tile[row][col + e];
-            if (X3) x3_words_of<N>(v);
-            Vec<T>::store(dst + (long)ci * Cout + co, v);
-        }
-    }
-}
-
-// The up-conv's data gradient is a 3x3 stride-2 convolution whose tap tp = (dy+1)*3 + (dx+1) is the sum of the 2x2 taps
-// S(dy) x S(dx), S(-1) = {1}, S(0) = {0, 1}, S(1) = {0}. load(k, u) fetches N elements of tap k. The summation order (ky outer,
-// kx inner, from zero) is part of the results: every path that forms this operand goes through here.
-template <int N, typename Load>
-__device__ __forceinline__ void upconv_combined_tap(int tp, float (&v)[N], Load load) {
-    const int dy = tp / 3 - 1, dx = tp % 3 - 1;
-#pragma unroll
-    for (int e = 0; e < N; ++e) v[e] = 0.f;
-    for (int ky = 0; ky < 2; ++ky) {
-        if ((dy == -1 && ky != 1) || (dy == 1 && ky != 0)) continue;
-        for (int kx = 0; kx < 2; ++kx) {
-            if ((dx == -1 && kx != 1) || (dx == 1 && kx != 0)) continue;
-            float u[N];
-            load(ky * 2 + kx, u);
-#pragma unroll
-            for (int e = 0; e < N; ++e) v[e] += u[e];
-        }
-    }
-}
-
-// [4 taps][R ci][32 co] fp32 tile of an up-conv kernel -> forward copy [tap][co][ci] and data-gradient copy [tap'][ci][co]
-template <typename T, bool X3, int R>
-__device__ __forceinline__ void upconv_tile_store(const float (*tile)[R][33], T* wf, T* wd, int Cin, int Cout, int ci0, int co0) {
-    constexpr int N = Vec<T>::N, GI = R / N, GO = 32 / N;        // 16-byte groups along ci / along co
-    const long per_tap = (long)Cin * Cout;
-    for (int idx = threadIdx.x; idx < 4 * 32 * GI; idx += 256) {
-        const int tp = idx / (32 * GI), rem = idx % (32 * GI);
-        const int col = rem / GI, cil = (rem % GI) * N;
-        const int co = co0 + col, ci = ci0 + cil;
-        if (ci < Cin && co < Cout) {
-            float v[N];
-#pragma unroll
-            for (int e = 0; e < N; ++e) v[e] = tile[tp][cil + e][col];
-            if (X3) x3_words_of<N>(v);
-            Vec<T>::store(wf + tp * per_tap + (long)co * Cin + ci, v);
-        }
-    }
-    for (int idx = threadIdx.x; idx < 9 * R * GO; idx += 256) {
-        const int tp = idx / (R * GO), rem = idx % (R * GO);
-        const int row = rem / GO, col = (rem % GO) * N;
-        const int ci = ci0 + row, co = co0 + col;
-        if (ci < Cin && co < Cout) {
-            float v[N];
-            upconv_combined_tap<N>(tp, v, [&](int k, float (&u)[N]) {
-#pragma unroll
-                for (int e = 0; e < N; ++e) u[e] = tile[k][row][col + e];
-            });
-            if (X3) x3_words_of<N>(v);
-            Vec<T>::store(wd + tp * per_tap + (long)ci * Cout + co, v);
-        }
-    }
-}
-
 // forward operand of one layer, unit t = one (tap, 64 ci, 64 co) tile: 16-byte reads along co, transpose through LDS
 template <typename T>
 __device__ __forceinline__ void pack_fwd_tile(const float* __restrict__ W, T* wf, int Cin, int Cout, int t, float (*tile)[65]) {
@@ -242,27 +124,11 @@ int launch_x3_words(void* buf, long n, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------- //
-// Adam
+// plain Adam, decay == 0 (every other configuration: optimizer_rules.hip)
 // ------------------------------------------------------------------------- //
-// TF ApplyAdam: m += (g-m)(1-b1); v += (g*g-v)(1-b2); p -= m*alpha/(sqrt(v)+eps)
-// (one definition for the plain and the fused kernels: the same instruction sequence, bit-identical results)
-// No FMA contraction inside (pragma): the compiler contracted the multiply-adds in one kernel and not in the other, and
-// the fused and the plain path differed by one ulp in 1.4 % of the first moments (HIP's __fadd_rn & co. are plain
-// operators and contract just the same).
-__device__ __forceinline__ void adam_update(float gg, float& m, float& v, float& p, float alpha, float b1, float b2, float eps) {
-#pragma clang fp contract(off)
-    const float d1 = gg - m, o1 = 1.f - b1;
-    const float mm = m + d1 * o1;
-    const float g2 = gg * gg;
-    const float d2 = g2 - v, o2 = 1.f - b2;
-    const float vv = v + d2 * o2;
-    m = mm; v = vv;
-    const float num = mm * alpha, den = sqrtf(vv) + eps;
-    p = p - num / den;
-}
-// step size of step t (1-based), on the host and from a device-resident counter (graph replay: a captured launch cannot take a
-// new host-computed step size on every replay). step_bias: 1 = the counter holds t - 1 (the caller increments it after the
-// update), 0 = it already holds t
+// Plain Adam's step size of step t (1-based), on the host and from a device-resident counter (graph replay: a captured launch
+// cannot take a new host-computed step size on every replay). step_bias: 1 = the counter holds t - 1 (the caller increments it
+// after the update), 0 = it already holds t
 static inline float adam_alpha_host(long long t, double lr, double b1, double b2) {
     return (float)(lr * std::sqrt(1.0 - std::pow(b2, (double)t)) / (1.0 - std::pow(b1, (double)t)));
 }
@@ -270,135 +136,28 @@ __device__ __forceinline__ float adam_alpha_dev(const long long* step, double lr
     const double t = (double)(*step + step_bias);
     return (float)(lr * sqrt(1.0 - pow(b2d, t)) / (1.0 - pow(b1d, t)));
 }
-
-// the flat buffers and the step's constants, as every unit below takes them
-struct AdamArgs { float* p; const float* g; float* m; float* v; float alpha, b1, b2, eps; };
-__device__ __forceinline__ AdamArgs adam_args(float* p, const float* g, float* m, float* v, const long long* step, double lr,
-                                              double b1d, double b2d, float alpha_host, float eps, int step_bias) {
-    return {p, g, m, v, step ? adam_alpha_dev(step, lr, b1d, b2d, step_bias) : alpha_host, (float)b1d, (float)b2d, eps};
+// the flat buffers and the step's constants, as every unit takes them
+__device__ __forceinline__ OptArgs adam_args(float* p, const float* g, float* m, float* v, const long long* step, double lr,
+                                             double b1d, double b2d, float alpha_host, float eps, int step_bias) {
+    return {p, g, {m, v, nullptr}, {step ? adam_alpha_dev(step, lr, b1d, b2d, step_bias) : alpha_host, (float)b1d, (float)b2d, eps}};
 }
-
-// One float4 of g, m, v, p at a clamped offset. load() only issues the loads -- how many of these a thread holds in flight is
-// its caller's schedule; finish() updates, stores m, v, p when the float4 is in range (a clamped duplicate would be updated
-// twice) and hands the new p on (zeros outside).
-struct Adam4 {
-    float4 g, m, v, p; long off; bool in;
-    __device__ __forceinline__ void load(const AdamArgs& a, long o, bool inside) {
-        off = o; in = inside;
-        g = *reinterpret_cast<const float4*>(a.g + o); m = *reinterpret_cast<const float4*>(a.m + o);
-        v = *reinterpret_cast<const float4*>(a.v + o); p = *reinterpret_cast<const float4*>(a.p + o);
-    }
-    __device__ __forceinline__ float4 finish(const AdamArgs& a) {
-        adam_update(g.x, m.x, v.x, p.x, a.alpha, a.b1, a.b2, a.eps); adam_update(g.y, m.y, v.y, p.y, a.alpha, a.b1, a.b2, a.eps);
-        adam_update(g.z, m.z, v.z, p.z, a.alpha, a.b1, a.b2, a.eps); adam_update(g.w, m.w, v.w, p.w, a.alpha, a.b1, a.b2, a.eps);
-        if (in) {
-            *reinterpret_cast<float4*>(a.m + off) = m; *reinterpret_cast<float4*>(a.v + off) = v;
-            *reinterpret_cast<float4*>(a.p + off) = p;
-        }
-        return in ? p : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-};
-
-// plain unit: 1024 floats of [off, off + n) -- everything that is not a 3x3 / 2x2 kernel (biases, BatchNorm gamma / beta, the
-// 1x1 head): Adam only, float4 body, scalar tail and unaligned ranges
-__device__ __forceinline__ void adam_plain_unit(const AdamArgs& a, long off, long n, int unit) {
-    const long e = (long)unit * 1024 + threadIdx.x * 4;
-    if (e >= n) return;
-    const long o = off + e;
-    if (e + 4 <= n && (o & 3) == 0) {
-        Adam4 x;
-        x.load(a, o, true);
-        x.finish(a);
-    } else {
-        for (int i = 0; i < 4 && e + i < n; ++i) {
-            float mm = a.m[o + i], vv = a.v[o + i], pp = a.p[o + i];
-            adam_update(a.g[o + i], mm, vv, pp, a.alpha, a.b1, a.b2, a.eps);
-            a.m[o + i] = mm; a.v[o + i] = vv; a.p[o + i] = pp;
-        }
-    }
-}
-
-// ---- Adam + weight packing in ONE pass (round 3) ---------------------------------------------------------------
-// The separate chain read the gradients and wrote the parameters (adam_kernel), then read the parameters twice more
-// to write the two bf16 operand copies (pack_all_kernel). Here a unit loads g, m, v, p of one kernel tile, updates
-// them, and writes m, v, p AND both packed copies from the tile: 0.25 GB less traffic per step and one launch less.
-//   CONV3 job  : unit = (tap, 64 ci, 64 co) tile; forward copy [tap][co][ci] transposed through LDS, data-gradient
-//                copy [8 - tap][ci][co] from the same tile (16-byte stores).
-//   UPCONV2 job: unit = (32 ci, 32 co) x the four taps (the data-gradient copy is the 3x3 stride-2 combination,
-//                which needs all four updated taps of an element).
-//   plain units: adam_plain_unit, ranges in the table.
-// dtype "bf16x3" (X3): the operand words are written by the optimizer pass itself.
-struct AdamRange { long off, n; int unit_begin, _pad; };
-constexpr int ADAM_MAX_RANGES = 48;
-struct AdamPackTable { int njobs, nranges, plain_begin, _pad; PackJob job[PACK_MAX_JOBS]; AdamRange range[ADAM_MAX_RANGES]; };
-
-// the job that workgroup u runs a unit of; a plain unit is run here (-1)
-__device__ __forceinline__ int adam_pack_job_of(const AdamPackTable& tab, const AdamArgs& a, int u) {
-    if (u < tab.plain_begin) return find_unit(tab.job, tab.njobs, u);
-    const AdamRange& r = tab.range[find_unit(tab.range, tab.nranges, u)];
-    adam_plain_unit(a, r.off, r.n, u - r.unit_begin);
-    return -1;
-}
-
-template <typename T, bool X3>
-__device__ __forceinline__ void adam_pack_conv3_tile(const AdamArgs& a, long w, T* wf, T* wd, int Cin, int Cout, int t,
-                                                     float (*tile)[65]) {
-    const Tile64 c = tile64_of(t, Cin, Cout);
-    const long per_tap = (long)Cin * Cout, base = w + c.tap * per_tap;
-    const int ty = threadIdx.x >> 4, tx4 = (threadIdx.x & 15) * 4;
-    Adam4 x[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {                                // all 16 loads of the thread in flight together
-        bool in;
-        const long o = base + clamped_off(c.ci0 + ty + 16 * k, c.co0 + tx4, Cin, Cout, in);
-        x[k].load(a, o, in);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) tile_put(&tile[ty + 16 * k][tx4], x[k].finish(a));
-    __syncthreads();
-    tile_store_fwd<T, X3>(tile, wf + c.tap * per_tap, Cin, Cout, c.ci0, c.co0);
-    tile_store_dgrad<T, X3>(tile, wd + (8 - c.tap) * per_tap, Cin, Cout, c.ci0, c.co0);   // 180-degree rotated taps
-}
-
-// unit = (R ci, 32 co) x the four taps; a thread holds R / 8 taps of one float4
-template <typename T, bool X3, int R>
-__device__ __forceinline__ void adam_pack_upconv_tile(const AdamArgs& a, long w, T* wf, T* wd, int Cin, int Cout, int t, void* lds) {
-    constexpr int TPT = R / 8;
-    float (*tile)[R][33] = reinterpret_cast<float (*)[R][33]>(lds);
-    const int tco = (Cout + 31) / 32;
-    const int ci0 = (t / tco) * R, co0 = (t % tco) * 32;
-    const long per_tap = (long)Cin * Cout;
-    {
-        const int tp0 = (threadIdx.x / (R * 8)) * TPT, cil = (threadIdx.x % (R * 8)) >> 3, tx4 = (threadIdx.x & 7) * 4;
-        bool in;
-        const long o0 = w + clamped_off(ci0 + cil, co0 + tx4, Cin, Cout, in);
-        Adam4 x[TPT];
-#pragma unroll
-        for (int k = 0; k < TPT; ++k) x[k].load(a, o0 + (tp0 + k) * per_tap, in);
-#pragma unroll
-        for (int k = 0; k < TPT; ++k) tile_put(&tile[tp0 + k][cil][tx4], x[k].finish(a));
-    }
-    __syncthreads();
-    upconv_tile_store<T, X3, R>(tile, wf, wd, Cin, Cout, ci0, co0);
-}
-
+// plain Adam, decay == 0 (the default configuration; also the serial half of mpu_unet_backward_adam's tail)
 template <typename T, bool X3 = false>
 __global__ __launch_bounds__(256) void adam_pack_all_kernel(AdamPackTable tab, float* __restrict__ params,
                                                             const float* __restrict__ grads, float* __restrict__ am,
                                                             float* __restrict__ av, T* packed, const long long* __restrict__ step,
                                                             double lr, double b1d, double b2d, float alpha_host, float eps, int step_bias) {
     __shared__ float tile_raw[4 * 32 * 33];                      // >= 64 x 65: both tile views live here
-    const AdamArgs a = adam_args(params, grads, am, av, step, lr, b1d, b2d, alpha_host, eps, step_bias);
-    const int ji = adam_pack_job_of(tab, a, (int)blockIdx.x);
+    const OptArgs a = adam_args(params, grads, am, av, step, lr, b1d, b2d, alpha_host, eps, step_bias);
+    const int ji = opt_pack_job_of<AdamRule>(tab, a, (int)blockIdx.x);
     if (ji < 0) return;
     const PackJob& j = tab.job[ji];
     const int t = (int)blockIdx.x - j.unit_begin;
-    if (j.mode == UPCONV2) adam_pack_upconv_tile<T, X3, 32>(a, j.w, packed + j.wf, packed + j.wd, j.Cin, j.Cout, t, tile_raw);
-    else adam_pack_conv3_tile<T, X3>(a, j.w, packed + j.wf, packed + j.wd, j.Cin, j.Cout, t, reinterpret_cast<float (*)[65]>(tile_raw));
+    if (j.mode == UPCONV2) opt_pack_upconv_tile<AdamRule, T, X3, 32>(a, j.w, packed + j.wf, packed + j.wd, j.Cin, j.Cout, t, tile_raw);
+    else opt_pack_conv3_tile<AdamRule, T, X3>(a, j.w, packed + j.wf, packed + j.wd, j.Cin, j.Cout, t, reinterpret_cast<float (*)[65]>(tile_raw));
 }
-
 // ---- round 6: the optimizer beside the weight gradients -----------------------------------------------------------
-// adam_pack_lean_kernel (bf16 operands): the same update and the same two packed copies as adam_pack_all_kernel, but small
+// adam_pack_lean_kernel (bf16 operands, plain Adam only: its budget was tuned for two slots): the same update and the same two packed copies as adam_pack_all_kernel, but small
 // enough -- <= 64 registers, 8.5 KB of LDS -- to be CO-RESIDENT with a wgrad_taps workgroup (448 of a SIMD's 512 registers,
 // 148 of a CU's 160 KB): the grouped weight-gradient launch is bound by MFMA issue and LDS reads, this kernel by HBM, so the
 // optimizer of the parameters whose gradients are already final (the deep levels: 90 % of the bytes) runs on a second stream
@@ -408,7 +167,7 @@ __global__ __launch_bounds__(256) void adam_pack_all_kernel(AdamPackTable tab, f
 //   UPCONV2 job: unit = (16 ci, 32 co) x the four taps, fp32 in LDS (the data-gradient copy sums taps in fp32 before rounding).
 // Bit-identical to adam_pack_all_kernel (tests/test_gpu_unet.py).
 constexpr int LEAN_TP = 68;                      // bf16 tile pitch (elements): rows 8-byte aligned
-__device__ __forceinline__ void adam_pack_conv3_tile_lean(const AdamArgs& a, long w, bf16_t* wf, bf16_t* wd, int Cin, int Cout, int t,
+__device__ __forceinline__ void adam_pack_conv3_tile_lean(const OptArgs& a, long w, bf16_t* wf, bf16_t* wd, int Cin, int Cout, int t,
                                                           bf16_t (*tile)[LEAN_TP]) {
     const Tile64 c = tile64_of(t, Cin, Cout);
     const int ci0 = c.ci0, co0 = c.co0;
@@ -416,7 +175,7 @@ __device__ __forceinline__ void adam_pack_conv3_tile_lean(const AdamArgs& a, lon
     const int ty = threadIdx.x >> 4, tx4 = (threadIdx.x & 15) * 4;
 #pragma unroll 1
     for (int half = 0; half < 2; ++half) {
-        Adam4 x[2];
+        Opt4<AdamRule> x[2];
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             bool in;
@@ -459,30 +218,27 @@ __global__ __launch_bounds__(256, 8) void adam_pack_lean_kernel(AdamPackTable ta
                                                                 float* __restrict__ av, bf16_t* packed, const long long* __restrict__ step,
                                                                 double lr, double b1d, double b2d, float alpha_host, float eps, int step_bias) {
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[64 * LEAN_TP * 2];          // 8704 B >= 4 x 16 x 33 floats (8448)
-    const AdamArgs a = adam_args(params, grads, am, av, step, lr, b1d, b2d, alpha_host, eps, step_bias);
-    const int ji = adam_pack_job_of(tab, a, (int)blockIdx.x);
+    const OptArgs a = adam_args(params, grads, am, av, step, lr, b1d, b2d, alpha_host, eps, step_bias);
+    const int ji = opt_pack_job_of<AdamRule>(tab, a, (int)blockIdx.x);
     if (ji < 0) return;
     const PackJob& j = tab.job[ji];
     const int t = (int)blockIdx.x - j.unit_begin;
-    if (j.mode == UPCONV2) adam_pack_upconv_tile<bf16_t, false, 16>(a, j.w, packed + j.wf, packed + j.wd, j.Cin, j.Cout, t, lds_raw);
+    if (j.mode == UPCONV2) opt_pack_upconv_tile<AdamRule, bf16_t, false, 16>(a, j.w, packed + j.wf, packed + j.wd, j.Cin, j.Cout, t, lds_raw);
     else adam_pack_conv3_tile_lean(a, j.w, packed + j.wf, packed + j.wd, j.Cin, j.Cout, t, reinterpret_cast<bf16_t (*)[LEAN_TP]>(lds_raw));
 }
 
 __global__ void incr_step_kernel(long long* step) { *step += 1; }
+int launch_incr_step(long long* step, hipStream_t st) {
+    incr_step_kernel<<<1, 1, 0, st>>>(step);
+    return launch_ok();
+}
 
-// Adam + both packed operand copies of the parameters in the nr ascending, disjoint ranges [p_lo[k], p_hi[k]) in ONE launch.
+// The unit table of one update-and-pack launch over the parameters in the nr ascending, disjoint ranges [p_lo[k], p_hi[k]).
 // jobs: every 3x3 / 2x2 kernel of the model (mode, Cin, Cout, w, wf, wd set), ordered by offset; a job is taken when its kernel
-// lies inside a range, which must not cut one; the rest of each range are plain units. dtype MPU_F32X3: f32 storage, the
-// operand words written here. lean: the co-resident kernel (bf16 only). step == NULL: t_host is the 1-based step number;
-// else the device counter holds this step's number already (step_is_t: mpu_unet_backward_adam advances it at the start of the
-// backward pass, so that no launch of the tail has to wait for "every reader is done" before it moves) or the number before
-// it, and is advanced here, behind the update.
-int launch_adam_pack(int dtype, const PackTable& jobs, float* params, const float* grads, float* am, float* av, const long* p_lo,
-                     const long* p_hi, int nr, void* packed, long long* step, bool step_is_t, long long t_host, double lr, double b1,
-                     double b2, float eps, bool lean, hipStream_t st) {
-    AdamPackTable tab; tab.njobs = 0; tab.nranges = 0; tab._pad = 0;
-    const bool use_lean = lean && dtype == MPU_BF16;
-    int units = 0;
+// lies inside a range, which must not cut one; the rest of each range are plain units. lean: the up-conv unit of the lean kernel.
+int opt_pack_table(const PackTable& jobs, const long* p_lo, const long* p_hi, int nr, bool lean, AdamPackTable& tab, int& units) {
+    tab.njobs = 0; tab.nranges = 0; tab._pad = 0;
+    units = 0;
     long prev_w = -1;
     int job_range[PACK_MAX_JOBS];
     auto end_of = [](const PackJob& j) { return j.w + (long)(j.mode == UPCONV2 ? 4 : 9) * j.Cin * j.Cout; };
@@ -498,7 +254,7 @@ int launch_adam_pack(int dtype, const PackTable& jobs, float* params, const floa
         }
         if (in < 0) continue;
         j.unit_begin = units;
-        j.fwd_units = j.mode == UPCONV2 ? cdiv(j.Cin, use_lean ? 16 : 32) * cdiv(j.Cout, 32) : 9 * cdiv(j.Cin, 64) * cdiv(j.Cout, 64);
+        j.fwd_units = j.mode == UPCONV2 ? cdiv(j.Cin, lean ? 16 : 32) * cdiv(j.Cout, 32) : 9 * cdiv(j.Cin, 64) * cdiv(j.Cout, 64);
         units += j.fwd_units;
         job_range[tab.njobs] = in;
         tab.job[tab.njobs++] = j;
@@ -519,6 +275,21 @@ int launch_adam_pack(int dtype, const PackTable& jobs, float* params, const floa
             if (i < tab.njobs) cur = end_of(tab.job[i]);
         }
     }
+    return MPU_OK;
+}
+
+// Plain Adam (decay == 0) + both packed operand copies of the parameters in the ranges, ONE launch. dtype MPU_F32X3: f32 storage,
+// the operand words written here. lean: the co-resident kernel (bf16 only). step == NULL: t_host is the 1-based step number;
+// else the device counter holds this step's number already (step_is_t: mpu_unet_backward_adam advances it at the start of the
+// backward pass, so that no launch of the tail has to wait for "every reader is done" before it moves) or the number before
+// it, and is advanced here, behind the update.
+int launch_adam_pack(int dtype, const PackTable& jobs, float* params, const float* grads, float* am, float* av, const long* p_lo,
+                     const long* p_hi, int nr, void* packed, long long* step, bool step_is_t, long long t_host, double lr, double b1,
+                     double b2, float eps, bool lean, hipStream_t st) {
+    AdamPackTable tab;
+    const bool use_lean = lean && dtype == MPU_BF16;
+    int units = 0;
+    if (const int rc = opt_pack_table(jobs, p_lo, p_hi, nr, use_lean, tab, units)) return rc;
     if (units == 0) return MPU_OK;
     const float alpha_host = step ? 0.f : adam_alpha_host(t_host, lr, b1, b2);
     const int step_bias = step_is_t ? 0 : 1;
@@ -547,12 +318,8 @@ int launch_adam_pack(int dtype, const PackTable& jobs, float* params, const floa
 // the element-wise step (the two-pass form: Adam, then launch_pack_all); step as in launch_adam_pack with step_is_t false
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
                             const long long* __restrict__ step, double lr, double b1d, double b2d, float alpha_host, float eps) {
-    const AdamArgs a = adam_args(p, g, m, v, step, lr, b1d, b2d, alpha_host, eps, 1);
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-        float mm = m[e], vv = v[e], pp = p[e];
-        adam_update(g[e], mm, vv, pp, a.alpha, a.b1, a.b2, a.eps);
-        m[e] = mm; v[e] = vv; p[e] = pp;
-    }
+    const OptArgs a = adam_args(p, g, m, v, step, lr, b1d, b2d, alpha_host, eps, 1);
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) opt_update_one<AdamRule>(a, e);
 }
 int launch_adam(float* p, const float* g, float* m, float* v, long n, long long* step, long long t_host, double lr, double b1,
                 double b2, float eps, hipStream_t st) {

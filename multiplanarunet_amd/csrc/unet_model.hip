@@ -1162,6 +1162,43 @@ int mpu_adam_step_device_counter(float* d_params, const float* d_grads, float* d
     return launch_adam(d_params, d_grads, d_m, d_v, n, (long long*)d_step, 0, lr, beta1, beta2, (float)eps, (hipStream_t)stream);
 }
 
+int mpu_optimizer_num_slots(const mpu_optimizer_config* cfg) {
+    MPU_REQUIRE(cfg, "mpu_optimizer_num_slots: null argument");
+    return optimizer_num_slots(*cfg);
+}
+
+// the configuration is valid and the slots it has are there
+static int check_optimizer_call(const char* who, const mpu_optimizer_config* cfg, float* const d_slots[3], int64_t t, const int64_t* d_step) {
+    if (!cfg) return fail(MPU_EINVAL, "%s: null configuration", who);
+    const int ns = optimizer_num_slots(*cfg);
+    if (ns < 0) return ns;
+    for (int i = 0; i < ns; ++i)
+        if (!d_slots || !d_slots[i]) return fail(MPU_EINVAL, "%s: this configuration needs %ld slot buffers", who, (long)ns);
+    if (!d_step && t < 1) return fail(MPU_EINVAL, "%s: need a device step counter or a 1-based step number", who);
+    return MPU_OK;
+}
+
+int mpu_optimizer_step(const mpu_optimizer_config* cfg, float* d_params, const float* d_grads, float* const d_slots[3],
+                       int64_t n, int64_t t, int64_t* d_step, void* stream) {
+    MPU_REQUIRE(d_params && d_grads && n >= 0, "mpu_optimizer_step: bad argument");
+    RC(check_optimizer_call("mpu_optimizer_step", cfg, d_slots, t, d_step));
+    float* s[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < optimizer_num_slots(*cfg); ++i) s[i] = d_slots[i];
+    return launch_optimizer(*cfg, d_params, d_grads, s, n, (long long*)d_step, (long long)t, (hipStream_t)stream);
+}
+
+int mpu_unet_optimizer_pack(const mpu_unet* m, const mpu_optimizer_config* cfg, float* d_params, const float* d_grads,
+                            float* const d_slots[3], int64_t t, int64_t* d_step, void* d_packed, void* stream) {
+    MPU_REQUIRE(m && d_params && d_grads && d_packed, "mpu_unet_optimizer_pack: null argument");
+    RC(check_optimizer_call("mpu_unet_optimizer_pack", cfg, d_slots, t, d_step));
+    float* s[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < optimizer_num_slots(*cfg); ++i) s[i] = d_slots[i];
+    PackTable tab;
+    RC(pack_jobs_of(m, tab));
+    return launch_optimizer_pack(m->x3 ? MPU_F32X3 : m->cfg.dtype, tab, *cfg, d_params, d_grads, s, m->n_params, d_packed,
+                                 (long long*)d_step, (long long)t, (hipStream_t)stream);
+}
+
 // ---- op-level entry points (unit tests, integration of single layers) ------
 int mpu_conv2d_pack_weights(int32_t dtype, int32_t mode, const float* d_w, int32_t Cin, int32_t Cout,
                             void* d_w_fwd, void* d_w_dgrad, void* stream) {

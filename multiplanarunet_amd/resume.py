@@ -11,7 +11,9 @@ mpunet/utils/utils.py:113-172). Same decisions as the reference, restated withou
     reproduced as it is);
   * the learning rate is the one logged in row N of the CSV's `lr` / `LR` / `learning_rate` / `LearningRate` column.
 
-Only the weights come back (a Keras weights file carries no optimizer state): Adam restarts from zero moments, as there.
+Only the weights come back (a Keras weights file carries no optimizer state): whichever optimizer `fit.optimizer` names restarts
+from zero slots (Adam's moments, a momentum buffer, RMSprop's mean squares) and from step 0 -- so learning-rate decay and the
+bias corrections start over too -- as there.
 """
 import csv
 import glob

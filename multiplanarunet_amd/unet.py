@@ -28,6 +28,47 @@ _CUSTOM_LOSSES = {
 _CUSTOM_LOSSES["SparseExpLogDice"] = _CUSTOM_LOSSES["SparseExponentialLogarithmicLoss"]          # :270
 _GDL_WEIGHTS = {"square": _lib.MPU_GDL_SQUARE, "simple": _lib.MPU_GDL_SIMPLE, "uniform": _lib.MPU_GDL_UNIFORM}
 
+# tf.keras.optimizers (TF 2.3), as mpunet/train/utils.py:100-111 resolves `fit.optimizer`: class name -> (mpu_optimizer_kind,
+# constructor keywords with their defaults). Adam's lr and epsilon are the project YAML's (train_hparams.yaml:125-126), which
+# this class has always started from; the others take the Keras defaults.
+_OPTIMIZERS = {
+    "Adam": (_lib.MPU_OPT_ADAM, dict(lr=5e-5, beta_1=0.9, beta_2=0.999, epsilon=1e-8, amsgrad=False, decay=0.0)),
+    "SGD": (_lib.MPU_OPT_SGD, dict(lr=0.01, momentum=0.0, nesterov=False, decay=0.0)),
+    "RMSprop": (_lib.MPU_OPT_RMSPROP, dict(lr=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, decay=0.0)),
+    "Adamax": (_lib.MPU_OPT_ADAMAX, dict(lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, decay=0.0)),
+}
+_UNSUPPORTED = "supported optimizers: Adam (also amsgrad), SGD, RMSprop, Adamax, each with learning-rate decay"
+
+
+def _resolve_optimizer(optimizer, optimizer_kwargs):
+    """(class name, validated keywords) of `fit.optimizer` / `fit.optimizer_kwargs`. Unknown keywords raise TypeError as the
+    Keras constructor would; what is not built raises NotImplementedError -- nothing falls back to another optimizer."""
+    name = optimizer if isinstance(optimizer, str) else type(optimizer).__name__
+    by_lower = {k.lower(): k for k in _OPTIMIZERS}
+    if name.lower() not in by_lower:
+        raise NotImplementedError("optimizer %r is not supported (%s)" % (name, _UNSUPPORTED))
+    name = by_lower[name.lower()]
+    kw = dict(optimizer_kwargs or {})
+    kw.pop("name", None)
+    if "learning_rate" in kw:
+        lr = kw.pop("learning_rate")
+        kw.setdefault("lr", lr)
+    for k in ("clipnorm", "clipvalue"):
+        if kw.get(k) is not None:
+            raise NotImplementedError("gradient clipping (%s) is not supported (%s)" % (k, _UNSUPPORTED))
+        kw.pop(k, None)
+    defaults = _OPTIMIZERS[name][1]
+    for k in kw:
+        if k not in defaults:
+            raise TypeError("%s() got an unexpected keyword argument %r" % (name, k))
+    for k in ("amsgrad", "nesterov", "centered"):
+        if k in kw:
+            kw[k] = bool(kw[k])
+    for k, v in kw.items():
+        if not isinstance(v, bool):
+            kw[k] = float(v)
+    return name, kw
+
 
 class _ScreenLogger:
     def __call__(self, *args, **kwargs):
@@ -139,10 +180,11 @@ class UNet:
         self.grads = torch.zeros(n_par, dtype=torch.float32, device=dev)
         self.bn_state = torch.zeros(n_st, dtype=torch.float32, device=dev)
         self.packed = torch.zeros(lib.mpu_unet_packed_bytes(self._h), dtype=torch.uint8, device=dev)
-        self._adam_m = self._adam_v = None
+        self._slots = None             # the optimizer's slot buffers (Adam: m, v[, vhat]), allocated at the first step
         self._ws = None
         self._ws_batch = 0
-        self.optimizer_kwargs = dict(lr=5e-5, beta_1=0.9, beta_2=0.999, epsilon=1e-8)
+        self.optimizer_name = "Adam"
+        self.optimizer_kwargs = dict(_OPTIMIZERS["Adam"][1])
         self.iterations = 0
         self._l2_ws = None
         self.reg_loss = None
@@ -452,10 +494,19 @@ class UNet:
         SparseJaccardDistanceLoss, SparseGeneralizedDiceLoss, SparseFocalLoss, SparseExponentialLogarithmicLoss
         (alias SparseExpLogDice) -- with `loss_kwargs` as their constructors take them (trainer.py:82). Those five give ONE
         loss value per image (reduction=NONE over the flattened output): forward_backward / train_step return [B, 1].
+
+        `optimizer`: Adam, SGD, RMSprop or Adamax by their tf.keras.optimizers names, `optimizer_kwargs` as their constructors
+        take them (an unknown key: TypeError; anything else Keras has: NotImplementedError). A key that is omitted takes the
+        Keras default when the optimizer's NAME changes (Adam: this project's lr 5e-5, epsilon 1e-8) and slots and step count
+        start from zero. Compiling the SAME name again UPDATES the stored kwargs and keeps the state, as it always did for
+        Adam's lr: compile("SGD", momentum 0.9) then compile("SGD") still has momentum 0.9, and amsgrad / nesterov / centered /
+        decay stay set until they are given again. Pass every key, or compile another name in between, for a fresh start.
         """
-        name = optimizer if isinstance(optimizer, str) else type(optimizer).__name__
-        if name.lower() != "adam":
-            raise NotImplementedError("only the Adam optimizer is supported")
+        opt_name, opt_kw = _resolve_optimizer(optimizer, optimizer_kwargs)     # (both raise before anything is changed)
+        same = opt_name == self.optimizer_name  # another optimizer starts from its own defaults
+        new_kw = dict(self.optimizer_kwargs if same else _OPTIMIZERS[opt_name][1])
+        new_kw.update(opt_kw)
+        n_slots = self._optimizer_config(opt_name, new_kw)[1]
         if loss is not None:
             lname = loss if isinstance(loss, str) else getattr(loss, "__name__", type(loss).__name__)
             if isinstance(loss, (list, tuple)):
@@ -469,15 +520,40 @@ class UNet:
             else:
                 raise NotImplementedError("loss %r is not supported: SparseCategoricalCrossentropy or one of %s"
                                           % (lname, ", ".join(sorted(_CUSTOM_LOSSES))))
-        if optimizer_kwargs:
-            kw = dict(optimizer_kwargs)
-            if "learning_rate" in kw:
-                kw["lr"] = kw.pop("learning_rate")
-            if kw.get("decay"):
-                raise NotImplementedError("Adam decay != 0 is not supported")
-            kw.pop("decay", None)
-            self.optimizer_kwargs.update(kw)
+        if not same or (self._slots is not None and len(self._slots) != n_slots):
+            self._slots = None                  # no state of the previous optimizer (or of another variant: other slots)
+            self.iterations = 0
+        self.optimizer_name, self.optimizer_kwargs = opt_name, new_kw
         return self
+
+    def optimizer_description(self):
+        """The line Trainer.compile_model logs (trainer.py:98, "Optimizer:   %s")."""
+        return "%s(%s)" % (self.optimizer_name, ", ".join("%s=%r" % kv for kv in self.optimizer_kwargs.items()))
+
+    def _plain_adam(self):
+        """The default configuration -- Adam without decay and AMSGrad -- keeps its own entry points (mpu_unet_backward_adam: the
+        optimizer beside the weight gradients); every other one runs the backward pass, then ONE update-and-pack launch."""
+        k = self.optimizer_kwargs
+        return self.optimizer_name == "Adam" and not k.get("decay") and not k.get("amsgrad")
+
+    def _optimizer_config(self, name=None, k=None):
+        """(mpu_optimizer_config of the compiled optimizer, its number of slot buffers); the library validates the values
+        (mpu_optimizer_num_slots: what the Keras constructors refuse)."""
+        name, k = name or self.optimizer_name, self.optimizer_kwargs if k is None else k
+        cfg = _lib.OptimizerConfig()
+        cfg.kind = _OPTIMIZERS[name][0]
+        cfg.flags = (_lib.MPU_OPT_NESTEROV if k.get("nesterov") else 0) | (_lib.MPU_OPT_AMSGRAD if k.get("amsgrad") else 0) \
+            | (_lib.MPU_OPT_CENTERED if k.get("centered") else 0)
+        cfg.lr, cfg.decay = float(k["lr"]), float(k.get("decay", 0.0))
+        cfg.beta1, cfg.beta2 = float(k.get("beta_1", 0.9)), float(k.get("beta_2", 0.999))
+        cfg.epsilon, cfg.momentum, cfg.rho = float(k.get("epsilon", 1e-7)), float(k.get("momentum", 0.0)), float(k.get("rho", 0.9))
+        n = _lib.load().mpu_optimizer_num_slots(C.byref(cfg))
+        if n < 0:
+            raise ValueError("%s: %s" % (name, (_lib.load().mpu_last_error() or b"").decode()))
+        return cfg, n
+
+    def _slot_ptrs(self):
+        return (C.c_void_p * 3)(*[s.data_ptr() for s in self._slots] + [None] * (3 - len(self._slots)))
 
     def _set_loss(self, lname, kw):
         """Validate `kw` against the constructor of loss_functions.<lname> and attach the loss to the library handle
@@ -525,10 +601,19 @@ class UNet:
         self._ws = None                    # the workspace plan of a handle with a per-image loss is larger
         self._ws_batch = 0
 
-    def _ensure_adam(self):
-        if self._adam_m is None:
-            self._adam_m = torch.zeros_like(self.params)
-            self._adam_v = torch.zeros_like(self.params)
+    def _ensure_slots(self):
+        if self._slots is None:
+            self._slots = [torch.zeros_like(self.params) for _ in range(self._optimizer_config()[1])]
+
+    _ensure_adam = _ensure_slots
+
+    @property
+    def _adam_m(self):
+        return self._slots[0] if self._slots and self.optimizer_name == "Adam" else None
+
+    @property
+    def _adam_v(self):
+        return self._slots[1] if self._slots and self.optimizer_name == "Adam" else None
 
     def grad_ready_points(self):
         """Float offsets (descending) of the backward pass's gradient-ready points: after point k every gradient at
@@ -606,12 +691,23 @@ class UNet:
                   _lib.stream_ptr())
 
     def apply_gradients(self, fused=True):
-        """Keras Adam on the flat parameter buffer + refresh of the packed MFMA operands: one launch
-        (mpu_unet_adam_pack); fused=False runs the two separate passes (mpu_adam_step, mpu_unet_pack_weights;
-        bit-identical, kept for the equality test)."""
-        self._ensure_adam()
+        """The compiled optimizer on the flat parameter buffer + refresh of the packed MFMA operands: one launch
+        (mpu_unet_adam_pack; mpu_unet_optimizer_pack for anything but plain Adam); fused=False runs the two separate passes
+        (mpu_adam_step / mpu_optimizer_step, mpu_unet_pack_weights; bit-identical, kept for the equality test)."""
+        self._ensure_slots()
         self.iterations += 1
         k = self.optimizer_kwargs
+        if not self._plain_adam():
+            cfg = self._optimizer_config()[0]
+            if fused:
+                _lib.call("mpu_unet_optimizer_pack", self._h, C.byref(cfg), _lib.ptr(self.params), _lib.ptr(self.grads),
+                          self._slot_ptrs(), self.iterations, None, _lib.ptr(self.packed), _lib.stream_ptr())
+                self._infer_dirty = True
+                return
+            _lib.call("mpu_optimizer_step", C.byref(cfg), _lib.ptr(self.params), _lib.ptr(self.grads), self._slot_ptrs(),
+                      self.params.numel(), self.iterations, None, _lib.stream_ptr())
+            self._repack()
+            return
         if fused:
             _lib.call("mpu_unet_adam_pack", self._h, _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self._adam_m),
                       _lib.ptr(self._adam_v), self.iterations, None, float(k["lr"]), float(k["beta_1"]),
@@ -638,7 +734,7 @@ class UNet:
         for t in (x, y):
             if not torch.is_tensor(t) or t.device.type != "cuda":
                 raise ValueError("graphed train step needs device tensors")
-        self._ensure_adam()
+        self._ensure_slots()
         if not warmup and (self._ws is None or (self.l2_reg and self._l2_ws is None)):
             #  a capture without a warm-up step is a RE-capture: the lazily created buffers must exist already, or
             # their allocations would land in the graph's private pool
@@ -646,7 +742,10 @@ class UNet:
         step_dev = torch.tensor([self.iterations], dtype=torch.int64, device=self.device)
         k = self.optimizer_kwargs
 
-        fused_tail = not self.l2_reg and os.environ.get("MPU_FUSED_ADAM") != "0"
+        plain_adam = self._plain_adam()
+        fused_tail = plain_adam and not self.l2_reg and os.environ.get("MPU_FUSED_ADAM") != "0"
+        cfg = None if plain_adam else self._optimizer_config()[0]      # (lr is captured by value: a new rate needs a re-capture)
+        slot_ptrs = None if plain_adam else self._slot_ptrs()
 
         def body():
             if fused_tail:               # backward + optimizer in one call: the optimizer beside the weight gradients
@@ -660,6 +759,11 @@ class UNet:
                 loss_sum.add_(self.loss_mean().double())
                 if self.l2_reg:
                     loss_sum.add_(self.reg_loss.double())
+            if not plain_adam:           # the serial tail: ONE update-and-pack launch behind the backward pass
+                _lib.call("mpu_unet_optimizer_pack", self._h, C.byref(cfg), _lib.ptr(self.params), _lib.ptr(self.grads),
+                          slot_ptrs, 0, _lib.ptr(step_dev), _lib.ptr(self.packed), _lib.stream_ptr())
+                self._infer_dirty = True
+                return
             if os.environ.get("MPU_FUSED_ADAM") == "0":         # A/B: the two separate passes
                 _lib.call("mpu_adam_step_device_counter", _lib.ptr(self.params), _lib.ptr(self.grads),
                           _lib.ptr(self._adam_m), _lib.ptr(self._adam_v), self.params.numel(), _lib.ptr(step_dev),
@@ -697,14 +801,14 @@ class UNet:
         # (The model's own buffers too: a later, larger eager batch REPLACES self._ws -- the graph keeps running on the one it
         # was captured with, which must therefore stay allocated.)
         replay.keep_alive = (step_dev, x, y, sample_weight, loss_sum, self._ws, self._l2_ws, getattr(self, "reg_loss", None),
-                             self._adam_m, self._adam_v, self.params, self.grads, self.packed, self.bn_state)
+                             tuple(self._slots), self.params, self.grads, self.packed, self.bn_state)
         return replay
 
     def train_step(self, x, y, sample_weight=None, want_loss=True):
         """One Model.fit inner step. Returns the per-pixel loss [B,H*W] (device) or None."""
         hook = self._grad_hook
-        if hook is None and not self.l2_reg:     # single GPU, no l2 term: backward + optimizer as one library call
-            self._ensure_adam()
+        if hook is None and not self.l2_reg and self._plain_adam():     # single GPU, no l2 term: backward + optimizer as one library call
+            self._ensure_slots()
             self.iterations += 1
             _, loss = self.forward_backward(x, y, sample_weight, want_loss, adam=(self.iterations, None))
             return loss
