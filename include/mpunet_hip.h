@@ -93,6 +93,58 @@ int mpu_sample_view_planes(const float* d_vol, const uint8_t* d_labels,
                            const double* d_center, const double* d_scale,
                            float* d_out, uint8_t* d_out_lab, void* stream);
 
+/* MultiChannelScaler.transform (mpunet/preprocessing/scaling.py:75-89) of a sampled value v, per channel c, for the five
+ * sklearn classes the reference's YAML documents (bin/defaults/MultiPlanar/train_hparams.yaml:132-136). Every step is an
+ * f64 operation followed by an f32 store, as sklearn's in-place operations on an f32 plane with f64 parameters are:
+ *   MPU_SCALER_NONE      identity
+ *   MPU_SCALER_SUB_DIV   RobustScaler, StandardScaler   v = f32(v - p0[c]); v = f32(v / p1[c])      (p0 center_/mean_, p1 scale_)
+ *   MPU_SCALER_MUL_ADD   MinMaxScaler (0,1), no clip    v = f32(v * p0[c]); v = f32(v + p1[c])      (p0 scale_, p1 min_)
+ *   MPU_SCALER_DIV       MaxAbsScaler                   v = f32(v / p0[c])                          (p0 scale_)
+ *   MPU_SCALER_QUANTILE  QuantileTransformer (uniform)  v = f32(0.5 * (interp(v, q, r) - interp(-v, -q[::-1], -r[::-1]))) for
+ *                        every non-NaN v, np.interp's rule; then v == q[-1] -> 1 and v == q[0] -> 0 (_transform_col).
+ *                        q = quantiles[c], r = references; the tables of all channels are staged in LDS:
+ *                        (n_channels + 1) * n_quantiles * 8 bytes <= 64 KiB, else MPU_EUNSUPPORTED. */
+typedef enum { MPU_SCALER_NONE = 0, MPU_SCALER_SUB_DIV = 1, MPU_SCALER_MUL_ADD = 2, MPU_SCALER_DIV = 3,
+               MPU_SCALER_QUANTILE = 4 } mpu_scaler_kind;
+typedef struct {
+    int32_t       kind;          /* mpu_scaler_kind                               */
+    int32_t       n_quantiles;   /* QUANTILE only                                 */
+    const double* p0;            /* device f64 [C]                                */
+    const double* p1;            /* device f64 [C] (unused by DIV, QUANTILE)      */
+    const double* quantiles;     /* device f64 [C][n_quantiles] or NULL           */
+    const double* references;    /* device f64 [n_quantiles] or NULL              */
+} mpu_scaler;
+
+/* mpu_sample_view_planes with a scaler descriptor (NULL = identity) in place of d_center, d_scale. The call above is this
+ * one with kind MPU_SCALER_SUB_DIV. */
+int mpu_sample_view_planes_sc(const float* d_vol, const uint8_t* d_labels,
+                              const int32_t vol_shape[4],
+                              const double* d_ax, const double* d_ay, const double* d_az,
+                              const mpu_view_geom* geom, const double* d_offsets,
+                              const float* d_bg, uint8_t bg_class, const mpu_scaler* scaler,
+                              float* d_out, uint8_t* d_out_lab, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * Volume statistics: what the per-channel scaler fits and the '<N>pct' background value need, computed on the resident
+ * volume (the reference runs np.percentile / sklearn fits on the host: image_pair.py:300-341,469-484, scaling.py:47-73).
+ * d_vol f32 [n_vox, n_channels], 16-byte aligned; n_vox < 2^31. Both calls below SYNCHRONISE the stream: they return
+ * host values. The workspace (16-byte aligned, mpu_volume_stats_workspace_bytes) is the caller's.
+ * ------------------------------------------------------------------------ */
+int64_t mpu_volume_stats_workspace_bytes(int32_t n_channels);
+
+/* Exact order statistics of one channel: values[i] = np.sort(x[~isnan(x)])[ranks[i]] for up to 16 zero-based ranks (host
+ * i64; a rank outside [0, n_vox - nan_count) gives NaN), and the channel's NaN count. -0.0 and +0.0 are one value (+0.0 is
+ * returned). Three-pass radix select: three reads of the volume, integer counters only -- the same bits on every run. */
+int mpu_volume_order_stats(const float* d_vol, int64_t n_vox, int32_t n_channels, int32_t channel,
+                           const int64_t* ranks, int32_t n_ranks, void* d_workspace, int64_t workspace_bytes,
+                           float* values, int64_t* nan_count, void* stream);
+
+/* Per channel c, out[c*8 + k], fp64, NaNs ignored. mean == NULL: k = 0..4 = count, min, max, max|x|, sum(x). mean = host f64
+ * [n_channels]: k = 5, 6 = sum(x - mean[c]), sum((x - mean[c])^2) -- the two-pass form of sklearn's _incremental_mean_and_var
+ * on a first batch. The entries of the pass not run are left alone. Fixed-order two-stage sums: bit-identical run to run. */
+int mpu_volume_moments(const float* d_vol, int64_t n_vox, int32_t n_channels, const double* mean,
+                       void* d_workspace, int64_t workspace_bytes, double* out, void* stream);
+
 /* One view's prediction volume as seen by the back-mapping
  * (mpunet/utils/fusion/fuse_and_predict.py:92-137). */
 typedef struct {
@@ -286,6 +338,12 @@ int mpu_sample_plane_stats(const float* d_vol, const uint8_t* d_labels, const in
                            const mpu_view_geom* geom, const double* d_offset,
                            const float* d_bg, uint8_t bg_class, const double* d_center, const double* d_scale,
                            float* d_out, uint8_t* d_out_lab, const float* d_bg_scaled, uint32_t* d_stats2, void* stream);
+/* The same with a scaler descriptor (mpu_sample_view_planes_sc). */
+int mpu_sample_plane_stats_sc(const float* d_vol, const uint8_t* d_labels, const int32_t vol_shape[4],
+                              const double* d_ax, const double* d_ay, const double* d_az,
+                              const mpu_view_geom* geom, const double* d_offset,
+                              const float* d_bg, uint8_t bg_class, const mpu_scaler* scaler,
+                              float* d_out, uint8_t* d_out_lab, const float* d_bg_scaled, uint32_t* d_stats2, void* stream);
 
 /* Elastic2D augmentation of one training slice (mpunet/augmentation/elastic_deformation.py:6-69, applied by
  * mpunet/augmentation/augmenters.py:87-107 after scaling): image [H][W][C] f32 bilinear with fill d_bg[c],

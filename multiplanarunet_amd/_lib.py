@@ -91,6 +91,14 @@ class OptimizerConfig(C.Structure):    # mpu_optimizer_config
                 ("epsilon", f64), ("momentum", f64), ("rho", f64)]
 
 
+# mpu_scaler_kind
+MPU_SCALER_NONE, MPU_SCALER_SUB_DIV, MPU_SCALER_MUL_ADD, MPU_SCALER_DIV, MPU_SCALER_QUANTILE = range(5)
+
+
+class ScalerDesc(C.Structure):         # mpu_scaler
+    _fields_ = [("kind", i32), ("n_quantiles", i32), ("p0", c_p), ("p1", c_p), ("quantiles", c_p), ("references", c_p)]
+
+
 class MpuError(RuntimeError):
     pass
 
@@ -173,6 +181,13 @@ _SIGS = {
     "mpu_debug_tail_events": (C.c_int, [i32, c_p]),
     "mpu_sample_plane_stats": (C.c_int, [c_p, c_p, C.POINTER(i32), c_p, c_p, c_p, C.POINTER(ViewGeom), c_p, c_p, u8, c_p, c_p,
                                         c_p, c_p, c_p, c_p, c_p]),
+    "mpu_sample_view_planes_sc": (C.c_int, [c_p, c_p, C.POINTER(i32), c_p, c_p, c_p, C.POINTER(ViewGeom), c_p, c_p, u8,
+                                           C.POINTER(ScalerDesc), c_p, c_p, c_p]),
+    "mpu_sample_plane_stats_sc": (C.c_int, [c_p, c_p, C.POINTER(i32), c_p, c_p, c_p, C.POINTER(ViewGeom), c_p, c_p, u8,
+                                           C.POINTER(ScalerDesc), c_p, c_p, c_p, c_p, c_p]),
+    "mpu_volume_stats_workspace_bytes": (i64, [i32]),
+    "mpu_volume_order_stats": (C.c_int, [c_p, i64, i32, i32, C.POINTER(i64), i32, c_p, i64, C.POINTER(f32), C.POINTER(i64), c_p]),
+    "mpu_volume_moments": (C.c_int, [c_p, i64, i32, C.POINTER(f64), c_p, i64, C.POINTER(f64), c_p]),
     "mpu_unet_backward_adam": (C.c_int, [c_p, i32] + [c_p] * 10 + [i64, c_p, f64, f64, f64, f64, c_p]),
     "mpu_optimizer_num_slots": (C.c_int, [C.POINTER(OptimizerConfig)]),
     "mpu_optimizer_step": (C.c_int, [C.POINTER(OptimizerConfig), c_p, c_p, C.POINTER(c_p), i64, i64, c_p, c_p]),

@@ -124,12 +124,88 @@ struct SampleArgs {
     Mat3 basis, rot; int has_rot;
     int dim, P; double g_start, g_step;
     const float* bg; uint8_t bg_class;
-    const double *center, *scale;
+    const double *center, *scale;          // mpu_scaler p0, p1 (NULL: identity)
     float* out; uint8_t* out_lab;
+    static constexpr bool GENSC = false;   // kinds NONE / SUB_DIV only
+};
+// the kernels' argument for the other scaler kinds (the kernels are templates over the argument type, so the instantiations
+// for NONE / SUB_DIV keep the argument block -- and the code -- they always had)
+struct SampleArgsSc : SampleArgs {
+    int sc_kind, sc_nq;                    // mpu_scaler kind, n_quantiles
+    const double *sc_q, *sc_r;             // QUANTILE: quantiles [C][nq], references [nq]
+    static constexpr bool GENSC = true;
 };
 
+// ---- MultiChannelScaler.transform on one sampled value (preprocessing/scaling.py:75-89) --------------------------------------
+// Every step is an f64 operation followed by an f32 store: what sklearn's in-place ops on an f32 plane with f64 parameters do.
+// A = SampleArgs is the instantiation of the kinds NONE / SUB_DIV (the code the kernels always had); A = SampleArgsSc adds the
+// other kinds behind a wave-uniform switch, with the QUANTILE tables staged in LDS: references [nq], then quantiles [C][nq].
+// np.interp's C rule for one non-NaN x over the knots xp, fp (MIRROR: over -xp[::-1], -fp[::-1])
+template <bool MIRROR>
+__device__ __forceinline__ double interp_np(double x, const double* xq, const double* fr, int n) {
+    auto xp = [&](int k) -> double { return MIRROR ? -xq[n - 1 - k] : xq[k]; };
+    auto fp = [&](int k) -> double { return MIRROR ? -fr[n - 1 - k] : fr[k]; };
+    if (x > xp(n - 1)) return fp(n - 1);
+    if (x < xp(0)) return fp(0);
+    int lo = 0, hi = n;                    // j = (number of knots <= x) - 1
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (x >= xp(mid)) lo = mid + 1; else hi = mid;
+    }
+    const int j = lo - 1;
+    if (j == n - 1) return fp(j);
+    if (xp(j) == x) return fp(j);
+    const double slope = (fp(j + 1) - fp(j)) / (xp(j + 1) - xp(j));
+    double r = slope * (x - xp(j)) + fp(j);
+    if (r != r) {
+        r = slope * (x - xp(j + 1)) + fp(j + 1);
+        if (r != r && fp(j) == fp(j + 1)) r = fp(j);
+    }
+    return r;
+}
+template <typename A>
+__device__ __forceinline__ float apply_scaler(const A& a, int c, float v32, const double* tab) {
+    if constexpr (!A::GENSC) {
+        if (a.center) {    // sklearn: X -= center_; X /= scale_ (f64 op, f32 store)
+            v32 = (float)((double)v32 - a.center[c]);
+            v32 = (float)((double)v32 / a.scale[c]);
+        }
+    } else if (a.sc_kind == MPU_SCALER_SUB_DIV) {
+        v32 = (float)((double)v32 - a.center[c]);
+        v32 = (float)((double)v32 / a.scale[c]);
+    } else if (a.sc_kind == MPU_SCALER_MUL_ADD) {             // MinMaxScaler: X *= scale_; X += min_
+        v32 = (float)((double)v32 * a.center[c]);
+        v32 = (float)((double)v32 + a.scale[c]);
+    } else if (a.sc_kind == MPU_SCALER_DIV) {                 // MaxAbsScaler: X /= scale_
+        v32 = (float)((double)v32 / a.center[c]);
+    } else if (a.sc_kind == MPU_SCALER_QUANTILE) {            // QuantileTransformer._transform_col, uniform output
+        const int n = a.sc_nq;
+        const double* r = tab; const double* q = tab + (long)(1 + c) * n;
+        const double x = (double)v32;
+        if (x == x) v32 = (float)(0.5 * (interp_np<false>(x, q, r, n) - interp_np<true>(-x, q, r, n)));
+        if (x == q[n - 1]) v32 = 1.f;
+        if (x == q[0]) v32 = 0.f;
+    }
+    return v32;
+}
+template <typename A>
+__device__ __forceinline__ const double* stage_scaler(const A& a) {
+    if constexpr (A::GENSC) {
+        extern __shared__ double sc_tab[];
+        if (a.sc_kind == MPU_SCALER_QUANTILE) {
+            const int n = a.sc_nq, total = n * (1 + a.C);
+            for (int k = threadIdx.x; k < total; k += blockDim.x) sc_tab[k] = k < n ? a.sc_r[k] : a.sc_q[k - n];
+        }
+        __syncthreads();
+        return sc_tab;
+    } else {
+        return nullptr;
+    }
+}
+
 // One sample of get_view_from: the exact NumPy-order evaluation (any axis kind, any channel count).
-__device__ __forceinline__ void sample_one(const SampleArgs& a, int p, int i, int j) {
+template <typename A>
+__device__ __forceinline__ void sample_one(const A& a, int p, int i, int j, const double* tab) {
     const long t = ((long)p * a.dim + i) * a.dim + j;
     const double gx = (double)i * a.g_step + a.g_start;
     const double gy = (double)j * a.g_step + a.g_start;
@@ -164,11 +240,7 @@ __device__ __forceinline__ void sample_one(const SampleArgs& a, int p, int i, in
             }
             v32 = (float)acc;
         }
-        if (a.center) {    // sklearn: X -= center_; X /= scale_ (f64 op, f32 store)
-            v32 = (float)((double)v32 - a.center[c]);
-            v32 = (float)((double)v32 / a.scale[c]);
-        }
-        o[c] = v32;
+        o[c] = apply_scaler(a, c, v32, tab);
     }
     if (a.out_lab) {
         uint8_t l = a.bg_class;
@@ -182,7 +254,9 @@ __device__ __forceinline__ void sample_one(const SampleArgs& a, int p, int i, in
     }
 }
 // Generic kernel (any axis kind / channel count): one workgroup = one 16x16 patch of one plane.
-__global__ __launch_bounds__(256) void sample_view_planes_kernel(SampleArgs a) {
+template <typename A>
+__global__ __launch_bounds__(256) void sample_view_planes_kernel(A a) {
+    const double* tab = stage_scaler(a);
     const int tpd = (a.dim + 15) / 16;
     const long nblk = (long)a.P * tpd * tpd;
     for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
@@ -190,13 +264,15 @@ __global__ __launch_bounds__(256) void sample_view_planes_kernel(SampleArgs a) {
         const int ti = (int)((blk / tpd) % tpd), tj = (int)(blk % tpd);
         const int i = ti * 16 + (threadIdx.x >> 4), j = tj * 16 + (threadIdx.x & 15);
         if (i >= a.dim || j >= a.dim) continue;
-        sample_one(a, p, i, j);
+        sample_one(a, p, i, j, tab);
     }
 }
 
 // exact recomputation of the samples on the straight-line kernel's work list (all samples if the list overflowed)
-__global__ __launch_bounds__(256) void sample_fixup_kernel(SampleArgs a, const unsigned* list, const unsigned* count, unsigned cap,
+template <typename A>
+__global__ __launch_bounds__(256) void sample_fixup_kernel(A a, const unsigned* list, const unsigned* count, unsigned cap,
                                                            unsigned* next_count) {
+    const double* tab = stage_scaler(a);
     const unsigned n = *count;
     if (blockIdx.x == 0 && threadIdx.x == 0) *next_count = 0;
     const long total = (long)a.P * a.dim * a.dim;
@@ -204,7 +280,7 @@ __global__ __launch_bounds__(256) void sample_fixup_kernel(SampleArgs a, const u
     const long m = all ? total : (long)n;
     for (long k = (long)blockIdx.x * 256 + threadIdx.x; k < m; k += (long)gridDim.x * 256) {
         const long t = all ? k : (long)list[k];
-        sample_one(a, (int)(t / ((long)a.dim * a.dim)), (int)((t / a.dim) % a.dim), (int)(t % a.dim));
+        sample_one(a, (int)(t / ((long)a.dim * a.dim)), (int)((t / a.dim) % a.dim), (int)(t % a.dim), tab);
     }
 }
 
@@ -267,9 +343,10 @@ __global__ __launch_bounds__(256) void cell_div_check_kernel(double start, doubl
     if (local) atomicAdd(bad, local);
 }
 
-template <int KIND, int C, bool LAB>
-__global__ __launch_bounds__(256) void sample_fast_kernel(SampleArgs a, unsigned* list, unsigned* count, unsigned cap) {
+template <int KIND, int C, bool LAB, typename A>
+__global__ __launch_bounds__(256) void sample_fast_kernel(A a, unsigned* list, unsigned* count, unsigned cap) {
     // one workgroup = 8 rows x 32 columns of one plane (128-byte rows of output, compact footprint in the volume)
+    const double* tab = stage_scaler(a);
     const int p = blockIdx.z;
     const int i = blockIdx.y * 8 + (threadIdx.x >> 5), j = blockIdx.x * 32 + (threadIdx.x & 31);
     if (i >= a.dim || j >= a.dim) return;
@@ -332,12 +409,8 @@ __global__ __launch_bounds__(256) void sample_fast_kernel(SampleArgs a, unsigned
         double acc = 0.0;
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc = acc + (double)cv[c][e] * w[e];
-        float v32 = oob ? a.bg[c] : (float)acc;
-        if (a.center) {    // sklearn: X -= center_; X /= scale_ (f64 op, f32 store)
-            v32 = (float)((double)v32 - a.center[c]);
-            v32 = (float)((double)v32 / a.scale[c]);
-        }
-        res[c] = v32;
+        const float v32 = oob ? a.bg[c] : (float)acc;
+        res[c] = apply_scaler(a, c, v32, tab);
     }
     if (C == 1) a.out[t] = res[0];
     else { float2 v; v.x = res[0]; v.y = res[C - 1]; __builtin_memcpy(a.out + t * 2, &v, 8); }
@@ -1188,22 +1261,37 @@ int mpu_geometry_check_cell_division(const mpu_axis* axis, int64_t count, uint64
     return MPU_OK;
 }
 
-int mpu_sample_view_planes(const float* d_vol, const uint8_t* d_labels, const int32_t vol_shape[4],
-                           const double* d_ax, const double* d_ay, const double* d_az,
-                           const mpu_view_geom* geom, const double* d_offsets,
-                           const float* d_bg, uint8_t bg_class,
-                           const double* d_center, const double* d_scale,
-                           float* d_out, uint8_t* d_out_lab, void* stream) {
+int mpu_sample_view_planes_sc(const float* d_vol, const uint8_t* d_labels, const int32_t vol_shape[4],
+                              const double* d_ax, const double* d_ay, const double* d_az,
+                              const mpu_view_geom* geom, const double* d_offsets,
+                              const float* d_bg, uint8_t bg_class, const mpu_scaler* scaler,
+                              float* d_out, uint8_t* d_out_lab, void* stream) {
     { const int rc_ = sync_fast_switch(); if (rc_) return rc_; }
     MPU_REQUIRE(d_vol && vol_shape && d_ax && d_ay && d_az && geom && d_offsets && d_bg && d_out,
                 "mpu_sample_view_planes: null argument");
     MPU_REQUIRE(vol_shape[0] >= 2 && vol_shape[1] >= 2 && vol_shape[2] >= 2 && vol_shape[3] >= 1,
                 "mpu_sample_view_planes: volume must be at least 2x2x2x1");
     MPU_REQUIRE(geom->dim >= 2 && geom->n_planes >= 1, "mpu_sample_view_planes: bad dim / n_planes");
-    MPU_REQUIRE((d_center == nullptr) == (d_scale == nullptr),
-                "mpu_sample_view_planes: center and scale must both be given or both NULL");
     MPU_REQUIRE(!d_out_lab || d_labels, "mpu_sample_view_planes: label output requested without labels");
-    SampleArgs a;
+    mpu_scaler sc;
+    memset(&sc, 0, sizeof(sc));
+    if (scaler) sc = *scaler;
+    size_t lds = 0;
+    switch (sc.kind) {
+    case MPU_SCALER_NONE: sc.p0 = sc.p1 = nullptr; break;
+    case MPU_SCALER_SUB_DIV: case MPU_SCALER_MUL_ADD:
+        MPU_REQUIRE(sc.p0 && sc.p1, "mpu_sample_view_planes: center and scale must both be given or both NULL"); break;
+    case MPU_SCALER_DIV:
+        MPU_REQUIRE(sc.p0, "mpu_sample_view_planes: the DIV scaler needs p0"); break;
+    case MPU_SCALER_QUANTILE:
+        MPU_REQUIRE(sc.quantiles && sc.references && sc.n_quantiles >= 1, "mpu_sample_view_planes: the QUANTILE scaler needs its tables");
+        lds = (size_t)sc.n_quantiles * (size_t)(1 + vol_shape[3]) * sizeof(double);
+        if (lds > 65536) return fail(MPU_EUNSUPPORTED, "%s", "mpu_sample_view_planes: quantile tables of all channels must fit 64 KiB of LDS");
+        break;
+    default: MPU_REQUIRE(false, "mpu_sample_view_planes: unknown scaler kind");
+    }
+    const bool gensc = sc.kind > MPU_SCALER_SUB_DIV;
+    SampleArgsSc a;
     a.vol = d_vol; a.labels = d_labels;
     a.X = vol_shape[0]; a.Y = vol_shape[1]; a.Z = vol_shape[2]; a.C = vol_shape[3];
     a.ax = to_axis(d_ax, a.X, geom->vol_axis[0]);
@@ -1212,8 +1300,10 @@ int mpu_sample_view_planes(const float* d_vol, const uint8_t* d_labels, const in
     a.offsets = d_offsets;
     to_mat3(geom->basis, a.basis); to_mat3(geom->rot, a.rot); a.has_rot = geom->has_rot;
     a.dim = geom->dim; a.P = geom->n_planes; a.g_start = geom->g_start; a.g_step = geom->g_step;
-    a.bg = d_bg; a.bg_class = bg_class; a.center = d_center; a.scale = d_scale;
+    a.bg = d_bg; a.bg_class = bg_class; a.center = sc.p0; a.scale = sc.p1;
+    a.sc_kind = sc.kind; a.sc_nq = sc.n_quantiles; a.sc_q = sc.quantiles; a.sc_r = sc.references;
     a.out = d_out; a.out_lab = d_out_lab;
+    const SampleArgs& a0 = a;              // (sliced: what the NONE / SUB_DIV instantiations take)
     // straight-line kernel: ImagePair voxel axes (kind 2), 1 or 2 channels, 32-bit element offsets
     // (single planes -- the train-time sampler cuts one candidate plane per call -- stay on the one-launch kernel: the
     // straight-line kernel needs a second launch for its work list)
@@ -1227,13 +1317,18 @@ int mpu_sample_view_planes(const float* d_vol, const uint8_t* d_labels, const in
         unsigned *cnt = nullptr, *nxt = nullptr, *lst = nullptr;
         { const int rc_ = fuse_scratch(st, &cnt, &nxt, &lst); if (rc_) return rc_; }
         FuseCounterGuard guard{st, lst};
+#define MPU_SAMPLE_FAST3(KIND_, C_, LAB_) \
+        if (gensc) sample_fast_kernel<KIND_, C_, LAB_, SampleArgsSc><<<g, b, lds, st>>>(a, lst, cnt, FUSE_LIST_CAP); \
+        else sample_fast_kernel<KIND_, C_, LAB_, SampleArgs><<<g, b, 0, st>>>(a0, lst, cnt, FUSE_LIST_CAP);
 #define MPU_SAMPLE_FAST(KIND_) \
-        if (a.C == 1) { if (a.out_lab) sample_fast_kernel<KIND_, 1, true><<<g, b, 0, st>>>(a, lst, cnt, FUSE_LIST_CAP); else sample_fast_kernel<KIND_, 1, false><<<g, b, 0, st>>>(a, lst, cnt, FUSE_LIST_CAP); } \
-        else          { if (a.out_lab) sample_fast_kernel<KIND_, 2, true><<<g, b, 0, st>>>(a, lst, cnt, FUSE_LIST_CAP); else sample_fast_kernel<KIND_, 2, false><<<g, b, 0, st>>>(a, lst, cnt, FUSE_LIST_CAP); }
+        if (a.C == 1) { if (a.out_lab) { MPU_SAMPLE_FAST3(KIND_, 1, true) } else { MPU_SAMPLE_FAST3(KIND_, 1, false) } } \
+        else          { if (a.out_lab) { MPU_SAMPLE_FAST3(KIND_, 2, true) } else { MPU_SAMPLE_FAST3(KIND_, 2, false) } }
         if (a.ax.kind == 1) { MPU_SAMPLE_FAST(1) } else { MPU_SAMPLE_FAST(2) }
 #undef MPU_SAMPLE_FAST
+#undef MPU_SAMPLE_FAST3
         { const int rc_ = launch_ok(); if (rc_) return rc_; }
-        sample_fixup_kernel<<<dim3(64), dim3(256), 0, st>>>(a, lst, cnt, FUSE_LIST_CAP, nxt);
+        if (gensc) sample_fixup_kernel<SampleArgsSc><<<dim3(64), dim3(256), lds, st>>>(a, lst, cnt, FUSE_LIST_CAP, nxt);
+        else sample_fixup_kernel<SampleArgs><<<dim3(64), dim3(256), 0, st>>>(a0, lst, cnt, FUSE_LIST_CAP, nxt);
         if (sched_log_on()) sched_note("sample fast kind=%d C=%d labels=%d", a.ax.kind, a.C, a.out_lab ? 1 : 0);
         const int rc_ = launch_ok();
         guard.done = rc_ == MPU_OK;
@@ -1243,8 +1338,26 @@ int mpu_sample_view_planes(const float* d_vol, const uint8_t* d_labels, const in
     const long tpd = (a.dim + 15) / 16;
     long nblk = (long)a.P * tpd * tpd;
     if (nblk > (1L << 20)) nblk = 1L << 20;
-    sample_view_planes_kernel<<<dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream>>>(a);
+    if (gensc) sample_view_planes_kernel<SampleArgsSc><<<dim3((unsigned)nblk), dim3(256), lds, (hipStream_t)stream>>>(a);
+    else sample_view_planes_kernel<SampleArgs><<<dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream>>>(a0);
     return launch_ok();
+}
+
+/* the (center, scale) form: kind SUB_DIV of the call above */
+int mpu_sample_view_planes(const float* d_vol, const uint8_t* d_labels, const int32_t vol_shape[4],
+                           const double* d_ax, const double* d_ay, const double* d_az,
+                           const mpu_view_geom* geom, const double* d_offsets,
+                           const float* d_bg, uint8_t bg_class,
+                           const double* d_center, const double* d_scale,
+                           float* d_out, uint8_t* d_out_lab, void* stream) {
+    MPU_REQUIRE((d_center == nullptr) == (d_scale == nullptr),
+                "mpu_sample_view_planes: center and scale must both be given or both NULL");
+    mpu_scaler sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.kind = d_center ? MPU_SCALER_SUB_DIV : MPU_SCALER_NONE;
+    sc.p0 = d_center; sc.p1 = d_scale;
+    return mpu_sample_view_planes_sc(d_vol, d_labels, vol_shape, d_ax, d_ay, d_az, geom, d_offsets, d_bg, bg_class, &sc,
+                                     d_out, d_out_lab, stream);
 }
 
 int mpu_map_view_nearest(const mpu_voxel_grid* grid, const mpu_view_pred* view, int32_t n_classes,

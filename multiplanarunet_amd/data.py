@@ -65,22 +65,40 @@ def make_toy_volume(size=64, seed=0):
     return img[..., None].astype(np.float32), lab, np.eye(4)
 
 
-def as_volume(image, labels, affine, bg_value="1pct", scaler="RobustScaler", device="cuda", identifier="volume"):
-    """Host prep the reference does lazily per ImagePair (image_pair.py:300-341,469-484), then upload."""
+def as_volume(image, labels, affine, bg_value="1pct", scaler="RobustScaler", device="cuda", identifier="volume",
+              fit_on="device"):
+    """The preparation the reference does lazily per ImagePair (image_pair.py:300-341,469-484): the '<N>pct' background
+    value and the per-channel scaler, one of the five sklearn classes of the reference's YAML. fit_on="device" (default):
+    upload first, then compute both from the resident image (scalers.py, csrc/volume_stats.hip); fit_on="host": NumPy on the
+    host image, then upload -- the same numbers, kept for A/B and tests. A host image of another dtype is cast to f32 first, in both modes: f32 is what the
+    device holds and what the planes are cut from."""
+    from . import scalers
+    if fit_on not in ("device", "host"):
+        raise ValueError("fit_on must be 'device' or 'host'")
+    if scaler:
+        scalers.check_scaler_name(scaler)
+    if not torch.is_tensor(image):
+        image = np.asarray(image, np.float32)                 # the volume is f32 on the device: both modes prepare from f32
     C = image.shape[-1]
+    pct = None
     if isinstance(bg_value, str) and bg_value.endswith("pct"):
         pct = int(bg_value[:-3])
-        bg = [float(np.percentile(image[..., c], pct)) for c in range(C)]
+        bg = None
     elif isinstance(bg_value, (list, tuple, np.ndarray)):
         bg = [float(b) for b in bg_value]
     else:
         bg = [float(bg_value or 0.0)] * C
-    sc = None
-    if scaler:
-        if scaler != "RobustScaler":
-            raise NotImplementedError("only scaler: RobustScaler (YAML default) or Null")
-        sc = Volume.fit_robust_scaler(image)
-    return Volume(image, labels, affine, bg_value=bg, scaler=sc, device=device, identifier=identifier)
+    if fit_on == "host":
+        if pct is not None:
+            bg = [float(np.percentile(image[..., c], pct)) for c in range(C)]
+        sc = scalers.fit_scaler_host(scaler, image) if scaler else None
+        return Volume(image, labels, affine, bg_value=bg, scaler=sc, device=device, identifier=identifier)
+    img_dev = torch.as_tensor(image).to(device=device, dtype=torch.float32).contiguous()
+    if img_dev.ndim != 4:
+        raise ValueError("Input img of dim %i must be dim 4." % img_dev.ndim)
+    bg_dev, sc = scalers.prepare_device(img_dev, pct, scaler or None)
+    return Volume(img_dev, labels, affine, bg_value=bg if pct is None else bg_dev, scaler=sc, device=device,
+                  identifier=identifier)
 
 
 def random_views(n, min_angle_deg=60.0, seed=None):
@@ -167,15 +185,13 @@ class _VolCache:
         g.dim, g.n_planes = int(dim), 1
         g.g_start, g.g_step = float(-hd), float((hd - (-hd)) / float(dim - 1))
         self.geom = g
-        bg = torch.tensor(vol.bg_value, dtype=torch.float64, device=vol.device)
-        if vol.scaler is not None:                           # planes come out scaled: compare with the scaled value
-            c, s_ = vol.scaler
-            bg = (bg - torch.tensor(np.asarray(c, np.float64), device=vol.device)) / \
-                torch.tensor(np.asarray(s_, np.float64), device=vol.device)
-        self.bg_scaled = bg.float().contiguous()
+        bg = np.asarray(vol.bg_value, np.float32)[None, :]
+        if vol._scaler is not None:                          # planes come out scaled: compare with what the kernel makes of a fill
+            bg = vol._scaler.transform_host(bg)
+        self.bg_scaled = torch.tensor(bg[0], dtype=torch.float32, device=vol.device).contiguous()
         self.bg_scaled_ptr = self.bg_scaled.data_ptr()
         self.ptrs = [_lib.ptr(vol.image), _lib.ptr(vol.labels), _lib.ptr(vol._axes_dev[0]), _lib.ptr(vol._axes_dev[1]),
-                     _lib.ptr(vol._axes_dev[2]), _lib.ptr(vol._bg), _lib.ptr(vol._center), _lib.ptr(vol._scale)]
+                     _lib.ptr(vol._axes_dev[2]), _lib.ptr(vol._bg), vol._sc]
 
 
 class TrainSampler:
@@ -230,8 +246,8 @@ class TrainSampler:
         st = _lib.stream_ptr()
         p = vc.ptrs
         xs, ys = X[slot], Y[slot]
-        _lib.call("mpu_sample_view_planes", p[0], p[1], vc.shape, p[2], p[3], p[4], C.byref(g), _lib.ptr(od),
-                  p[5], vol.bg_class, p[6], p[7], _lib.ptr(xs), _lib.ptr(ys), st)
+        _lib.call("mpu_sample_view_planes_sc", p[0], p[1], vc.shape, p[2], p[3], p[4], C.byref(g), _lib.ptr(od),
+                  p[5], vol.bg_class, p[6], _lib.ptr(xs), _lib.ptr(ys), st)
         _lib.call("mpu_plane_stats", _lib.ptr(ys), _lib.ptr(xs), self.dim * self.dim, vol.n_channels,
                   _lib.ptr(vc.bg_scaled), _lib.ptr(stats[slot]), st)
 
@@ -301,9 +317,9 @@ class TrainSampler:
                 g = vc.geom
                 g.basis[:] = basis
                 p = vc.ptrs
-                _lib.check(lib.mpu_sample_plane_stats(p[0], p[1], vc.shape, p[2], p[3], p[4], C.byref(g), op + 8 * slot, p[5],
-                                                      vol.bg_class, p[6], p[7], xp + slot * xs, yp + slot * ys, vc.bg_scaled_ptr,
-                                                      sp + 8 * slot, stp), "mpu_sample_plane_stats")
+                _lib.check(lib.mpu_sample_plane_stats_sc(p[0], p[1], vc.shape, p[2], p[3], p[4], C.byref(g), op + 8 * slot, p[5],
+                                                         vol.bg_class, p[6], xp + slot * xs, yp + slot * ys, vc.bg_scaled_ptr,
+                                                         sp + 8 * slot, stp), "mpu_sample_plane_stats_sc")
             st = stats.tolist()                               # the round's one synchronisation
             self.rounds += 1
             while first < B:                                  # judge in slot order until a candidate is rejected

@@ -120,9 +120,12 @@ class ViewGeometry:
 class Volume:
     """
     image f32 [X,Y,Z,C], labels u8 [X,Y,Z] or None, affine 4x4. `bg_value` is a
-    number per channel (the reference's '1pct' percentile is host prep, outside
-    the path); `scaler` is None or (center[C], scale[C]) of a fitted sklearn
-    scaler (image_pair.py:323-341, preprocessing/scaling.py:47-89).
+    number per channel (data.as_volume computes the reference's '1pct'
+    percentile from the resident image: scalers.bg_percentile_device);
+    `scaler` is None, a scalers.Scaler (scalers.fit_scaler: the five sklearn
+    classes of the reference's YAML) or the (center[C], scale[C]) pair of a
+    fitted RobustScaler / StandardScaler (image_pair.py:323-341,
+    preprocessing/scaling.py:47-89).
     """
 
     def __init__(self, image, labels=None, affine=None, bg_value=0.0, scaler=None,
@@ -145,12 +148,13 @@ class Volume:
         self.identifier = identifier
         self.device = self.image.device
         self._bg = torch.tensor(self.bg_value, dtype=torch.float32, device=self.device)
-        self._center = self._scale = None
-        self.scaler = scaler
-        if scaler is not None:
-            c, s = scaler
-            self._center = torch.tensor(np.asarray(c, np.float64), device=self.device)
-            self._scale = torch.tensor(np.asarray(s, np.float64), device=self.device)
+        from .scalers import as_scaler
+        self.scaler = scaler                                   # as given: a (center, scale) pair stays one
+        self._scaler = as_scaler(scaler)
+        if self._scaler is not None and self._scaler.n_channels != C_:
+            raise ValueError("scaler fitted on %d channels, image has %d" % (self._scaler.n_channels, C_))
+        # mpu_scaler with device pointers (NULL: identity)
+        self._sc = None if self._scaler is None else C.pointer(self._scaler.device_struct(self.device))
         # voxel axes centred in real space + rot_mat (sample_grid.py:63-98)
         basis = self.affine[:3, :3]
         pixdims = np.linalg.norm(basis, axis=0)
@@ -214,12 +218,12 @@ def sample_view(volume, geom, want_labels=True, out=None):
     offs = geom.device_axes(dev)[1] if hasattr(geom, "device_axes") else torch.tensor(geom.offsets, device=dev)
     shape = (C.c_int32 * 4)(*[int(v) for v in volume.image.shape])
     gs = geom.struct(volume.rot_mat, volume.axes)
-    _lib.call("mpu_sample_view_planes", _lib.ptr(volume.image),
+    _lib.call("mpu_sample_view_planes_sc", _lib.ptr(volume.image),
               _lib.ptr(volume.labels if y is not None else None), shape,
               _lib.ptr(volume._axes_dev[0]), _lib.ptr(volume._axes_dev[1]),
               _lib.ptr(volume._axes_dev[2]), C.byref(gs), _lib.ptr(offs),
-              _lib.ptr(volume._bg), volume.bg_class, _lib.ptr(volume._center),
-              _lib.ptr(volume._scale), _lib.ptr(X), _lib.ptr(y), _lib.stream_ptr())
+              _lib.ptr(volume._bg), volume.bg_class, volume._sc,
+              _lib.ptr(X), _lib.ptr(y), _lib.stream_ptr())
     return X, y
 
 
