@@ -535,6 +535,29 @@ int mpu_conv2d_wgrad_first_layer(int32_t dtype, const void* d_x, int32_t n_image
 int mpu_validation_count(const float* d_pred, const uint8_t* d_y, int64_t n, int32_t n_classes, int64_t* d_counts,
                          void* stream);
 
+/* Training metrics (`fit.metrics`; Trainer.compile_model, mpunet/train/utils.py:29-97), accumulated on the device: each call
+ * is one batch of a Keras Mean-wrapped function metric. p = argmax over the class axis of d_pred [n][n_classes] (f32 scores,
+ * probabilities or logits; first maximum, as tf.argmax), y = d_y [n]; per class tp = #(y == p == c), rel = #(y == c),
+ * sel = #(p == c); Kb = 1 + the largest c with rel + sel > 0 (tf.math.confusion_matrix sized from the data). The step's
+ * values, in f64 from the exact integers (0 / 0 = NaN, never filtered), are ADDED to the state:
+ *
+ *   index  name                          total[index] +=                                  count[index] +=
+ *   0      sparse_categorical_accuracy   sum_c tp                                         n
+ *   1      sparse_fg_recall              sum_{c>=1} tp / sum_{c>=1} rel                   1
+ *   2      sparse_fg_precision           sum_{c>=1} tp / sum_{c>=1} sel                   1
+ *   3      sparse_mean_fg_precision      mean_{c=1..Kb-1} tp/sel                          1
+ *   4      sparse_mean_fg_recall         mean_{c=1..Kb-1} tp/rel                          1
+ *   5      sparse_mean_fg_f1             mean_{c=1..Kb-1} 2pr/(p+r), p = tp/sel, r = tp/rel    1
+ *
+ * The metric's value over the calls so far is total / count (0 where count == 0). State buffer (8-byte aligned,
+ * mpu_train_metrics_state_bytes() bytes): f64 total[6] at byte 0, f64 count[6] at byte 48, then private scratch that the call
+ * leaves zeroed. An all-zero buffer is a fresh state; zeroing it resets every metric. Two launches (count, then a one-wave
+ * finalize), no host synchronisation, nothing else read or written: the call may be captured into a HIP graph and replayed.
+ * Targets >= n_classes count for no class. n == 0 is a no-op. 1 <= n_classes <= 16. */
+int64_t mpu_train_metrics_state_bytes(void);
+int mpu_train_metrics_update(const float* d_pred, const uint8_t* d_y, int64_t n, int32_t n_classes, void* d_state,
+                             void* stream);
+
 /* Measurement aid (bench.py roofline leg; no reference counterpart): when
  * enabled, every MFMA convolution launch is bracketed by HIP events recorded on
  * its own stream. mpu_profile_summary synchronises on them and returns the summed

@@ -83,6 +83,16 @@ def loss_kwargs_of(fit):
     return kw
 
 
+def epoch_logs(loss, metric_totals, device=None):
+    """The epoch's `logs` as Keras hands them to the callbacks: the loss, then the compiled training metrics (fit.metrics; the
+    Mean over all replicas' steps, distributed.reduce_metrics), in front of the val_* keys Validation adds -- the epoch line,
+    CSVLogger's columns and the monitors of ReduceLROnPlateau / EarlyStopping / ModelCheckPointClean see them."""
+    from ..distributed import reduce_metrics
+    logs = {"loss": loss}
+    logs.update(reduce_metrics(metric_totals, device))
+    return logs
+
+
 def run(args):
     from .. import distributed as D
     from ..unet import UNet
@@ -148,6 +158,7 @@ def run(args):
     model.compile(fit["optimizer"], fit["loss"], fit.get("metrics"), optimizer_kwargs=fit.get("optimizer_kwargs"),
                   loss_kwargs=loss_kwargs_of(fit))
     log("Optimizer:   %s" % model.optimizer_description())              # trainer.py:98
+    log("Metrics:     %s" % model.metrics_description())                # trainer.py:100
     if world > 1:
         D.DataParallelTrainer(model)
     B = int(fit["batch_size"])
@@ -194,7 +205,7 @@ def run(args):
                 t = torch.tensor([loss], dtype=torch.float64, device=device)
                 torch.distributed.all_reduce(t)
                 loss = float(t.item()) / world
-            logs = {"loss": loss}
+            logs = epoch_logs(loss, pipe.epoch_metrics(), device)
             if validation is not None:
                 validation.on_epoch_end(model, ep, logs)
             log("Epoch %d/%d - " % (ep + 1, epochs) + " - ".join("%s: %.5f" % kv for kv in logs.items()))

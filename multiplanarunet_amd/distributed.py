@@ -63,6 +63,22 @@ def allreduce_sum_(flat, bucket_bytes=64 << 20):
     return flat
 
 
+def reduce_metrics(totals, device=None):
+    """{name: (total, count)} of this rank's training metrics (pipeline.TrainPipeline.epoch_metrics) -> {name: value}: totals and
+    counts are SUM-all-reduced over the ranks (one collective) BEFORE the division, so every replica's per-step scalar enters the
+    Mean once, as MirroredStrategy aggregates a Keras Mean; one rank's NaN total makes the value NaN on every rank. Then Keras'
+    Mean.result(): total / count, 0 where count == 0."""
+    from .unet import mean_metric
+    names = list(totals)
+    if not names:
+        return {}
+    t = torch.tensor([v for n in names for v in totals[n]], dtype=torch.float64, device=device)
+    if world_size() > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    t = t.cpu().tolist()
+    return {n: mean_metric(t[2 * i], t[2 * i + 1]) for i, n in enumerate(names)}
+
+
 def plan_buckets(ready_points, n, bucket_bytes, elem_bytes=4):
     """
     Gradient buckets for the overlapped all-reduce. ready_points: descending float offsets; after point k every

@@ -7,7 +7,8 @@ process instead of between threads: batch i+1 is cut on a side stream (chosen by
 with a fill probe, the first four then serve ten training steps each and the one with the fastest loop is kept) while train
 step i runs on the main stream. The sampler's per-candidate host read (8 bytes of accept / reject statistics) synchronises only the side stream, so the
 host never waits for the train step; the step itself is one HIP-graph replay (UNet.make_graphed_train_step on fixed input
-tensors -- the cut batch is copied into them, 1 MB) and the loss is accumulated on the device and read once per epoch.
+tensors -- the cut batch is copied into them, 1 MB) and the loss and the compiled metrics are accumulated on the device and
+read once per epoch each.
 
   main stream : [copy b_i -> graph inputs][step i .............][copy b_i+1][step i+1 ..........]
   side stream :          [cut b_i+1: ~16 candidates, each sample + stats + 8-byte read]   [cut b_i+2 ...]
@@ -111,7 +112,7 @@ class TrainPipeline:
         self.side, self.side_latency_us = self._cands[0] if self._cands else (None, None)
         self._cal = {"i": 0, "n": 0, "t0": 0.0} if len(self._cands) > 1 else None
         self.side_loop_ms = []
-        self._replay, self._lr = None, None
+        self._replay, self._lr, self._metrics_state = None, None, None
         self._pending = None
 
     # ---- producer ---------------------------------------------------------------------------------------------------------
@@ -138,10 +139,11 @@ class TrainPipeline:
                 self.loss_sum += m.reg_loss.double()
             return
         lr = float(m.optimizer_kwargs["lr"])
-        if self._replay is None or lr != self._lr:      # first step, or ReduceLROnPlateau moved the rate: (re)capture
+        # first step, ReduceLROnPlateau moved the rate, or compile() replaced the metric state the captured launches add to: (re)capture
+        if self._replay is None or lr != self._lr or m._metrics_state is not self._metrics_state:
             self._replay = m.make_graphed_train_step(self.gx, self.gy, self.gw, loss_sum=self.loss_sum,
                                                      warmup=self._replay is None)
-            self._lr = lr
+            self._lr, self._metrics_state = lr, m._metrics_state
             if self._replay.warmup_ran:                  # the capture's warm-up WAS this step (a real one, loss included)
                 return
         self._replay()
@@ -189,6 +191,13 @@ class TrainPipeline:
         self.loss_sum.zero_()
         self.steps_in_sum = 0
         return tot / n
+
+    def epoch_metrics(self):
+        """{name: (total, count)} of the model's compiled metrics over the steps since the last call -- the Keras Mean of each is
+        total / count (unet.mean_metric; under data parallelism after a SUM over the ranks: distributed.reduce_metrics) -- in ONE
+        device read, and the state starts from zero again. The metrics are accumulated by the step itself (eager or replayed:
+        mpu_train_metrics_update behind the training forward), the capture's warm-up step included once. {} without metrics."""
+        return self.model.metrics_totals(reset=True)
 
     def run_epoch(self, steps):
         for _ in range(int(steps)):

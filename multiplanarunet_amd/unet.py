@@ -39,6 +39,35 @@ _OPTIMIZERS = {
 }
 _UNSUPPORTED = "supported optimizers: Adam (also amsgrad), SGD, RMSprop, Adamax, each with learning-rate decay"
 
+# `fit.metrics` (mpunet/train/utils.py:29-97: tf.keras.metrics first, then mpunet/evaluate/metrics.py), in the order of the state
+# buffer of mpu_train_metrics_update (include/mpunet_hip.h): index = position here
+METRICS = ("sparse_categorical_accuracy", "sparse_fg_recall", "sparse_fg_precision", "sparse_mean_fg_precision",
+           "sparse_mean_fg_recall", "sparse_mean_fg_f1")
+
+
+def mean_metric(total, count):
+    """Keras Mean.result(): total / count, 0 where count == 0 (div_no_nan); a NaN total stays NaN."""
+    return float(total) / float(count) if count else 0.0
+
+
+def _resolve_metrics(metrics):
+    """The validated list of `fit.metrics` names (None, [] -> []). A name that is not one of METRICS -- `accuracy`, a Keras metric
+    class, sparse_top_k_categorical_accuracy, the NumPy helpers of metrics.py (dice, dice_all, class_wise_kappa, one_class_dice)
+    -- raises NotImplementedError: nothing is accepted and then left out of the logs."""
+    if metrics is None:
+        return []
+    if isinstance(metrics, str) or not isinstance(metrics, (list, tuple)):
+        metrics = [metrics]
+    names = []
+    for m in metrics:
+        name = m if isinstance(m, str) else getattr(m, "__name__", type(m).__name__)
+        if name not in METRICS:
+            raise NotImplementedError("metric %r is not supported (supported metrics: %s)" % (name, ", ".join(METRICS)))
+        if name in names:
+            raise ValueError("metric %r is listed twice" % name)
+        names.append(name)
+    return names
+
 
 def _resolve_optimizer(optimizer, optimizer_kwargs):
     """(class name, validated keywords) of `fit.optimizer` / `fit.optimizer_kwargs`. Unknown keywords raise TypeError as the
@@ -202,6 +231,8 @@ class UNet:
         self.receptive_field = np.array([rf, rf])
         self.layers = [_OutputLayerShim(self)]
         self.metrics_names = ["loss"]
+        self._metric_names = []        # compile(metrics=...): the compiled names, and the device state of mpu_train_metrics_update
+        self._metrics_state = None     #   (f64 view: total[6] | count[6] | scratch); None = nothing is allocated or launched
         self.log()
 
     # ------------------------------------------------------------------ #
@@ -501,8 +532,21 @@ class UNet:
         start from zero. Compiling the SAME name again UPDATES the stored kwargs and keeps the state, as it always did for
         Adam's lr: compile("SGD", momentum 0.9) then compile("SGD") still has momentum 0.9, and amsgrad / nesterov / centered /
         decay stay set until they are given again. Pass every key, or compile another name in between, for a fresh start.
+
+        `metrics`: names out of METRICS -- tf.keras.metrics' sparse_categorical_accuracy and sparse_fg_recall, sparse_fg_precision,
+        sparse_mean_fg_precision, sparse_mean_fg_recall, sparse_mean_fg_f1 of mpunet/evaluate/metrics.py:84-156 -- anything else
+        raises NotImplementedError; None / [] compile none (nothing allocated, no launch added to the step). As in Keras they are
+        UNWEIGHTED (sample_weight goes to the loss only) and each is the Mean over the epoch's batches (accuracy: over its
+        pixels) of the batch's value, NaN batches included: metrics_result(), reset_metrics(). Every training forward then
+        feeds the step's probabilities and labels to mpu_train_metrics_update (csrc/train_metrics.hip), eager or inside the
+        graphed step. The three sparse_mean_fg_* call tf.confusion_matrix / tf.diag_part, TF-1 names that the reference's pinned
+        TF 2.3 no longer has (there they raise AttributeError); they are built with the semantics of the renamed
+        tf.math.confusion_matrix / tf.linalg.diag_part: classes above the largest one present in the batch's labels and
+        predictions drop out of the mean. Values are f64 from exact integer counts; Keras keeps f32 totals (and rounds accuracy
+        totals above 2**24 pixels), which is not imitated. Compiling another list starts the state from zero.
         """
-        opt_name, opt_kw = _resolve_optimizer(optimizer, optimizer_kwargs)     # (both raise before anything is changed)
+        opt_name, opt_kw = _resolve_optimizer(optimizer, optimizer_kwargs)     # (all three raise before anything is changed)
+        metric_names = _resolve_metrics(metrics)
         same = opt_name == self.optimizer_name  # another optimizer starts from its own defaults
         new_kw = dict(self.optimizer_kwargs if same else _OPTIMIZERS[opt_name][1])
         new_kw.update(opt_kw)
@@ -524,7 +568,46 @@ class UNet:
             self._slots = None                  # no state of the previous optimizer (or of another variant: other slots)
             self.iterations = 0
         self.optimizer_name, self.optimizer_kwargs = opt_name, new_kw
+        if metric_names != self._metric_names:
+            self._metric_names = metric_names
+            self.metrics_names = ["loss"] + metric_names
+            self._metrics_state = None
+            if metric_names:
+                n = int(_lib.load().mpu_train_metrics_state_bytes())
+                self._metrics_state = torch.zeros(n // 8, dtype=torch.float64, device=self.device)
         return self
+
+    def metrics_description(self):
+        """The line Trainer.compile_model logs (trainer.py:100, "Metrics:     %s")."""
+        return str(list(self._metric_names))
+
+    def reset_metrics(self):
+        """Start the compiled metrics from zero (Keras does at the start of every epoch)."""
+        if self._metrics_state is not None:
+            self._metrics_state.zero_()
+
+    def metrics_totals(self, reset=False):
+        """{name: (total, count)} of the compiled metrics since the last reset: ONE device read."""
+        if self._metrics_state is None:
+            return {}
+        nm = len(METRICS)
+        host = self._metrics_state[:2 * nm].cpu().numpy()
+        if reset:
+            self._metrics_state.zero_()
+        return {name: (float(host[METRICS.index(name)]), float(host[nm + METRICS.index(name)])) for name in self._metric_names}
+
+    def metrics_result(self):
+        """{name: value} of the compiled metrics since the last reset_metrics() (Keras Mean.result(): total / count, 0 where
+        count == 0): ONE device read."""
+        return {name: mean_metric(t, c) for name, (t, c) in self.metrics_totals().items()}
+
+    def _update_metrics(self, probs, y):
+        """One batch into the metric state: right behind the training forward, on its stream (probs: the f32 view the forward left
+        in the workspace; y: uint8 [B, H*W])."""
+        if self._metrics_state is None:
+            return
+        _lib.call("mpu_train_metrics_update", _lib.ptr(probs), _lib.ptr(y), int(y.numel()), int(self.n_classes),
+                  _lib.ptr(self._metrics_state), _lib.stream_ptr())
 
     def optimizer_description(self):
         """The line Trainer.compile_model logs (trainer.py:98, "Optimizer:   %s")."""
@@ -643,6 +726,7 @@ class UNet:
             sw = torch.as_tensor(np.asarray(sample_weight, np.float32) if not torch.is_tensor(sample_weight)
                                  else sample_weight).to(device=self.device, dtype=torch.float32).contiguous()
         probs = self._forward(X, training=True)
+        self._update_metrics(probs, y)
         loss = torch.empty((B, 1 if self._per_image_loss else y.shape[1]), dtype=torch.float32,
                            device=self.device) if want_loss else None
         if adam is not None:
@@ -801,7 +885,7 @@ class UNet:
         # (The model's own buffers too: a later, larger eager batch REPLACES self._ws -- the graph keeps running on the one it
         # was captured with, which must therefore stay allocated.)
         replay.keep_alive = (step_dev, x, y, sample_weight, loss_sum, self._ws, self._l2_ws, getattr(self, "reg_loss", None),
-                             tuple(self._slots), self.params, self.grads, self.packed, self.bn_state)
+                             tuple(self._slots), self.params, self.grads, self.packed, self.bn_state, self._metrics_state)
         return replay
 
     def train_step(self, x, y, sample_weight=None, want_loss=True):
@@ -820,23 +904,36 @@ class UNet:
         self.apply_gradients()
         return loss
 
-    def train_on_batch(self, x, y, sample_weight=None):
-        """Scalar Keras reports for the step: mean of the weighted per-pixel loss (+ the l2 term when l2_reg is set)."""
+    def _batch_loss(self, x, y, sample_weight=None):
         loss = float(self.train_step(x, y, sample_weight).mean().item())
         return loss + float(self.reg_loss.item()) if self.l2_reg else loss
 
+    def train_on_batch(self, x, y, sample_weight=None):
+        """Scalar Keras reports for the step: mean of the weighted per-pixel loss (+ the l2 term when l2_reg is set). With compiled
+        metrics: [loss, m1, ...] of THIS batch in the order of metrics_names (Keras' default reset_metrics=True: the state holds
+        this batch alone afterwards)."""
+        self.reset_metrics()
+        loss = self._batch_loss(x, y, sample_weight)
+        if not self._metric_names:
+            return loss
+        res = self.metrics_result()
+        return [loss] + [res[n] for n in self._metric_names]
+
     def fit(self, data, steps_per_epoch, epochs=1, callbacks=None, initial_epoch=0, verbose=0, **kwargs):
-        """Minimal Model.fit over an iterator of (x, y, w) batches (trainer.py:246-257)."""
+        """Minimal Model.fit over an iterator of (x, y, w) batches (trainer.py:246-257). The compiled metrics run over the whole
+        epoch (reset at its start); `verbose` reports them beside the loss."""
         it = iter(data)
         history = []
         for ep in range(initial_epoch, epochs):
             tot = 0.0
+            self.reset_metrics()
             for _ in range(steps_per_epoch):
                 x, y, w = next(it)
-                tot += self.train_on_batch(x, y, w)
+                tot += self._batch_loss(x, y, w)
             history.append(tot / steps_per_epoch)
             if verbose:
-                self.logger("epoch %d: loss %.5f" % (ep + 1, history[-1]))
+                self.logger("epoch %d: loss %.5f" % (ep + 1, history[-1])
+                            + "".join(" - %s: %.5f" % kv for kv in self.metrics_result().items()))
             if self.stop_training:
                 break
         return history
