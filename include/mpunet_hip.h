@@ -558,6 +558,24 @@ int64_t mpu_train_metrics_state_bytes(void);
 int mpu_train_metrics_update(const float* d_pred, const uint8_t* d_y, int64_t n, int32_t n_classes, void* d_state,
                              void* stream);
 
+/* The compiled loss of one batch from its probabilities, with no training step around it (Model.evaluate / test_on_batch; the
+ * batch-wise val_loss of the Validation callback, mpunet/callbacks/validation.py:148-206). d_pred f32 [B, ppi, n_classes]
+ * probabilities (the output of mpu_unet_forward), d_y [B, ppi], d_sw [B] per-image weights or NULL (= ones). cfg: any
+ * mpu_loss_kind. The five per-image kinds give L_b exactly as the train step reports it for the same probabilities (the same
+ * kernels). MPU_LOSS_SPARSE_CE: L_b = the mean over the image's pixels of the Keras form on clipped probabilities,
+ * -log q_y + log sum_k q_k with q = clip(p, 1e-7, 1 - 1e-7) (the second term is what TF's softmax cross-entropy makes of the
+ * clipped row; it is zero unless the clip moved an entry), so that mean_b w_b L_b is the mean over all B * ppi pixels that Keras
+ * logs for the flattened output. Outputs, each optional: d_loss [B] = w_b * L_b; d_acc f64 [2]: d_acc[0] += mean_b(w_b L_b),
+ * d_acc[1] += 1 (a Keras Mean over batches; zero it to start, SUM all-reduce it across replicas).
+ * 1 <= n_classes <= 8, 1 <= B <= 65535, 1 <= ppi <= 2^40, else MPU_EUNSUPPORTED; a NULL or misaligned (8 bytes: d_scratch, d_acc)
+ * argument or a bad cfg: MPU_EINVAL. A label >= n_classes enters no sum and indexes nothing. d_scratch:
+ * mpu_eval_loss_scratch_bytes(B, ppi, n_classes) bytes (< 0 + mpu_last_error() outside the ranges above), contents irrelevant
+ * before and after. Two launches, f64 sums in a fixed order and no atomics (two calls on the same input give the same bits), no
+ * host synchronisation, nothing read or written but the arguments: the call may be captured into a HIP graph. */
+int64_t mpu_eval_loss_scratch_bytes(int32_t B, int64_t ppi, int32_t n_classes);
+int mpu_eval_loss(const mpu_loss_config* cfg, const float* d_pred, const uint8_t* d_y, const float* d_sw, int32_t B, int64_t ppi,
+                  int32_t n_classes, void* d_scratch, float* d_loss, double* d_acc, void* stream);
+
 /* Measurement aid (bench.py roofline leg; no reference counterpart): when
  * enabled, every MFMA convolution launch is bracketed by HIP events recorded on
  * its own stream. mpu_profile_summary synchronises on them and returns the summed

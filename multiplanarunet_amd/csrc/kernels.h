@@ -326,9 +326,12 @@ inline int head_loss_form(int loss_kind) {
 // Statistics pass + coefficient step of such a loss, two launches: per image and class I = sum [y=k] p, P = sum p, R = sum [y=k]
 // (exp-log: on the clipped p) and the image's sum of the per-pixel term (focal, exp-log), in fixed-order f64 partials whose
 // geometry depends on the image size alone; then `coef`, d_loss[b] = w_b * L_b (may be NULL) and *loss_mean = mean_b w_b L_b.
+// The evaluation entry (eval_loss.hip) takes the VALUES alone: coef and loss_mean NULL, sw NULL = ones, and acc (f64 [2], optional):
+// acc[0] += mean_b w_b L_b, acc[1] += 1.
+constexpr long HEAD_LOSS_MAX_PPI = 1L << 40;     // (the chunk count stays an int)
 long head_loss_scratch_doubles(int B, long ppi, int K);
 int launch_head_loss_coeffs(const mpu_loss_config& cfg, const float* probs, const uint8_t* y, const float* sw, int B, long ppi, int K,
-                            double* scratch, float* coef, float* d_loss, float* loss_mean, hipStream_t st);
+                            double* scratch, float* coef, float* d_loss, float* loss_mean, hipStream_t st, double* acc = nullptr);
 // Loss gradient at the logits (Keras sparse CE on clipped probabilities, see oracle/unet_ref.py keras_sparse_ce, or `hl`), sum-gradient:
 // dn = dlogits @ Wh^T, dWh, dbh, per-pixel loss (CE only)
 int launch_head_backward(int dtype, const void* n, const float* probs, const uint8_t* y,

@@ -12,6 +12,8 @@
 //   head_loss_coef_kernel   one workgroup: chunk partials -> sums (fixed order), the [B][K][2] table (a, c) with
 //                           dL_b/dp_mk = a_bk + [y_m = k] c_bk (+ the per-pixel term's own derivative, formed per pixel), L_b,
 //                           d_loss[b] = w_b L_b and the logged mean. No host read: the step is captured into a HIP graph.
+//                           Value-only mode (mpu_eval_loss, eval_loss.hip): coef and loss_mean NULL, sw NULL = ones, and the mean
+//                           ADDED to a f64 accumulator acc = (sum of batch means, number of batches).
 // Determinism: a chunk is a fixed set of pixels (the grid depends on the image size alone), a thread adds its 16 pixels in order, the
 // workgroup reduces by a fixed butterfly and wave order, the coefficient step adds the chunks in order. All sums in f64: every
 // addend of I, P is in [0, 1] and a row has at most H*W <= 2^25 of them, so a sum carries ~2^-53 * log2 of relative rounding error.
@@ -58,6 +60,7 @@ __global__ __launch_bounds__(256) void head_loss_stats_kernel(const float* __res
                 if (k == yy) { sI[k] += (double)v; sR[k] += 1.0; }
             }
         }
+        if (yy >= K) continue;                                   // a label outside the classes has no per-pixel term
         if (kind == MPU_LOSS_FOCAL) sE += -(double)cwy * head_pow_f64((double)(1.f - qy), (double)gamma) * log((double)qy);
         else if (kind == MPU_LOSS_EXP_LOG) sE += head_pow_f64(-log((double)qy), (double)gamma);
     }
@@ -79,7 +82,8 @@ __global__ __launch_bounds__(256) void head_loss_stats_kernel(const float* __res
 // scratch (doubles): part [B][nchunk][NS] | sums [B][NS] | term [B][K] | wl [B]
 __global__ __launch_bounds__(256) void head_loss_coef_kernel(mpu_loss_config cfg, const float* __restrict__ sw, int B, int K, int nchunk,
                                                             double inv_ppi, double* __restrict__ scratch, float* __restrict__ coef,
-                                                            float* __restrict__ d_loss, float* __restrict__ loss_mean) {
+                                                            float* __restrict__ d_loss, float* __restrict__ loss_mean,
+                                                            double* __restrict__ acc) {
     const int NS = 3 * K + 1;
     double* part = scratch;
     double* sums = part + (long)B * nchunk * NS;
@@ -128,7 +132,7 @@ __global__ __launch_bounds__(256) void head_loss_coef_kernel(mpu_loss_config cfg
             const double h = -(double)cfg.weight_dice * iK * gd * pow(nl, gd - 1.0) / X;     // d(share)/dX
             t = (double)cfg.weight_dice * iK * pow(nl, gd); a = -h * A / (U * U); c = 2.0 * h / U;
         }
-        coef[2 * i] = (float)a; coef[2 * i + 1] = (float)c;
+        if (coef) { coef[2 * i] = (float)a; coef[2 * i + 1] = (float)c; }
         term[i] = t;
     }
     __syncthreads();
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(256) void head_loss_coef_kernel(mpu_loss_config cfg
         const double E = sums[b * NS + 3 * K] * inv_ppi;         // pixel mean of the per-pixel term
         if (cfg.kind == MPU_LOSS_FOCAL) L += E;
         else if (cfg.kind == MPU_LOSS_EXP_LOG) L += (double)cfg.weight_cross * E;
-        const double v = (double)sw[b] * L;
+        const double v = (sw ? (double)sw[b] : 1.0) * L;
         wl[b] = v;
         if (d_loss) d_loss[b] = (float)v;
     }
@@ -146,7 +150,8 @@ __global__ __launch_bounds__(256) void head_loss_coef_kernel(mpu_loss_config cfg
     if (threadIdx.x == 0) {
         double s = 0.0;
         for (int b = 0; b < B; ++b) s += wl[b];
-        *loss_mean = (float)(s / (double)B);
+        if (loss_mean) *loss_mean = (float)(s / (double)B);
+        if (acc) { acc[0] += s / (double)B; acc[1] += 1.0; }
     }
 }
 
@@ -160,9 +165,10 @@ long head_loss_scratch_doubles(int B, long ppi, int K) {
 }
 
 int launch_head_loss_coeffs(const mpu_loss_config& cfg, const float* probs, const uint8_t* y, const float* sw, int B, long ppi, int K,
-                            double* scratch, float* coef, float* d_loss, float* loss_mean, hipStream_t st) {
+                            double* scratch, float* coef, float* d_loss, float* loss_mean, hipStream_t st, double* acc) {
     if (cfg.kind <= MPU_LOSS_SPARSE_CE || cfg.kind > MPU_LOSS_EXP_LOG) return fail(MPU_EINVAL, "%s", "head loss: not a per-image loss kind");
     if (B < 1 || B > 65535) return fail(MPU_EUNSUPPORTED, "%s", "head loss: batch must be 1..65535");
+    if (ppi < 1 || ppi > HEAD_LOSS_MAX_PPI) return fail(MPU_EUNSUPPORTED, "%s", "head loss: pixels per image must be 1..2^40");
     const int nchunk = loss_chunks(ppi);
     HeadLoss cwv{};
     for (int k = 0; k < 8; ++k) cwv.cw[k] = (cfg.n_class_weights > 0 && k < cfg.n_class_weights) ? cfg.class_weights[k] : 1.f;
@@ -176,7 +182,7 @@ int launch_head_loss_coeffs(const mpu_loss_config& cfg, const float* probs, cons
     }
     int rc = launch_ok();
     if (rc) return rc;
-    head_loss_coef_kernel<<<1, 256, 0, st>>>(cfg, sw, B, K, nchunk, 1.0 / (double)ppi, scratch, coef, d_loss, loss_mean);
+    head_loss_coef_kernel<<<1, 256, 0, st>>>(cfg, sw, B, K, nchunk, 1.0 / (double)ppi, scratch, coef, d_loss, loss_mean, acc);
     return launch_ok();
 }
 

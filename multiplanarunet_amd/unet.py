@@ -233,6 +233,11 @@ class UNet:
         self.metrics_names = ["loss"]
         self._metric_names = []        # compile(metrics=...): the compiled names, and the device state of mpu_train_metrics_update
         self._metrics_state = None     #   (f64 view: total[6] | count[6] | scratch); None = nothing is allocated or launched
+        self._loss_cfg = _lib.LossConfig()     # the compiled loss as mpu_eval_loss takes it (kind 0: the sparse cross-entropy)
+        self._eval_acc = None          # evaluation (test_on_batch / evaluate / the Validation callback): buffers of its own,
+        self._eval_metrics_state = None    # allocated on first use -- never the state of the running training epoch
+        self._eval_ws, self._eval_ws_shape = None, None
+        self._eval_loss_sum, self._eval_loss_n = 0.0, 0
         self.log()
 
     # ------------------------------------------------------------------ #
@@ -572,6 +577,7 @@ class UNet:
             self._metric_names = metric_names
             self.metrics_names = ["loss"] + metric_names
             self._metrics_state = None
+            self._eval_metrics_state = None
             if metric_names:
                 n = int(_lib.load().mpu_train_metrics_state_bytes())
                 self._metrics_state = torch.zeros(n // 8, dtype=torch.float64, device=self.device)
@@ -679,6 +685,7 @@ class UNet:
                 for i, v in enumerate(cw):
                     cfg.class_weights[i] = v
         _lib.call("mpu_unet_set_loss", self._h, C.byref(cfg))
+        self._loss_cfg = cfg
         self.loss_name = lname or "SparseCategoricalCrossentropy"
         self._per_image_loss = lname is not None
         self._ws = None                    # the workspace plan of a handle with a per-image loss is larger
@@ -918,6 +925,135 @@ class UNet:
             return loss
         res = self.metrics_result()
         return [loss] + [res[n] for n in self._metric_names]
+
+    # ---- evaluation ----------------------------------------------------- #
+    def evaluation_begin(self):
+        """(acc, metrics_state): the zeroed device accumulators of one evaluation pass, owned by the model and apart from the
+        training epoch's metric state -- acc f64 [2] (sum of batch-mean losses, number of batches), metrics_state as
+        mpu_train_metrics_update lays it out (None without compiled metrics)."""
+        if self._eval_acc is None:
+            self._eval_acc = torch.zeros(2, dtype=torch.float64, device=self.device)
+        if self._metric_names and self._eval_metrics_state is None:
+            n = int(_lib.load().mpu_train_metrics_state_bytes())
+            self._eval_metrics_state = torch.zeros(n // 8, dtype=torch.float64, device=self.device)
+        self._eval_acc.zero_()
+        if self._eval_metrics_state is not None:
+            self._eval_metrics_state.zero_()
+        self._eval_loss_sum, self._eval_loss_n = 0.0, 0        # test_on_batch / evaluate: sum of w_b * L_b and number of images
+        return self._eval_acc, self._eval_metrics_state
+
+    def evaluation_update(self, probs, y, acc=None, metrics_state=None, sample_weight=None, loss_out=None):
+        """One batch of already-computed probabilities (f32 device tensor, [B, ..., K]: predict_on_batch's output) and labels into
+        device accumulators, no host read: the compiled loss of the batch by mpu_eval_loss (csrc/eval_loss.hip) -- acc[0] += mean
+        over the batch of w_b * L_b, acc[1] += 1; loss_out f32 [B] receives w_b * L_b -- and the compiled metrics by
+        mpu_train_metrics_update into metrics_state (unweighted). The Validation callback feeds its batches through here."""
+        K = int(self.n_classes)
+        B = int(probs.shape[0])
+        p = probs.reshape(B, -1, K)
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            p = p.to(torch.float32).contiguous()
+        if not torch.is_tensor(y):
+            y = torch.from_numpy(np.ascontiguousarray(y))
+        y = y.to(device=p.device, dtype=torch.uint8).reshape(B, -1).contiguous()
+        ppi = int(p.shape[1])
+        if y.shape[1] != ppi:
+            raise ValueError("evaluation_update: %d labels for %d predictions per image" % (y.shape[1], ppi))
+        sw = None
+        if sample_weight is not None:
+            sw = torch.as_tensor(np.asarray(sample_weight, np.float32) if not torch.is_tensor(sample_weight)
+                                 else sample_weight).to(device=p.device, dtype=torch.float32).reshape(-1).contiguous()
+            if sw.numel() != B:
+                raise ValueError("evaluation_update: sample_weight needs one entry per image")
+        if self._eval_ws is None or self._eval_ws_shape != (B, ppi):      # (validation batches share one shape: one query per run)
+            need = int(_lib.load().mpu_eval_loss_scratch_bytes(B, ppi, K))
+            if need < 0:
+                raise ValueError("mpu_eval_loss: " + (_lib.load().mpu_last_error() or b"").decode())
+            if self._eval_ws is None or self._eval_ws.numel() < need:
+                self._eval_ws = torch.empty(need, dtype=torch.uint8, device=p.device)
+            self._eval_ws_shape = (B, ppi)
+        _lib.call("mpu_eval_loss", C.byref(self._loss_cfg), _lib.ptr(p), _lib.ptr(y), _lib.ptr(sw), B, ppi, K,
+                  _lib.ptr(self._eval_ws), _lib.ptr(loss_out), _lib.ptr(acc), _lib.stream_ptr())
+        if metrics_state is not None and self._metric_names:
+            _lib.call("mpu_train_metrics_update", _lib.ptr(p), _lib.ptr(y), B * ppi, K, _lib.ptr(metrics_state),
+                      _lib.stream_ptr())
+
+    def evaluation_totals(self, acc, metrics_state=None):
+        """{"loss": (total, count), <metric>: (total, count), ...} of the accumulators, in metrics_names order: the pairs a Keras
+        Mean holds (result: mean_metric), ready for a SUM all-reduce over replicas."""
+        out = {"loss": tuple(float(v) for v in acc.cpu().tolist())}
+        if metrics_state is not None and self._metric_names:
+            nm = len(METRICS)
+            host = metrics_state[:2 * nm].cpu().numpy()
+            for name in self._metric_names:
+                out[name] = (float(host[METRICS.index(name)]), float(host[nm + METRICS.index(name)]))
+        return out
+
+    def l2_penalty(self):
+        """l2_reg * sum W^2 over the kernels mpu_unet_l2_regularizer covers (every conv kernel but the 1x1 head's), in f64,
+        without touching the gradients: the term Keras adds to an evaluated loss. Device scalar; None without l2_reg."""
+        if not self.l2_reg:
+            return None
+        tot = torch.zeros((), dtype=torch.float64, device=self.device)
+        for nm in self._order:
+            kind, off, ps, _ = self._tensors[nm]
+            if kind == 0 and nm.endswith("/kernel") and nm != "conv2d/kernel":
+                tot += self.params[off:off + int(np.prod(ps))].double().pow(2).sum()     # (the channel padding holds zeros)
+        return tot * float(np.float32(self.l2_reg))                                      # (the train step's l2 is an f32 too)
+
+    def _evaluate_chunks(self, x, y, sample_weight, batch_size, reset_metrics):
+        """The inference-mode forward (BatchNorm on the moving statistics: predict_on_batch's path) over chunks of batch_size images,
+        each fed to evaluation_update; the per-image losses w_b * L_b land in one [N] buffer whose mean is Keras' loss Mean
+        (weighted by batch size). One host read at the end."""
+        n = int(x.shape[0])
+        if n < 1:
+            raise ValueError("evaluation needs at least one image")
+        if reset_metrics or self._eval_acc is None or (self._metric_names and self._eval_metrics_state is None):
+            self.evaluation_begin()
+        state = self._eval_metrics_state
+        if not torch.is_tensor(y):
+            y = torch.from_numpy(np.ascontiguousarray(y))
+        y = y.reshape(n, -1)
+        if sample_weight is not None and not torch.is_tensor(sample_weight):
+            sample_weight = torch.from_numpy(np.asarray(sample_weight, np.float32))
+        per_image = torch.empty(n, dtype=torch.float32, device=self.device)
+        for s in range(0, n, batch_size):
+            e = min(n, s + batch_size)
+            probs = self._forward(self._as_input(x[s:e]), training=False)
+            self.evaluation_update(probs, y[s:e], None, state, None if sample_weight is None else sample_weight[s:e],
+                                   loss_out=per_image[s:e])
+        self._eval_loss_sum += float(per_image.double().sum().item())
+        self._eval_loss_n += n
+        loss = self._eval_loss_sum / self._eval_loss_n
+        reg = self.l2_penalty()
+        if reg is not None:
+            loss += float(reg.item())
+        res = {"loss": loss}
+        if self._metric_names:
+            totals = self.evaluation_totals(self._eval_acc, state)
+            res.update({k: mean_metric(*totals[k]) for k in self._metric_names})
+        return res
+
+    def _evaluation_output(self, res, return_dict):
+        if return_dict:
+            return res
+        return res["loss"] if not self._metric_names else [res[k] for k in self.metrics_names]
+
+    def test_on_batch(self, x, y, sample_weight=None, reset_metrics=True, return_dict=False):
+        """Keras Model.test_on_batch: the compiled loss (sample-weighted; + the l2 term when l2_reg is set) and the compiled metrics
+        (unweighted) of one batch under the inference-mode forward -- a scalar, or [loss, m1, ...] in metrics_names order as
+        train_on_batch returns them; return_dict: {"loss": ..., name: ...}. reset_metrics=False continues the Means of the
+        calls before. Nothing of the model changes: no gradient, no optimizer state, no moving statistic, and not the metric
+        state of the running training epoch (the forward refreshes the folded BatchNorm coefficients at the tail of `packed`
+        after a weight change, exactly as predict_on_batch does)."""
+        res = self._evaluate_chunks(x, y, sample_weight, max(1, int(x.shape[0])), reset_metrics)
+        return self._evaluation_output(res, return_dict)
+
+    def evaluate(self, x, y, batch_size=32, sample_weight=None, return_dict=False):
+        """Keras Model.evaluate on arrays: test_on_batch's computation in chunks of batch_size. The loss is the Mean over the batches
+        weighted by batch size (= the mean over the images of w_b * L_b; the cross-entropy: over all pixels), the metrics follow
+        the accumulator semantics of compile()'s docstring over the chunks."""
+        res = self._evaluate_chunks(x, y, sample_weight, 32 if batch_size is None else int(batch_size), True)
+        return self._evaluation_output(res, return_dict)
 
     def fit(self, data, steps_per_epoch, epochs=1, callbacks=None, initial_epoch=0, verbose=0, **kwargs):
         """Minimal Model.fit over an iterator of (x, y, w) batches (trainer.py:246-257). The compiled metrics run over the whole

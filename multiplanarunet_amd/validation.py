@@ -20,6 +20,9 @@ import numpy as np
 import torch
 
 
+LOG_ROUND = 4          # decimals of the batch-wise values in the logs (validation.py:49: log_round)
+
+
 def count_cm_elements(pred, true, n_classes, counts=None):
     """
     validation.py:115-125 on the GPU: argmax of the class scores `pred` [..., K] (f32, device) fused with the
@@ -82,12 +85,25 @@ class Validation:
     def evaluate(self, model):
         K = self.n_classes
         cnt = torch.zeros((3, K), dtype=torch.int64, device=model.device)      # TP, relevant, selected
+        # batch-wise loss and metrics "as specified in model.compile" (validation.py:19,24-27,148-206), for a model that offers
+        # the hook (UNet.evaluation_update): device accumulators, no host read per step, no sample weights
+        batch_wise = hasattr(model, "evaluation_update")
+        acc, state = model.evaluation_begin() if batch_wise else (None, None)
         for _ in range(self.steps):
             x, y, _w = self.sampler()
             pred = model.predict_on_batch(x)
             count_cm_elements(pred, y, K, counts=cnt)
+            if batch_wise:
+                model.evaluation_update(pred, y, acc, state)
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             torch.distributed.all_reduce(cnt)
+        self.batch_wise = {}
+        if batch_wise:
+            # (total, count) pairs, SUM-reduced over the replicas before the division; val_loss = the mean over the validation
+            # batches of the batch's mean loss, val_<metric> = the metric's Mean over them (validation.py:196,206), 4 decimals (:49,276)
+            from .distributed import reduce_metrics
+            values = reduce_metrics(model.evaluation_totals(acc, state), model.device)
+            self.batch_wise = {name: float(np.round(v, LOG_ROUND)) for name, v in values.items()}
         TP, REL, SEL = cnt[0], cnt[1], cnt[2]
         # as the reference: sel=relevant, rel=selected
         precisions, recalls, dices = compute_dice(TP.cpu().numpy(), rel=SEL.cpu().numpy(), sel=REL.cpu().numpy())
@@ -97,17 +113,32 @@ class Validation:
 
     def on_epoch_end(self, model, epoch, logs):
         cw = self.evaluate(model)
+        for name, value in self.batch_wise.items():             # validation.py:275-279: batch-wise first, then class-wise
+            logs["val_" + name] = value
         with np.errstate(all="ignore"):
             for name, values in cw.items():
                 logs["val_" + name] = float(np.nanmean(values)) if np.any(~np.isnan(values)) else float("nan")
         if self.verbose:
+            fmt = lambda v: "-" if np.isnan(v) else "%.4f" % v
+            col = "%%-%ds" % max([9] + [len(n) + 2 for n in self.batch_wise])       # (9: the class-wise names alone)
             rows = ["Validation Results for epoch %d" % epoch,
-                    "        " + "  ".join("%9s" % c for c in ["mean"] + ["cls %d" % i for i in range(self.n_classes)])]
+                    (col % "")[1:] + "  ".join("%9s" % c for c in ["mean"] + ["cls %d" % i for i in range(self.n_classes)])]
+            for name, value in self.batch_wise.items():         # one row each, the `mean` column alone (validation.py:255-256)
+                rows.append(col % name + "  ".join("%9s" % v for v in [fmt(value)] + ["-"] * self.n_classes))
             for name, values in cw.items():
                 vals = [logs["val_" + name]] + list(values)
-                rows.append("%-9s" % name + "  ".join("%9s" % ("-" if np.isnan(v) else "%.4f" % v) for v in vals))
+                rows.append(col % name + "  ".join("%9s" % fmt(v) for v in vals))
             self.logger("\n".join(rows))
         return cw
+
+
+def resolve_mode(mode, monitor, checkpoint=False):
+    """mode "auto" as tf.keras 2.3 resolves it: max when "acc" is in the monitor's name (ModelCheckpoint: or the name starts with
+    "fmeasure"), else min. "min" / "max" pass through; anything else is treated as auto, as Keras does after its warning."""
+    if mode in ("min", "max"):
+        return mode
+    monitor = str(monitor)
+    return "max" if "acc" in monitor or (checkpoint and monitor.startswith("fmeasure")) else "min"
 
 
 class ReduceLROnPlateau:
@@ -115,6 +146,7 @@ class ReduceLROnPlateau:
                  verbose=1, logger=None):
         if factor >= 1.0:
             raise ValueError("ReduceLROnPlateau does not support a factor >= 1.0.")
+        mode = resolve_mode(mode, monitor)
         self.monitor, self.factor, self.patience, self.mode = monitor, factor, patience, mode
         self.min_delta, self.cooldown, self.min_lr = min_delta, cooldown, min_lr
         self.logger = logger or print
@@ -151,6 +183,7 @@ class ReduceLROnPlateau:
 
 class EarlyStopping:
     def __init__(self, monitor="val_dice", min_delta=0, patience=15, mode="max", verbose=1, logger=None):
+        mode = resolve_mode(mode, monitor)
         self.monitor, self.min_delta, self.patience, self.mode = monitor, abs(min_delta), patience, mode
         self.logger = logger or print
         self.verbose = verbose
@@ -178,6 +211,7 @@ class ModelCheckPointClean:
     """save_best_only + save_weights_only; the previously saved file is removed (mcp_clean.py:25-59)."""
 
     def __init__(self, filepath, monitor="val_dice", mode="max", verbose=1, logger=None):
+        mode = resolve_mode(mode, monitor, checkpoint=True)
         self.filepath, self.monitor, self.mode = filepath, monitor, mode
         self.logger = logger or print
         self.verbose = verbose
