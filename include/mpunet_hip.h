@@ -203,6 +203,38 @@ int mpu_fusion_finalize(const float* d_z, int64_t n, int32_t n_classes,
                         const float* d_b, int32_t sum_fusion,
                         float* d_probs, uint8_t* d_labels, void* stream);
 
+/* map_real_space_pred(method="linear") (fuse_and_predict.py:92-137): the view's
+ * prediction is the RegularGridInterpolator's `values` on (g, g, offsets), the
+ * voxel's point q = inv_basis * p its query. Per axis _find_indices (cell
+ * clipped to [0, n-2], y by IEEE division; a point ON the last node is in
+ * bounds: cell n-2, y = 1); per class an fp64 sum from 0.0 over the eight
+ * corners in itertools.product order (first axis slowest, plane axis fastest)
+ * of (double)pred[corner][k] * (((1.0*wx)*wy)*wz), w = {1-y, y}, rounded once
+ * to f32, no FMA contraction; a voxel out of the view's box on any axis takes
+ * [1,0,...,0]. Bit for bit the reference's result. 1 <= n_classes <= 16, any
+ * axis kind. The three calls take the arguments of their nearest counterparts:
+ *   mpu_map_view_linear        d_mapped f32 [X,Y,Z,K]
+ *   mpu_map_fuse_views_linear  the f32 vector above in the place of the gathered
+ *                              one, then exactly mpu_map_fuse_views' arithmetic;
+ *                              d_probs or d_labels may be NULL
+ *   mpu_map_accumulate_view_linear  view->d_pred holds the planes
+ *       [p_lo, min(p_hi + 1, P)): the chunk and ONE halo plane. A voxel belongs
+ *       to the chunk when the CELL index of its plane axis lies in [p_lo, p_hi)
+ *       (cells end at P-2: the last chunk owns that cell, a chunk of the last
+ *       plane alone owns nothing), so a voxel's eight-corner sum stays on one
+ *       rank and rounds as in the unsharded call. The chunk with owns_oob adds
+ *       the fill vector of the out-of-box voxels. */
+int mpu_map_view_linear(const mpu_voxel_grid* grid, const mpu_view_pred* view,
+                        int32_t n_classes, float* d_mapped, void* stream);
+int mpu_map_fuse_views_linear(const mpu_voxel_grid* grid, const mpu_view_pred* views,
+                              int32_t n_views, int32_t n_classes,
+                              const float* d_W, const float* d_b, int32_t sum_fusion,
+                              float* d_probs, uint8_t* d_labels, void* stream);
+int mpu_map_accumulate_view_linear(const mpu_voxel_grid* grid, const mpu_view_pred* view,
+                                   int32_t n_classes, const float* d_Wv,
+                                   int32_t p_lo, int32_t p_hi, int32_t owns_oob,
+                                   float* d_z, void* stream);
+
 
 /* ------------------------------------------------------------------------ *
  * 2-D U-Net (MFMA-bound): mpunet.models.UNet (mpunet/models/unet.py:20-251)

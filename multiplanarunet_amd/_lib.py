@@ -115,6 +115,11 @@ _SIGS = {
                                           i32, i32, i32, c_p, c_p]),
     "mpu_map_fuse_views": (C.c_int, [C.POINTER(VoxelGrid), C.POINTER(ViewPred), i32, i32,
                                      c_p, c_p, i32, c_p, c_p, c_p]),
+    "mpu_map_view_linear": (C.c_int, [C.POINTER(VoxelGrid), C.POINTER(ViewPred), i32, c_p, c_p]),
+    "mpu_map_accumulate_view_linear": (C.c_int, [C.POINTER(VoxelGrid), C.POINTER(ViewPred), i32, c_p,
+                                                 i32, i32, i32, c_p, c_p]),
+    "mpu_map_fuse_views_linear": (C.c_int, [C.POINTER(VoxelGrid), C.POINTER(ViewPred), i32, i32,
+                                            c_p, c_p, i32, c_p, c_p, c_p]),
     "mpu_fusion_forward": (C.c_int, [c_p, i64, i32, i32, c_p, c_p, c_p, c_p, c_p]),
     "mpu_fusion_finalize": (C.c_int, [c_p, i64, i32, c_p, i32, c_p, c_p, c_p]),
     "mpu_unet_create": (c_p, [C.POINTER(UNetConfig)]),

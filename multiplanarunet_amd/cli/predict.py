@@ -34,6 +34,10 @@ def get_argparser():
     p.add_argument("--wait_for", type=str, default="")
     p.add_argument("--continue", action="store_true", dest="continue_")
     p.add_argument("--synthetic", type=int, default=0)
+    p.add_argument("--map_method", default="nearest", choices=("nearest", "linear"),
+                   help="how a voxel reads a view's prediction: nearest (default, the reference's predict) or linear (trilinear "
+                        "interpolation of the class probabilities, map_real_space_pred(method='linear')). Fusion weights should be "
+                        "trained with the method used at predict time (mp train_fusion --map_method)")
     p.add_argument("--dtype", default="bf16", choices=("bf16", "f32", "bf16x3"),
                    help="bf16 (default, the benchmarked mode), f32 (exact-f32 MFMAs: the parity mode), bf16x3 (f32 storage, three bf16 "
                         "MFMAs per product: f32-grade results at 2.6x the f32 speed)")
@@ -84,6 +88,7 @@ def run(args):
     wpath = best_model_path(os.path.join(project_dir, "model"))
     model.load_weights(wpath, by_name=True)
     log("Loaded weights:", wpath)
+    log("Back-mapping method:", args.map_method)
     fm = None
     if not args.sum_fusion:
         fm = FusionModel(len(views), build["n_classes"], verbose=False, device=device)
@@ -112,7 +117,8 @@ def run(args):
             raise OSError("%s exists (use --overwrite or --continue)" % dst)
         if world > 1:
             res = D.multi_view_predict_sharded(model, v, views, build["dim"], fit["real_space_span"], fm,
-                                               sum_fusion=args.sum_fusion, batch_size=None, want_probs=args.no_argmax)
+                                               sum_fusion=args.sum_fusion, batch_size=None, want_probs=args.no_argmax,
+                                               map_method=args.map_method)
             probs, labels = res if args.no_argmax else (None, res)
         else:
             pve = None
@@ -122,7 +128,7 @@ def run(args):
                            report=lambda i, view, vd, md, mean, rows=rows: rows.__setitem__(i, (view, vd, md, float(mean))))
             probs, labels = multi_view_predict(model, v, views, build["dim"], fit["real_space_span"], fm,
                                                sum_fusion=args.sum_fusion, batch_size=None,
-                                               want_probs=args.no_argmax, per_view_eval=pve)
+                                               want_probs=args.no_argmax, per_view_eval=pve, map_method=args.map_method)
         if rank == 0 and args.save_input_files:
             sub = out_base                                # the volume as it was read: unscaled image, label map
             os.makedirs(sub, exist_ok=True)

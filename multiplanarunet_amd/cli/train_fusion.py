@@ -41,19 +41,24 @@ def get_argparser():
                    help="bf16 (default, the benchmarked mode), f32 (exact-f32 MFMAs: the parity mode), bf16x3 (f32 storage, three bf16 "
                         "MFMAs per product: f32-grade results at 2.6x the f32 speed)")
     p.add_argument("--seed", type=int, default=None)
+    p.add_argument("--map_method", default="nearest", choices=("nearest", "linear"),
+                   help="how the training points are read from a view's prediction: nearest (default) or linear (trilinear "
+                        "interpolation of the class probabilities). Fusion weights should be trained with the method used at "
+                        "predict time (mp predict --map_method)")
     return p
 
 
-def predict_and_map(model, sampler, volume, view, batch_size, n_planes="same+20"):
-    """One view: sample planes, predict, nearest-map to the voxel grid -> probabilities [X*Y*Z, K] (device)."""
+def predict_and_map(model, sampler, volume, view, batch_size, n_planes="same+20", map_method="nearest"):
+    """One view: sample planes, predict, map (nearest / linear) to the voxel grid -> probabilities [X*Y*Z, K] (device)."""
     from ..interpolation import predict_volume, map_real_space_pred
     X, y, grid, inv_basis = sampler.get_view_from(volume, view, n_planes=n_planes)
     pred = predict_volume(model, X, axis=2, batch_size=batch_size)
-    mapped = map_real_space_pred(pred, grid, inv_basis, volume)
+    mapped = map_real_space_pred(pred, grid, inv_basis, volume, method=map_method)
     return mapped.reshape(-1, mapped.shape[-1]), (y, pred)
 
 
-def collect_points(model, sampler, volumes, views, n_classes, batch_size, log, eval_prob=1.0, rng=None):
+def collect_points(model, sampler, volumes, views, n_classes, batch_size, log, eval_prob=1.0, rng=None,
+                   map_method="nearest"):
     """points [sum voxels, V, K] f32 and targets [sum voxels] u8, both resident on the GPU."""
     from ..interpolation import dice_all
     rng = rng or np.random
@@ -66,7 +71,7 @@ def collect_points(model, sampler, volumes, views, n_classes, batch_size, log, e
         n = int(np.prod(vol.image.shape[:3]))
         pts = torch.empty((n, len(views), n_classes), dtype=torch.float32, device=vol.image.device)
         for k, view in enumerate(views):
-            mapped, (yv, pred) = predict_and_map(model, sampler, vol, view, batch_size)
+            mapped, (yv, pred) = predict_and_map(model, sampler, vol, view, batch_size, map_method=map_method)
             pts[:, k, :] = mapped
             if rng.rand() <= eval_prob:
                 d = dice_all(vol.labels.reshape(-1), mapped.argmax(-1), n_classes=n_classes, ignore_zero=False)
@@ -118,6 +123,7 @@ def run(args):
     unet = UNet(logger=log, dtype=args.dtype, device=device, **bkw)
     unet.load_weights(wpath, by_name=True)
     log("Loaded weights:", wpath)
+    log("Back-mapping method:", args.map_method)
     fm = FusionModel(len(views), n_classes, weight=args.dice_weight, logger=log, verbose=False, device=device)
     if args.continue_training and os.path.exists(fpath):
         fm.load_weights(fpath)
@@ -140,7 +146,7 @@ def run(args):
         mine = [images[i] for i in list(ids_r)[rank::world]]          # the round's images dealt over the ranks
         eval_rng = np.random.RandomState(int(rng.randint(0, 2 ** 31 - 1)) + rank)   # (keeps `rng` in step on every rank)
         X, y = collect_points(unet, sampler, mine, views, n_classes, int(fit["batch_size"]),
-                              log, args.eval_prob, eval_rng)
+                              log, args.eval_prob, eval_rng, map_method=args.map_method)
         fit_seed = int(rng.randint(0, 2 ** 31 - 1))
         perm = torch.from_numpy(np.random.RandomState(fit_seed + 7919 * rank).permutation(X.shape[0])).to(device)
         X, y = X[perm], y[perm]

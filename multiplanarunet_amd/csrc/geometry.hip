@@ -907,6 +907,107 @@ __global__ __launch_bounds__(256) void map_view_fixup_kernel(MapArgs a, const un
     }
 }
 
+// ---- linear back-mapping: map_real_space_pred(method="linear"), fuse_and_predict.py:92-137 ----------------
+// The view's prediction pred[P,dim,dim,K] is the `values` of the RegularGridInterpolator on the axes (g, g, offsets)
+// and the voxel's point q = inv_basis p its query: per axis find_cell (the sampler's _find_indices: cell clipped to
+// [0, n-2], y by IEEE division, a point ON the last node is in bounds with y = 1), then per class the fp64 sum from 0.0
+// over the eight corners in itertools.product order (first axis slowest, plane axis fastest) of
+// (double)pred[corner][k] * (((1.0 * wx) * wy) * wz), w = {1 - y, y}, rounded once to f32 -- sample_one's arithmetic
+// with the K classes in the place of the C channels. A voxel out of the view's box takes [1, 0, ..., 0].
+// The corner (ex, ey, ez) lies at (((i2 + ez) dim + (i0 + ex)) dim + (i1 + ey)) K + k: the two ey corners are 2K
+// contiguous floats, so a voxel issues FOUR 2K-wide gathers per view (8 K floats = 96 bytes at K = 3 where the nearest
+// kernels gather 12), all of them unconditionally at the clipped cell before the first use: eight independent K-vectors
+// in flight per lane, which is why a lane owns ONE voxel here (the nearest kernels own four to have four gathers in
+// flight; four voxels x eight corners at K = 16 would not fit the register file).
+// Plane chunks (the sharded accumulate): v.pred points at plane p_lo and holds planes [p_lo, min(p_hi + 1, P)); a voxel
+// belongs to the chunk when its plane-axis CELL lies in [p_lo, p_hi), so its eight corners are on one rank and the
+// fp64 sum rounds as in the unsharded path. Voxels of other chunks gather at cell 0 of the chunk (never used); a chunk
+// of the last plane alone has no second plane and owns no cell (cells end at P - 2): its plane step is 0.
+enum { LIN_MINE = 0, LIN_OOB = 1, LIN_OTHER = 2 };
+template <int K>
+__device__ __forceinline__ int view_linear(const ViewDev& v, double rx, double ry, double rz, int p_lo, int p_hi,
+                                           float (&x)[K]) {
+    double qx, qy, qz;
+    mat3_apply(v.invb, rx, ry, rz, qx, qy, qz);
+    int i0, i1, i2; double y0, y1, y2; bool o0, o1, o2;
+    find_cell(v.g, qx, i0, y0, o0);
+    find_cell(v.g, qy, i1, y1, o1);
+    find_cell(v.offs, qz, i2, y2, o2);
+    const bool oob = o0 || o1 || o2;
+    const bool mine = !oob && i2 >= p_lo && i2 < p_hi;
+    const long sy = (long)v.dim * K, sz = (long)v.dim * sy;
+    const long dz = (p_lo + 1 < v.P) ? sz : 0;
+    const float* base = v.pred + (long)(mine ? i2 - p_lo : 0) * sz + (long)i0 * sy + (long)i1 * K;
+    float cv[2][2][2 * K];                                       // [ez][ex][ey * K + k]
+#pragma unroll
+    for (int q = 0; q < 4; ++q) __builtin_memcpy(cv[q >> 1][q & 1], base + (q >> 1) * dz + (q & 1) * sy, 2 * K * sizeof(float));
+    // itertools.product order of the 8 corners, weight = ((1*wx)*wy)*wz
+    const double wx[2] = {1.0 - y0, y0}, wy[2] = {1.0 - y1, y1}, wz[2] = {1.0 - y2, y2};
+    double w[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) w[e] = ((1.0 * wx[e >> 2]) * wy[(e >> 1) & 1]) * wz[e & 1];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double acc = 0.0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc = acc + (double)cv[e & 1][e >> 2][((e >> 1) & 1) * K + k] * w[e];
+        x[k] = oob ? (k == 0 ? 1.f : 0.f) : (float)acc;
+    }
+    return oob ? LIN_OOB : (mine ? LIN_MINE : LIN_OTHER);
+}
+
+// ACCUM=false: mapped[t,:] = linear (map_real_space_pred). ACCUM=true: z[t,:] += Wv * linear for the voxels whose
+// plane-axis cell lies in [p_lo, p_hi). One workgroup = one 4x4x16 brick, a lane = one voxel.
+template <int K, bool ACCUM>
+__global__ __launch_bounds__(256) void map_view_linear_kernel(MapArgs a) {
+    const long nblk = brick_count(a.grid);
+    for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        int vx, vy, vz; long t;
+        if (!brick_voxel(a.grid, blk, vx, vy, vz, t)) continue;
+        double rx, ry, rz;
+        voxel_real(a.grid, vx, vy, vz, rx, ry, rz);
+        float x[K];
+        const int st = view_linear<K>(a.view, rx, ry, rz, a.p_lo, a.p_hi, x);
+        if (!ACCUM) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) a.out[t * K + k] = x[k];
+        } else if (st == LIN_MINE) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) a.out[t * K + k] += a.Wv[k] * x[k];
+        } else if (st == LIN_OOB && a.owns_oob) {
+            a.out[t * K] += a.Wv[0];
+        }
+    }
+}
+
+// Fused form: the f32 vector of view_linear takes the place of map_fuse_kernel's gathered vector, same accumulation.
+template <int K>
+__global__ __launch_bounds__(256) void map_fuse_linear_kernel(FuseArgs a) {
+    const long nblk = brick_count(a.grid);
+    for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        int vx, vy, vz; long t;
+        if (!brick_voxel(a.grid, blk, vx, vy, vz, t)) continue;
+        double rx, ry, rz;
+        voxel_real(a.grid, vx, vy, vz, rx, ry, rz);
+        float z[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) z[k] = 0.f;
+#pragma unroll 1
+        for (int v = 0; v < a.V; ++v) {
+            const ViewDev& vw = a.views[v];
+            float x[K];
+            view_linear<K>(vw, rx, ry, rz, 0, vw.P, x);
+#pragma unroll
+            for (int k = 0; k < K; ++k) z[k] = a.sum_fusion ? (z[k] + x[k]) : (z[k] + a.W[v * K + k] * x[k]);
+        }
+        if (!a.sum_fusion) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) z[k] = z[k] + a.b[k];
+        }
+        softmax_argmax_store<K>(z, !a.sum_fusion, t, a.probs, a.labels);
+    }
+}
+
 template <int K>
 __global__ __launch_bounds__(256) void fusion_forward_kernel(const float* __restrict__ x, long n, int V,
                                                              const float* W, const float* b,
@@ -1439,6 +1540,56 @@ int mpu_map_fuse_views(const mpu_voxel_grid* grid, const mpu_view_pred* views, i
     }
     if (sched_log_on()) sched_note("map_fuse generic views=%d K=%d", n_views, n_classes);
     MPU_DISPATCH_K(n_classes, (map_fuse_kernel<KK><<<dim3(fuse_grid(a.grid)), dim3(256), 0, (hipStream_t)stream>>>(a)));
+    return launch_ok();
+}
+
+/* map_real_space_pred(method="linear") of one view (any axis kind: find_cell's exact search; its closed-form cell on
+ * uniform axes follows mpu_geometry_set_fast_path / MPU_GEOM_FAST as in the sampler) */
+int mpu_map_view_linear(const mpu_voxel_grid* grid, const mpu_view_pred* view, int32_t n_classes,
+                        float* d_mapped, void* stream) {
+    { const int rc_ = sync_fast_switch(); if (rc_) return rc_; }
+    MPU_REQUIRE(grid && view && d_mapped && view->d_pred && view->d_g && view->d_offsets,
+                "mpu_map_view_linear: null argument");
+    MPU_REQUIRE(view->dim >= 2 && view->n_planes >= 2, "mpu_map_view_linear: view needs dim>=2, planes>=2");
+    MapArgs a; to_grid(*grid, a.grid); to_view(*view, a.view);
+    a.Wv = nullptr; a.p_lo = 0; a.p_hi = view->n_planes; a.owns_oob = 1; a.out = d_mapped;
+    if (sched_log_on()) sched_note("map_view linear accum=0 K=%d", n_classes);
+    MPU_DISPATCH_K(n_classes, (map_view_linear_kernel<KK, false><<<dim3(brick_grid(a.grid)), dim3(256), 0, (hipStream_t)stream>>>(a)));
+    return launch_ok();
+}
+
+int mpu_map_accumulate_view_linear(const mpu_voxel_grid* grid, const mpu_view_pred* view, int32_t n_classes,
+                                   const float* d_Wv, int32_t p_lo, int32_t p_hi, int32_t owns_oob,
+                                   float* d_z, void* stream) {
+    { const int rc_ = sync_fast_switch(); if (rc_) return rc_; }
+    MPU_REQUIRE(grid && view && d_z && d_Wv && view->d_pred && view->d_g && view->d_offsets,
+                "mpu_map_accumulate_view_linear: null argument");
+    MPU_REQUIRE(view->dim >= 2 && view->n_planes >= 2, "mpu_map_accumulate_view_linear: view needs dim>=2, planes>=2");
+    MPU_REQUIRE(0 <= p_lo && p_lo < p_hi && p_hi <= view->n_planes, "mpu_map_accumulate_view_linear: bad plane range");
+    MapArgs a; to_grid(*grid, a.grid); to_view(*view, a.view);
+    a.Wv = d_Wv; a.p_lo = p_lo; a.p_hi = p_hi; a.owns_oob = owns_oob; a.out = d_z;
+    if (sched_log_on()) sched_note("map_view linear accum=1 K=%d", n_classes);
+    MPU_DISPATCH_K(n_classes, (map_view_linear_kernel<KK, true><<<dim3(brick_grid(a.grid)), dim3(256), 0, (hipStream_t)stream>>>(a)));
+    return launch_ok();
+}
+
+int mpu_map_fuse_views_linear(const mpu_voxel_grid* grid, const mpu_view_pred* views, int32_t n_views,
+                              int32_t n_classes, const float* d_W, const float* d_b, int32_t sum_fusion,
+                              float* d_probs, uint8_t* d_labels, void* stream) {
+    { const int rc_ = sync_fast_switch(); if (rc_) return rc_; }
+    MPU_REQUIRE(grid && views, "mpu_map_fuse_views_linear: null argument");
+    MPU_REQUIRE(n_views >= 1 && n_views <= MAX_VIEWS, "mpu_map_fuse_views_linear: n_views must be in 1..16");
+    MPU_REQUIRE(sum_fusion || (d_W && d_b), "mpu_map_fuse_views_linear: W and b required unless sum_fusion");
+    MPU_REQUIRE(d_probs || d_labels, "mpu_map_fuse_views_linear: no output requested");
+    FuseArgs a; to_grid(*grid, a.grid);
+    for (int v = 0; v < n_views; ++v) {
+        MPU_REQUIRE(views[v].d_pred && views[v].d_g && views[v].d_offsets, "mpu_map_fuse_views_linear: null view field");
+        MPU_REQUIRE(views[v].dim >= 2 && views[v].n_planes >= 2, "mpu_map_fuse_views_linear: view needs dim>=2, planes>=2");
+        to_view(views[v], a.views[v]);
+    }
+    a.V = n_views; a.W = d_W; a.b = d_b; a.sum_fusion = sum_fusion; a.probs = d_probs; a.labels = d_labels;
+    if (sched_log_on()) sched_note("map_fuse linear views=%d K=%d", n_views, n_classes);
+    MPU_DISPATCH_K(n_classes, (map_fuse_linear_kernel<KK><<<dim3(brick_grid(a.grid)), dim3(256), 0, (hipStream_t)stream>>>(a)));
     return launch_ok();
 }
 

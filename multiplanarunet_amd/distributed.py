@@ -289,7 +289,7 @@ def all_gather_slabs(slab, X):
 
 def multi_view_predict_sharded(model, volume, views, dim, real_space_span, fusion_model=None,
                                sum_fusion=False, batch_size=None, n_planes="same+20", exchange=None, timings=None,
-                               want_probs=False):
+                               want_probs=False, map_method="nearest"):
     """
     multiplanarunet_amd.predict.multi_view_predict over all ranks. Every rank
     holds the full input volume; returns the full uint8 label volume on every rank -- with want_probs=True
@@ -302,14 +302,19 @@ def multi_view_predict_sharded(model, volume, views, dim, real_space_span, fusio
     its views to the voxel grid (`mapped_v [X,Y,Z,K]`), ALL-GATHER of the per-view volumes rebuilds
     `combined [V,X,Y,Z,K]` on every rank, then the FusionLayer + argmax runs locally. V times the traffic and
     at most V busy ranks; kept for equivalence testing and for fusion models that are not linear in the views.
+
+    map_method="linear": a work item (vi, lo, hi) samples and predicts the planes [lo, min(hi + 1, P)) -- its chunk and one
+    halo plane -- and accumulates the voxels whose plane-axis cell lies in [lo, hi), so that the eight corners of a voxel's
+    interpolation are summed on one rank (interpolation.map_accumulate); the all_gather scheme maps whole views.
     """
     exchange = exchange or os.environ.get("MPU_PREDICT_EXCHANGE") or "reduce_scatter"
     if exchange == "all_gather":
         return _multi_view_predict_allgather(model, volume, views, dim, real_space_span, fusion_model,
-                                             sum_fusion, batch_size, n_planes, timings, want_probs)
+                                             sum_fusion, batch_size, n_planes, timings, want_probs, map_method)
     if exchange != "reduce_scatter":
         raise ValueError("exchange must be 'reduce_scatter' or 'all_gather'")
-    from .interpolation import ViewGeometry, sample_view, map_accumulate, fusion_finalize
+    from .interpolation import ViewGeometry, sample_view, map_accumulate, fusion_finalize, linear_chunk_planes, _map_entry
+    _map_entry(map_method, None, None)                      # (refuses an unknown method before any work)
     world = world_size()
     rank = dist.get_rank() if world > 1 else 0
     K = model.n_classes
@@ -322,11 +327,13 @@ def multi_view_predict_sharded(model, volume, views, dim, real_space_span, fusio
     z = torch.zeros((X, Y, Z, K), dtype=torch.float32, device=volume.device)
     geoms = [ViewGeometry(v, dim, real_space_span, n_planes) for v in views]
     items = plane_work_items(len(views), geoms[0].n_planes, world)[rank]
+    how = {} if map_method == "nearest" else {"method": map_method}        # (the default call is the call it always was)
     for (vi, lo, hi) in items:
         g = geoms[vi]
         sub = ViewGeometry(views[vi], dim, real_space_span, n_planes)
-        sub.offsets = g.offsets[lo:hi]
-        sub.n_planes = hi - lo
+        s_lo, s_hi = linear_chunk_planes(lo, hi, g.n_planes) if map_method == "linear" else (lo, hi)
+        sub.offsets = g.offsets[s_lo:s_hi]
+        sub.n_planes = s_hi - s_lo
         Xs, _ = sample_view(volume, sub, want_labels=False)
         pred = model.predict(Xs, batch_size=batch_size)
         if pred.ndim == 3:
@@ -336,7 +343,7 @@ def multi_view_predict_sharded(model, volume, views, dim, real_space_span, fusio
         else:
             Wv = fusion_model.W[vi]
         map_accumulate(volume, pred, (g.real_axis, g.real_axis, g.offsets), g.inv_basis, Wv,
-                       lo, hi, owns_oob=(lo == 0), z=z)
+                       lo, hi, owns_oob=(lo == 0), z=z, **how)
     # timings (bench.py): the rank's own work up to here, then the exchange (reduce-scatter + finalize + all-gather);
     # with the blocking collectives a host clock around a synchronised region is the honest measure
     if timings is not None:
@@ -359,7 +366,7 @@ def multi_view_predict_sharded(model, volume, views, dim, real_space_span, fusio
 
 
 def _multi_view_predict_allgather(model, volume, views, dim, real_space_span, fusion_model, sum_fusion,
-                                  batch_size, n_planes, timings=None, want_probs=False):
+                                  batch_size, n_planes, timings=None, want_probs=False, map_method="nearest"):
     from .interpolation import ViewGeometry, sample_view, map_real_space_pred, pred_to_class
     import time
     world = world_size()
@@ -383,7 +390,7 @@ def _multi_view_predict_allgather(model, volume, views, dim, real_space_span, fu
             if pred.ndim == 3:
                 pred = pred.reshape(Xs.shape[0], dim, dim, -1)
             mine = map_real_space_pred(pred.permute(1, 2, 0, 3), (g.real_axis, g.real_axis, g.offsets),
-                                       g.inv_basis, volume)
+                                       g.inv_basis, volume, method=map_method)
         if world > 1:
             if timings is not None:
                 sync(); t1 = time.perf_counter()

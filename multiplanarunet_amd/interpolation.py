@@ -290,32 +290,45 @@ def predict_volume(model, X, batch_size=8, axis=0):
     return torch.movedim(pred, 0, axis) if torch.is_tensor(pred) else np.moveaxis(pred, 0, axis)
 
 
+def _map_entry(method, nearest, linear):
+    """C entry point of a back-mapping method; the reference's 'kNN' (and every other name) is not on the path."""
+    if method == "nearest":
+        return nearest
+    if method == "linear":
+        return linear
+    raise NotImplementedError("map method %r: 'nearest' and 'linear' are on the path (fuse_and_predict.py:92-137)" % (method,))
+
+
 def map_real_space_pred(pred, grid, inv_basis, volume, method="nearest"):
     """
     pred in the reference layout [dim,dim,P,K] (torch, device) on axes
     grid=(g,g,offsets) -> mapped f32 [X,Y,Z,K]; OOB voxels -> [1,0,..,0].
     `volume` stands in for voxel_grid_real_space (computed on the fly).
+    method="linear" (fuse_and_predict.py:130-134, the other half of the reference's signature): the K probability
+    maps are interpolated by the same RegularGridInterpolator -- per axis _find_indices, per class an fp64 sum over
+    the eight corners in itertools.product order of pred * ((1*wx)*wy)*wz, rounded once to f32 -- bit for bit.
     """
-    if method != "nearest":
-        raise NotImplementedError("only method='nearest' is on the path (predict.py:329-331)")
+    entry = _map_entry(method, "mpu_map_view_nearest", "mpu_map_view_linear")
     pm = pred.permute(2, 0, 1, 3)
     h = _ViewPredHolder(pm, grid, inv_basis, volume.device)
     K = int(pm.shape[-1])
     X, Y, Z = (int(v) for v in volume.image.shape[:3])
     mapped = torch.empty((X, Y, Z, K), dtype=torch.float32, device=volume.device)
     vg = volume.voxel_grid()
-    _lib.call("mpu_map_view_nearest", C.byref(vg), C.byref(h.struct), K, _lib.ptr(mapped),
+    _lib.call(entry, C.byref(vg), C.byref(h.struct), K, _lib.ptr(mapped),
               _lib.stream_ptr())
     return mapped
 
 
 def map_and_fuse(volume, view_preds, W=None, b=None, sum_fusion=False,
-                 want_probs=True, want_labels=True):
+                 want_probs=True, want_labels=True, method="nearest"):
     """
     Fused _multi_view_predict_on + merge_multi_view_preds. view_preds: list of
     (pred [P,dim,dim,K] device f32, grid=(g,g,offsets), inv_basis[, ViewGeometry.device_axes]). Returns
-    (merged f32 [X,Y,Z,K] or None, merged_map u8 [X,Y,Z] or None).
+    (merged f32 [X,Y,Z,K] or None, merged_map u8 [X,Y,Z] or None). method: how a voxel reads a view's prediction
+    ("nearest" / "linear", as map_real_space_pred); the fusion arithmetic is the same.
     """
+    entry = _map_entry(method, "mpu_map_fuse_views", "mpu_map_fuse_views_linear")
     dev = volume.device
     holders = [_ViewPredHolder(vp[0], vp[1], vp[2], dev, vp[3] if len(vp) > 3 else None) for vp in view_preds]
     V = len(holders)
@@ -329,19 +342,34 @@ def map_and_fuse(volume, view_preds, W=None, b=None, sum_fusion=False,
         Wd = torch.as_tensor(W, dtype=torch.float32).to(dev).reshape(V, K).contiguous()
         bd = torch.as_tensor(b, dtype=torch.float32).to(dev).reshape(K).contiguous()
     vg = volume.voxel_grid()
-    _lib.call("mpu_map_fuse_views", C.byref(vg), arr, V, K, _lib.ptr(Wd), _lib.ptr(bd),
+    _lib.call(entry, C.byref(vg), arr, V, K, _lib.ptr(Wd), _lib.ptr(bd),
               1 if sum_fusion else 0, _lib.ptr(probs), _lib.ptr(labels), _lib.stream_ptr())
     return probs, labels
 
 
-def map_accumulate(volume, pred_chunk, grid, inv_basis, Wv, p_lo, p_hi, owns_oob, z):
-    """Multi-GPU predict: z += Wv * nearest(x_v) for planes [p_lo,p_hi) (pred_chunk holds only those)."""
+def linear_chunk_planes(p_lo, p_hi, n_planes):
+    """Planes a linear work item [p_lo, p_hi) must hold: the chunk and one halo plane, [p_lo, min(p_hi + 1, P)). The item owns the
+    voxels whose plane-axis cell c (0 <= c <= P - 2, between the planes c and c + 1) lies in [p_lo, p_hi)."""
+    return int(p_lo), min(int(p_hi) + 1, int(n_planes))
+
+
+def map_accumulate(volume, pred_chunk, grid, inv_basis, Wv, p_lo, p_hi, owns_oob, z, method="nearest"):
+    """Multi-GPU predict: z += Wv * nearest(x_v) for planes [p_lo,p_hi) (pred_chunk holds only those).
+    method="linear": z += Wv * linear(x_v) for the voxels whose plane-axis cell lies in [p_lo, p_hi); pred_chunk holds
+    the planes linear_chunk_planes(p_lo, p_hi, P) -- the chunk and one halo plane -- so that a voxel's eight corners
+    are summed on one rank."""
+    entry = _map_entry(method, "mpu_map_accumulate_view", "mpu_map_accumulate_view_linear")
     dev = volume.device
+    if method == "linear":
+        lo_, hi_ = linear_chunk_planes(p_lo, p_hi, len(grid[2]))
+        if int(pred_chunk.shape[0]) != hi_ - lo_:
+            raise ValueError("linear map_accumulate of planes [%d, %d) needs the %d planes [%d, %d), got %d"
+                             % (p_lo, p_hi, hi_ - lo_, lo_, hi_, int(pred_chunk.shape[0])))
     h = _ViewPredHolder(pred_chunk, grid, inv_basis, dev)
     K = int(pred_chunk.shape[-1])
     Wd = torch.as_tensor(Wv, dtype=torch.float32).to(dev).reshape(K).contiguous()
     vg = volume.voxel_grid()
-    _lib.call("mpu_map_accumulate_view", C.byref(vg), C.byref(h.struct), K, _lib.ptr(Wd),
+    _lib.call(entry, C.byref(vg), C.byref(h.struct), K, _lib.ptr(Wd),
               int(p_lo), int(p_hi), 1 if owns_oob else 0, _lib.ptr(z), _lib.stream_ptr())
     return z
 

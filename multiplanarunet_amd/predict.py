@@ -1,7 +1,7 @@
 """
 The 6-view predict+fuse loop of `mp predict` (mpunet/bin/predict.py:294-366) on
 one GPU: per view sample planes (HIP) -> U-Net forward (HIP) -> after all views one
-fused nearest-map + weighted-softmax + argmax kernel. `combined[V,X,Y,Z,K]` and
+fused map (nearest, or linear with map_method="linear") + weighted-softmax + argmax kernel. `combined[V,X,Y,Z,K]` and
 the fp64 voxel grid of the reference are never materialised.
 """
 import numpy as np
@@ -24,7 +24,7 @@ def per_view_evaluation(pred, true, mapped_pred, mapped_true, n_classes):
 
 def multi_view_predict(model, volume, views, dim, real_space_span, fusion_model=None,
                        sum_fusion=False, batch_size=None, n_planes="same+20",
-                       want_probs=True, timings=None, per_view_eval=None):
+                       want_probs=True, timings=None, per_view_eval=None, map_method="nearest"):
     """
     Returns (merged f32 [X,Y,Z,K] or None, merged_map u8 [X,Y,Z]).
     per_view_eval: None, or dict(eval_prob=float, n_classes=int, report=callable(view_index, view, view_dices, mapped_dices,
@@ -34,6 +34,9 @@ def multi_view_predict(model, volume, views, dim, real_space_span, fusion_model=
     (UNet.auto_batch; 276 planes of 256x256 -> 3 x 92). The same batch size gives the same bits run after run; ANOTHER batch size
     selects other kernel schedules for some layers, i.e. another bf16 rounding pattern (measured on an untrained configs[1] network,
     128^3: fused probabilities within 1.7e-3, 0.013 % of the labels -- voxels whose two best classes are within 3e-4 -- differ).
+    map_method: "nearest" (the reference's predict.py:329-331) or "linear" -- how a voxel reads a view's prediction, in the
+    per-view evaluation and in the final fuse alike (interpolation.map_real_space_pred). Fusion weights should have been trained with
+    the method used here.
     fusion_model: object with .W (V,K) and .b (1,K) device tensors (FusionModel) or None with sum_fusion.
     """
     if fusion_model is None and not sum_fusion:
@@ -63,7 +66,7 @@ def multi_view_predict(model, volume, views, dim, real_space_span, fusion_model=
                 say("Skipping evaluation for view %s... (eval_prob=%.3f)" % (view, pve["eval_prob"]))
             else:
                 mapped = map_real_space_pred(pred.permute(1, 2, 0, 3), (geom.real_axis, geom.real_axis, geom.offsets),
-                                             geom.inv_basis, volume)
+                                             geom.inv_basis, volume, method=map_method)
                 vd, md, mean = per_view_evaluation(pred, y_view, mapped, volume.labels, pve["n_classes"])
                 del mapped
                 say("View dice scores:   ", vd)
@@ -77,7 +80,7 @@ def multi_view_predict(model, volume, views, dim, real_space_span, fusion_model=
     if not sum_fusion:
         W, b = fusion_model.W, fusion_model.b
     probs, labels = map_and_fuse(volume, view_preds, W, b, sum_fusion=sum_fusion,
-                                 want_probs=want_probs, want_labels=True)
+                                 want_probs=want_probs, want_labels=True, method=map_method)
     if timings is not None:
         f1.record()
         torch.cuda.synchronize()
