@@ -249,9 +249,14 @@ enum { MPU_CONV3 = 0,      /* Conv2D(k=3, padding="same")                 unet.p
 /* What UNet.__init__ / init_model (unet.py:26-112,182-216) derive from the
  * constructor arguments. filters[l] = int(64 * 2^l * sqrt(complexity_factor)),
  * l = 0..depth (unet.py:91,120,132). padding="same", activation="relu",
- * kernel_size=3 are the only supported values. */
+ * kernel_size=3 are the only supported values.
+ * Two class limits: a handle with 1..8 classes trains, evaluates and predicts; one with 9..16 classes is INFERENCE-ONLY
+ * (mpu_unet_forward with training == 0, the weight / packing / query entry points). On such a handle the training-mode forward,
+ * mpu_unet_backward / _backward_events / _backward_adam and mpu_unet_set_loss with anything but the plain MPU_LOSS_SPARSE_CE
+ * return MPU_EUNSUPPORTED ("U-Net training and evaluation support 1..8 classes; 9..16 are inference-only") before any launch
+ * and without changing the handle. mpu_eval_loss likewise takes 1..8 classes. */
 typedef struct {
-    int32_t n_classes;     /* 1..8                                              */
+    int32_t n_classes;     /* 1..16 (9..16: inference-only, see above)          */
     int32_t n_channels;
     int32_t depth;         /* 1..6                                              */
     int32_t H, W;          /* img_rows, img_cols: multiples of 2^depth          */
@@ -354,7 +359,8 @@ typedef struct {
     float   class_weights[8];
 } mpu_loss_config;
 /* MPU_EINVAL + mpu_last_error() on an unknown kind or type_weight, a negative smooth, a class-weight count that is neither 0 nor
- * n_classes, or a handle created with softmax == 0. */
+ * n_classes, or a handle created with softmax == 0. MPU_EUNSUPPORTED on a handle with more than 8 classes unless cfg is the
+ * default (MPU_LOSS_SPARSE_CE, no class weights). */
 int mpu_unet_set_loss(mpu_unet* m, const mpu_loss_config* cfg);
 
 /* Accept / reject statistics of one sampled training slice (mpunet/sequences/isotrophic_live_view_sequence.py:91-128:
@@ -393,7 +399,8 @@ int mpu_elastic_transform_2d(const float* d_image, const uint8_t* d_labels, int3
  * reference's per-point generalized Dice loss (mpunet/evaluate/loss_functions.py:207-246, SUM_OVER_BATCH_SIZE) plus
  * its 1e-6 * mean(square) regularisers. t >= 1: Keras Adam step t is applied to d_W [V][K] / d_b [K] (moments in
  * d_adam_m / d_adam_v, V*K+K floats); t == 0: gradients and loss only. d_grads_out (V*K+K floats) and d_loss_out
- * (1 float, the batch loss BEFORE the update) may be NULL. */
+ * (1 float, the batch loss BEFORE the update) may be NULL. 1 <= V <= 16 views, 1 <= K <= 16 classes (9..16: two lanes per
+ * point, eight classes each; same partial rows, same fixed-order reduction, bit-reproducible run to run). */
 int64_t mpu_fusion_train_workspace_floats(int32_t n_views, int32_t n_classes);
 int mpu_fusion_train_step(const float* d_x, const uint8_t* d_y, int64_t n, int32_t n_views,
                           int32_t n_classes, float* d_W, float* d_b, float* d_adam_m, float* d_adam_v,

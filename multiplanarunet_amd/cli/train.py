@@ -95,7 +95,7 @@ def epoch_logs(loss, metric_totals, device=None):
 
 def run(args):
     from .. import distributed as D
-    from ..unet import UNet
+    from ..unet import UNet, require_trainable
     from ..data import TrainSampler
     project_dir = os.path.abspath(args.project_dir)
     validate_project_dir(project_dir)
@@ -110,6 +110,8 @@ def run(args):
         raise OSError("There seems to be existing files in the project 'model' folder. "
                       "Use --overwrite or --continue_training.")
     hp = load_hparams(project_dir)
+    if hp["build"].get("n_classes"):                       # (an audited YAML; one that leaves it to the data is checked below)
+        require_trainable(hp["build"]["n_classes"], "mp train")
     note_inert_flags(args, [("no_images", "no sample images are written during training"), ("debug", "the TF debugger has no counterpart"),
                             ("max_loaded_images", "volumes stay resident in HBM: there is no image queue"),
                             ("num_access", "volumes stay resident in HBM: there is no image queue")], log)
@@ -119,6 +121,7 @@ def run(args):
     if not train:
         raise OSError("no training volumes (set train_data.base_dir to a folder with images/*.npz, or --synthetic N)")
     fill_build_from_data(hp, train)                        # audit the FULL training set (before --just_one)
+    require_trainable(hp["build"]["n_classes"], "mp train")    # 9..16 classes predict and fuse, they do not train: every rank, up front
     train_all = list(train)
     if args.just_one:
         train, val = train[:1], val[:1]

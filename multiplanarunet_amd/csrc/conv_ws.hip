@@ -21,7 +21,7 @@ namespace mpu {
 
 namespace {
 
-template <int TH>
+template <int TH, int HK = 8>                                    // HK: class rows of the fused head's weight table (8, or 16: the wide head)
 struct WsCfg {
     static constexpr int TW = 32, PW = TW + 2, PH = TH + 2;
     static constexpr int PROWS = (PH * PW + 7) / 8 * 8;
@@ -30,7 +30,7 @@ struct WsCfg {
     static constexpr int WPX = BM / 2;                           // pixels per wave (2 x 2 waves: channels x rows)
     static constexpr int OROW = 32 * 2 + 16;                     // per-wave staging row: 32 channels + pad
     static constexpr int WBYTES = 9 * 64 * 128;
-    static constexpr int HEADW = 64 * 8 * 4;                     // head weights [64 channels][8 classes] f32 (fused head)
+    static constexpr int HEADW = 2 * HK * 64 * 2;                // head weights [2 parts][HK classes][64 channels] bf16 (fused head)
     static constexpr int STAGE_MIN = 4 * WPX * OROW + 3 * 64 * 4 + HEADW;
     // LDS: [per-wave staging tiles + bias tables][patch 1][patch 0]; the whole weight tensor is staged
     // through the same bytes once, before the first patch is requested
@@ -40,10 +40,14 @@ struct WsCfg {
     static_assert(STAGE % 1024 == 0 && SMEM >= WBYTES, "LDS plan");
 };
 
-template <int TH, bool HEAD>
+// HW: width of the fused 1x1 head -- 0 none, 8 (1..8 classes) or 16 (9..16 classes: the same four MFMAs per pixel row, A rows
+// 8..15 carry the classes 8..15, +2 KB of LDS for their weights)
+template <int TH, int HW>
 __global__ __launch_bounds__(256, 2) void conv_ws_kernel(ConvArgs a, int ntiles, unsigned magic_x, unsigned magic_y,
                                                          unsigned magic_g, int xcd_chunk) {
-    using Cfg = WsCfg<TH>;
+    constexpr bool HEAD = HW != 0;
+    constexpr int HK = HW == 16 ? 16 : 8;                        // class rows of hwt
+    using Cfg = WsCfg<TH, HK>;
     constexpr int TW = Cfg::TW, PW = Cfg::PW, PROWS = Cfg::PROWS;
     constexpr int TM = TH / 2;                                   // pixel rows per wave (2 x 2 waves: channels x rows)
     constexpr int NPP = PROWS / 8, NPW = (NPP + 3) / 4;
@@ -120,16 +124,16 @@ __global__ __launch_bounds__(256, 2) void conv_ws_kernel(ConvArgs a, int ntiles,
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     float* stab = (float*)(smem + 4 * Cfg::WPX * OROW);         // bias; folded-BN affine (inference): scale, shift
-    // fused head: the head weights of classes 0..7 as two bf16 parts (w = hi + lo, |error| <= 2^-18 |w|), rows of 64
-    // channels: hwt[part][class][channel] -- the A operand of a 32x32x16 MFMA whose rows 8..31 are zero
+    // fused head: the head weights of classes 0..HK-1 as two bf16 parts (w = hi + lo, |error| <= 2^-18 |w|), rows of 64
+    // channels: hwt[part][class][channel] -- the A operand of a 32x32x16 MFMA whose rows HK..31 are zero
     bf16_t* hwt = (bf16_t*)(stab + 3 * 64);
     if (HEAD) {
-        for (int i = tid; i < 8 * 64; i += 256) {
+        for (int i = tid; i < HK * 64; i += 256) {
             const int k = i >> 6, c = i & 63;
             const float w = (c < a.Cout && k < a.head_k) ? a.head_w[(long)c * a.head_ldw + k] : 0.f;
             const bf16_t hi = f32_to_bf16(w);
             hwt[i] = hi;
-            hwt[8 * 64 + i] = f32_to_bf16(w - bf16_to_f32(hi));
+            hwt[HK * 64 + i] = f32_to_bf16(w - bf16_to_f32(hi));
         }
     }
     if (tid < 64) {
@@ -241,14 +245,15 @@ __global__ __launch_bounds__(256, 2) void conv_ws_kernel(ConvArgs a, int ntiles,
         if (HEAD) {
             // fused 1x1 head as 4 * TM MFMAs: logits[class][pixel] = sum_c w[class][c] * y[pixel][c] over this wave's 32
             // channels (two 16-channel k-steps, two weight parts), B fragments = the staged (rounded) pixels. The
-            // accumulator of lane l holds classes 4 * (l >> 5) + 0..3 of pixel l & 31; the output tensor is not stored.
+            // accumulator of lane l holds classes 4 * (l >> 5) + 0..3 of pixel l & 31 (wide head: also 8 + 4 * (l >> 5) + 0..3 in
+            // entries 4..7); the output tensor is not stored.
             int b, y0, x0; tile_coords(tile, b, y0, x0);
-            const bool arow = (lane & 31) < 8;
+            const bool arow = (lane & 31) < HK;
             uint4 ah[2], al[2];
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16_t* src = hwt + (lane & 7) * 64 + wn * 32 + s2 * 16 + 8 * fh;
-                ah[s2] = *(const uint4*)src; al[s2] = *(const uint4*)(src + 8 * 64);
+                const bf16_t* src = hwt + (lane & (HK - 1)) * 64 + wn * 32 + s2 * 16 + 8 * fh;
+                ah[s2] = *(const uint4*)src; al[s2] = *(const uint4*)(src + HK * 64);
                 if (!arow) { ah[s2] = make_uint4(0, 0, 0, 0); al[s2] = make_uint4(0, 0, 0, 0); }
             }
 #pragma unroll
@@ -267,6 +272,10 @@ __global__ __launch_bounds__(256, 2) void conv_ws_kernel(ConvArgs a, int ntiles,
                     float* hp = a.head_partial + ((long)wn * npix + ((long)b * H + py) * W + px) * a.head_k + 4 * fh;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) if (4 * fh + e < a.head_k) hp[e] = hacc[e];
+                    if (HW == 16) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) if (8 + 4 * fh + e < a.head_k) hp[8 + e] = hacc[4 + e];
+                    }
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // before the next tile's staging writes
@@ -373,10 +382,12 @@ __global__ __launch_bounds__(256, 2) void conv_ws_kernel(ConvArgs a, int ntiles,
     }
 }
 
-template <int TH, bool HEAD>
+template <int TH, int HW>
 int launch_ws(const ConvArgs& a_in, hipStream_t st) {
-    using Cfg = WsCfg<TH>;
-    auto kern = conv_ws_kernel<TH, HEAD>;
+    constexpr bool HEAD = HW != 0;
+    using Cfg = WsCfg<TH, HW == 16 ? 16 : 8>;
+    static_assert(2 * Cfg::SMEM <= 160 * 1024, "two workgroups per CU share the 160 KB of LDS");
+    auto kern = conv_ws_kernel<TH, HW>;
     ConvArgs a = a_in;
     if (a.w_elems <= 0) a.w_elems = 8 * a.w_tap_stride + (long)a.Cout * a.w_row_stride;
     static unsigned long long attr_set = 0;                      // (per instantiation: this function is a template)
@@ -418,8 +429,8 @@ int try_conv_ws(int dtype, int mode, const ConvArgs& a, hipStream_t st) {
     if (a.ksplit > 1) return 0;
     const long tiles4 = (long)a.B * cdiv(a.Ho, 4) * cdiv(a.Wo, 32);
     if (a.Wo < 32 || a.Ho < 4 || tiles4 < 1024) return 0;    // needs >= 2 tiles per workgroup to amortise the weight load
-    const bool head = a.head_partial && a.head_done && a.head_w && a.head_k >= 1 && a.head_k <= 8 && !a.mask && !a.stats && !a.pooled;
-    const int rc = head ? launch_ws<4, true>(a, st) : launch_ws<4, false>(a, st);
+    const bool head = a.head_partial && a.head_done && a.head_w && a.head_k >= 1 && a.head_k <= 16 && !a.mask && !a.stats && !a.pooled;
+    const int rc = !head ? launch_ws<4, 0>(a, st) : (a.head_k <= 8 ? launch_ws<4, 8>(a, st) : launch_ws<4, 16>(a, st));
     return rc ? rc : 1;
 }
 

@@ -98,6 +98,101 @@ __global__ __launch_bounds__(256) void fusion_grad_kernel(const float* __restric
             (float)((double)wsum[0][a] + (double)wsum[1][a] + (double)wsum[2][a] + (double)wsum[3][a]);
 }
 
+// 9 <= K <= 16 classes: fusion_grad_kernel<16> would keep 16 x 16 gradient accumulators per thread. Here two ADJACENT lanes share
+// one point; lane half h = lane & 1 owns the classes 8 h .. 8 h + 7 (those >= K are masked off), so a thread carries the 16 x 8
+// + 8 accumulators of the K = 8, V = 16 case. The softmax maximum, its sum and p_c cross the pair with one __shfl_xor(., 1)
+// each (max: order-free; sum: a + b = b + a bit for bit; p_c: one side is 0), so both lanes hold the same bits and every
+// per-class operation is the one fusion_grad_kernel does. A block covers 128 points per pass. Same partial row
+// [blk][V*K + K + 1], same two-stage fixed-order reduction (the wave butterfly leaves out distance 1: even lanes sum the lower
+// classes, odd lanes the upper ones).
+__global__ __launch_bounds__(256) void fusion_grad_wide_kernel(const float* __restrict__ x, const uint8_t* __restrict__ y, long n,
+                                                               int V, int K, const float* __restrict__ W,
+                                                               const float* __restrict__ b,
+                                                               float* __restrict__ partial /*[blk][V*K + K + 1]*/) {
+    constexpr int KH = 8, KMAX = 16;
+    __shared__ float sW[FT_MAXV * KMAX + KMAX];
+    for (int i = threadIdx.x; i < V * K + K; i += 256) sW[i] = i < V * K ? W[i] : b[i - V * K];
+    __syncthreads();
+    const int nacc = V * K + K + 1;
+    const int h = threadIdx.x & 1, k0 = KH * h;
+    const int nk = K - k0 < KH ? K - k0 : KH;                   // this lane's classes: k0 .. k0 + nk - 1 (8, or K - 8)
+    const float twoK = 2.f / (float)K;
+    float gW[FT_MAXV][KH];
+    float gb[KH];
+    float ls = 0.f;
+#pragma unroll
+    for (int v = 0; v < FT_MAXV; ++v)
+#pragma unroll
+        for (int i = 0; i < KH; ++i) gW[v][i] = 0.f;
+#pragma unroll
+    for (int i = 0; i < KH; ++i) gb[i] = 0.f;
+    for (long t = (long)blockIdx.x * 128 + (threadIdx.x >> 1); t < n; t += (long)gridDim.x * 128) {   // (both lanes of a pair: same t)
+        const float* xp = x + t * V * K + k0;
+        float z[KH];
+#pragma unroll
+        for (int i = 0; i < KH; ++i) z[i] = 0.f;
+        for (int v = 0; v < V; ++v)
+#pragma unroll
+            for (int i = 0; i < KH; ++i)
+                if (i < nk) z[i] = z[i] + sW[v * K + k0 + i] * xp[v * K + i];
+        float mx = -3.4e38f;
+#pragma unroll
+        for (int i = 0; i < KH; ++i)
+            if (i < nk) { z[i] = z[i] + sW[V * K + k0 + i]; mx = fmaxf(mx, z[i]); }
+        mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < KH; ++i) { z[i] = i < nk ? expf(z[i] - mx) : 0.f; s += z[i]; }
+        s = s + __shfl_xor(s, 1, 64);
+        const float inv = 1.f / s;
+        const int c = y[t];
+        float pc = 0.f;
+#pragma unroll
+        for (int i = 0; i < KH; ++i) { z[i] *= inv; if (k0 + i == c) pc = z[i]; }
+        pc = pc + __shfl_xor(pc, 1, 64);                        // (the other half holds 0)
+        if (c < K) {                                            // a target outside [0,K) has an all-zero one-hot: L_n = 1
+            const float den = 1.f + pc + 1e-6f;
+            if (h == 0) ls += 1.f - twoK * pc / den;
+            const float dLdp = -twoK * (1.f + 1e-6f) / (den * den);
+            float dz[KH];
+#pragma unroll
+            for (int i = 0; i < KH; ++i) dz[i] = i < nk ? dLdp * pc * ((k0 + i == c ? 1.f : 0.f) - z[i]) : 0.f;
+#pragma unroll
+            for (int v = 0; v < FT_MAXV; ++v)
+                if (v < V) {
+#pragma unroll
+                    for (int i = 0; i < KH; ++i)
+                        if (i < nk) gW[v][i] += dz[i] * xp[v * K + i];
+                }
+#pragma unroll
+            for (int i = 0; i < KH; ++i) gb[i] += dz[i];
+        } else if (h == 0) {
+            ls += 1.f;
+        }
+    }
+    // block reduction: butterfly over the 32 lanes of the same half in each wave (fixed order), then the 4 waves through LDS
+    auto half_sum = [](float v) {
+#pragma unroll
+        for (int o = 32; o > 1; o >>= 1) v += __shfl_xor(v, o, 64);
+        return v;
+    };
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __shared__ float wsum[4][FT_MAXV * KMAX + KMAX + 1];
+#pragma unroll
+    for (int v = 0; v < FT_MAXV; ++v)
+        if (v < V) {
+#pragma unroll
+            for (int i = 0; i < KH; ++i) { const float t = half_sum(gW[v][i]); if (lane < 2 && i < nk) wsum[wave][v * K + k0 + i] = t; }
+        }
+#pragma unroll
+    for (int i = 0; i < KH; ++i) { const float t = half_sum(gb[i]); if (lane < 2 && i < nk) wsum[wave][V * K + k0 + i] = t; }
+    { const float t = half_sum(ls); if (lane == 0) wsum[wave][V * K + K] = t; }
+    __syncthreads();
+    for (int a = threadIdx.x; a < nacc; a += 256)
+        partial[(long)blockIdx.x * nacc + a] =
+            (float)((double)wsum[0][a] + (double)wsum[1][a] + (double)wsum[2][a] + (double)wsum[3][a]);
+}
+
 __global__ __launch_bounds__(256) void fusion_update_kernel(const float* __restrict__ partial, int nblk, int V, int K, long n,
                                                             float* W, float* b, float* m, float* v2, double alpha,
                                                             float b1, float b2, float eps, int apply, float* grads_out,
@@ -179,6 +274,13 @@ __global__ __launch_bounds__(256) void fusion_apply_kernel(const double* __restr
 int launch_fusion_grad(const float* d_x, const uint8_t* d_y, long n, int V, int K, const float* d_W, const float* d_b,
                        float* d_workspace, long* blocks_out, hipStream_t st) {
     long blocks = (n + 255) / 256; if (blocks > FT_MAX_BLOCKS) blocks = FT_MAX_BLOCKS;
+    if (K > 8 && K <= 16) {                                      // two lanes per point: 128 points per block and pass
+        blocks = (n + 127) / 128; if (blocks > FT_MAX_BLOCKS) blocks = FT_MAX_BLOCKS;
+        *blocks_out = blocks;
+        if (blocks == 0) return MPU_OK;
+        fusion_grad_wide_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(d_x, d_y, n, V, K, d_W, d_b, d_workspace);
+        return launch_ok();
+    }
     *blocks_out = blocks;
     if (blocks == 0) return MPU_OK;                              // a rank without points in this batch
 #define MPU_FT_CASE(KK) case KK: fusion_grad_kernel<KK><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(d_x, d_y, n, V, d_W, d_b, d_workspace); break;
@@ -206,8 +308,8 @@ int mpu_fusion_train_step(const float* d_x, const uint8_t* d_y, int64_t n, int32
                           double beta1, double beta2, double eps, float* d_workspace, float* d_grads_out,
                           float* d_loss_out, void* stream) {
     MPU_REQUIRE(d_x && d_y && d_W && d_b && d_workspace, "mpu_fusion_train_step: null argument");
-    MPU_REQUIRE(n >= 1 && n_views >= 1 && n_views <= FT_MAXV && n_classes >= 1 && n_classes <= 8,
-                "mpu_fusion_train_step: need n >= 1, 1 <= views <= 16, 1 <= classes <= 8");
+    MPU_REQUIRE(n >= 1 && n_views >= 1 && n_views <= FT_MAXV && n_classes >= 1 && n_classes <= 16,
+                "mpu_fusion_train_step: need n >= 1, 1 <= views <= 16, 1 <= classes <= 16");
     MPU_REQUIRE(t == 0 || (d_adam_m && d_adam_v && t >= 1), "mpu_fusion_train_step: Adam state missing");
     hipStream_t st = (hipStream_t)stream;
     long blocks = 0;
@@ -223,8 +325,8 @@ int mpu_fusion_train_step(const float* d_x, const uint8_t* d_y, int64_t n, int32
 int mpu_fusion_grad_sums(const float* d_x, const uint8_t* d_y, int64_t n, int32_t n_views, int32_t n_classes,
                          const float* d_W, const float* d_b, float* d_workspace, double* d_sums, void* stream) {
     MPU_REQUIRE(d_W && d_b && d_workspace && d_sums && (n == 0 || (d_x && d_y)), "mpu_fusion_grad_sums: null argument");
-    MPU_REQUIRE(n >= 0 && n_views >= 1 && n_views <= FT_MAXV && n_classes >= 1 && n_classes <= 8,
-                "mpu_fusion_grad_sums: need n >= 0, 1 <= views <= 16, 1 <= classes <= 8");
+    MPU_REQUIRE(n >= 0 && n_views >= 1 && n_views <= FT_MAXV && n_classes >= 1 && n_classes <= 16,
+                "mpu_fusion_grad_sums: need n >= 0, 1 <= views <= 16, 1 <= classes <= 16");
     hipStream_t st = (hipStream_t)stream;
     long blocks = 0;
     int rc = launch_fusion_grad(d_x, d_y, (long)n, n_views, n_classes, d_W, d_b, d_workspace, &blocks, st);
@@ -237,7 +339,7 @@ int mpu_fusion_apply_sums(const double* d_sums, int32_t n_views, int32_t n_class
                           float* d_adam_m, float* d_adam_v, int64_t t, double lr, double beta1, double beta2, double eps,
                           float* d_grads_out, float* d_loss_out, void* stream) {
     MPU_REQUIRE(d_sums && d_W && d_b, "mpu_fusion_apply_sums: null argument");
-    MPU_REQUIRE(n_views >= 1 && n_views <= FT_MAXV && n_classes >= 1 && n_classes <= 8, "mpu_fusion_apply_sums: bad shape");
+    MPU_REQUIRE(n_views >= 1 && n_views <= FT_MAXV && n_classes >= 1 && n_classes <= 16, "mpu_fusion_apply_sums: bad shape");
     MPU_REQUIRE(t == 0 || (d_adam_m && d_adam_v && t >= 1), "mpu_fusion_apply_sums: Adam state missing");
     const double alpha = t >= 1 ? lr * sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t)) : 0.0;
     fusion_apply_kernel<<<1, 256, 0, (hipStream_t)stream>>>(d_sums, n_views, n_classes, d_W, d_b, d_adam_m, d_adam_v, alpha,

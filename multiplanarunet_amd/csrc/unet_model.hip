@@ -918,6 +918,16 @@ int make_run(Run& r, const mpu_unet* m, int batch, const float* params, const vo
     return MPU_OK;
 }
 
+// A handle with 9..16 classes is inference-only: the training step's head (the head_bn_* passes, HeadLoss::cw, the per-image
+// losses) and the evaluation kernels are built for 1..8 classes. Every entry point that would reach one of them asks here first,
+// before it launches or changes anything.
+constexpr int TRAIN_MAX_CLASSES = 8;
+int require_trainable(const mpu_unet* m) {
+    if (m && m->cfg.n_classes > TRAIN_MAX_CLASSES)
+        return fail(MPU_EUNSUPPORTED, "%s", "U-Net training and evaluation support 1..8 classes; 9..16 are inference-only");
+    return MPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -925,9 +935,9 @@ extern "C" {
 mpu_unet* mpu_unet_create(const mpu_unet_config* cfg) {
     if (!cfg) { fail(MPU_EINVAL, "%s", "mpu_unet_create: null config"); return nullptr; }
     const int D = cfg->depth;
-    if (cfg->n_classes < 1 || cfg->n_classes > 8 || cfg->n_channels < 1 || D < 1 || D > 6 || cfg->H < 1 || cfg->W < 1 ||
+    if (cfg->n_classes < 1 || cfg->n_classes > 16 || cfg->n_channels < 1 || D < 1 || D > 6 || cfg->H < 1 || cfg->W < 1 ||
         (cfg->H % (1 << D)) || (cfg->W % (1 << D)) || (cfg->dtype != MPU_F32 && cfg->dtype != MPU_BF16 && cfg->dtype != MPU_F32X3)) {
-        fail(MPU_EINVAL, "%s", "mpu_unet_create: unsupported configuration (need 1<=n_classes<=8, 1<=depth<=6, "
+        fail(MPU_EINVAL, "%s", "mpu_unet_create: unsupported configuration (need 1<=n_classes<=16, 1<=depth<=6, "
                                "H and W multiples of 2^depth, dtype f32|bf16|f32x3)");
         return nullptr;
     }
@@ -989,6 +999,7 @@ int mpu_unet_set_loss(mpu_unet* m, const mpu_loss_config* cfg) {
     if (cfg->kind == MPU_LOSS_FOCAL)
         MPU_REQUIRE(cfg->n_class_weights == 0 || cfg->n_class_weights == m->cfg.n_classes,
                     "mpu_unet_set_loss: class_weights needs one entry per class (or none)");
+    if (cfg->kind != MPU_LOSS_SPARSE_CE || cfg->n_class_weights != 0) RC(require_trainable(m));
     m->loss = *cfg;
     if (cfg->kind != MPU_LOSS_FOCAL) m->loss.n_class_weights = 0;
     return MPU_OK;
@@ -1065,6 +1076,7 @@ int mpu_unet_prepare_inference(const mpu_unet* m, const float* d_params, const f
 int mpu_unet_forward(const mpu_unet* m, int32_t batch, const float* d_x, const float* d_params, const void* d_packed,
                      float* d_bn_state, void* d_workspace, int32_t training, float* d_out, void* stream) {
     MPU_REQUIRE(d_x, "mpu_unet_forward: null input");
+    if (training) RC(require_trainable(m));
     Run r;
     RC(make_run(r, m, batch, d_params, d_packed, d_bn_state, nullptr, d_workspace, stream));
     return run_forward(r, d_x, training, d_out);
@@ -1075,6 +1087,7 @@ int mpu_unet_backward(const mpu_unet* m, int32_t batch, const uint8_t* d_y, cons
                       float* d_grads, float* d_loss, void* stream) {
     MPU_REQUIRE(d_y && d_sample_weight && d_grads, "mpu_unet_backward: null argument");
     MPU_REQUIRE(m && m->cfg.softmax, "mpu_unet_backward: training needs out_activation='softmax'");
+    RC(require_trainable(m));
     Run r;
     RC(make_run(r, m, batch, d_params, d_packed, d_bn_state, d_grads, d_workspace, stream));
     return run_backward(r, d_y, d_sample_weight, d_loss);
@@ -1086,6 +1099,7 @@ int mpu_unet_backward_adam(const mpu_unet* m, int32_t batch, const uint8_t* d_y,
                            double beta2, double eps, void* stream) {
     MPU_REQUIRE(d_y && d_sample_weight && d_grads && d_m && d_v, "mpu_unet_backward_adam: null argument");
     MPU_REQUIRE(m && m->cfg.softmax, "mpu_unet_backward_adam: training needs out_activation='softmax'");
+    RC(require_trainable(m));
     MPU_REQUIRE(d_step || t >= 1, "mpu_unet_backward_adam: need a device step counter or a 1-based step number");
     Run r;
     RC(make_run(r, m, batch, d_params, d_packed, d_bn_state, d_grads, d_workspace, stream));
@@ -1129,6 +1143,7 @@ int mpu_unet_backward_events(const mpu_unet* m, int32_t batch, const uint8_t* d_
                              void* stream) {
     MPU_REQUIRE(d_y && d_sample_weight && d_grads, "mpu_unet_backward_events: null argument");
     MPU_REQUIRE(m && m->cfg.softmax, "mpu_unet_backward_events: training needs out_activation='softmax'");
+    RC(require_trainable(m));
     Run r;
     RC(make_run(r, m, batch, d_params, d_packed, d_bn_state, d_grads, d_workspace, stream));
     r.ready_events = ready_events; r.n_ready = ready_events ? n_events : 0;

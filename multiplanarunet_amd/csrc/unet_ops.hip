@@ -1167,6 +1167,20 @@ __global__ __launch_bounds__(256) void head_forward_kernel(const T* __restrict__
         case 8: { constexpr int KK = 8; CALL; } break;                      \
         default: return fail(MPU_EUNSUPPORTED, "%s", "U-Net head supports 1..8 classes"); \
     }
+// 9..16 classes: the inference head only (head_forward_kernel, head_combine_kernel). The macro above also serves the training
+// head kernels, whose per-thread class arrays and loss tables stop at 8 classes, so it stays as it is.
+#define MPU_HEAD_DISPATCH_WIDE_K(K_, CALL)                                  \
+    switch (K_) {                                                           \
+        case 9: { constexpr int KK = 9; CALL; } break;                      \
+        case 10: { constexpr int KK = 10; CALL; } break;                    \
+        case 11: { constexpr int KK = 11; CALL; } break;                    \
+        case 12: { constexpr int KK = 12; CALL; } break;                    \
+        case 13: { constexpr int KK = 13; CALL; } break;                    \
+        case 14: { constexpr int KK = 14; CALL; } break;                    \
+        case 15: { constexpr int KK = 15; CALL; } break;                    \
+        case 16: { constexpr int KK = 16; CALL; } break;                    \
+        default: return fail(MPU_EUNSUPPORTED, "%s", "U-Net inference head supports 1..16 classes"); \
+    }
 // ... and over the head-kernel form of the loss (kernels.h HL_*): BODY sees constexpr int LL
 #define MPU_HEAD_DISPATCH_LK(LK_, BODY)                                     \
     switch (LK_) {                                                          \
@@ -1259,6 +1273,14 @@ int launch_head_forward(int dtype, const void* n, long M, int C, int K, const fl
     int G = 1; while (G < C / N && G < 64) G <<= 1;
     const long ppb = 256 / G;
     long blocks = (M + ppb - 1) / ppb; if (blocks > 4096) blocks = 4096;
+    if (K > 8) {                                                 // inference-only widths (the reduce-scatter variant needs K * (C / N) <= 64)
+        if (dtype == MPU_BF16) {
+            MPU_HEAD_DISPATCH_WIDE_K(K, (head_forward_kernel<bf16_t, KK><<<(unsigned)blocks, 256, 0, st>>>((const bf16_t*)n, M, C, Wh, ldw, bh, softmax, out)))
+        } else {
+            MPU_HEAD_DISPATCH_WIDE_K(K, (head_forward_kernel<float, KK><<<(unsigned)blocks, 256, 0, st>>>((const float*)n, M, C, Wh, ldw, bh, softmax, out)))
+        }
+        return launch_ok();
+    }
     const bool rs_on = env(ENV_HEAD_RS) != 0;
     if (rs_on && C == 64 && K * (C / N) <= 64) {                 // reduce-scatter variant: every lane finishes a pixel
         long rb = (M + 255) / 256; if (rb > 4096) rb = 4096;
@@ -1305,6 +1327,10 @@ __global__ __launch_bounds__(256) void head_combine_kernel(const float* __restri
 }
 int launch_head_combine(const float* partial, long M, int K, const float* bh, int softmax, float* out, hipStream_t st) {
     long rb = (M + 255) / 256; if (rb > 8192) rb = 8192;
+    if (K > 8) {
+        MPU_HEAD_DISPATCH_WIDE_K(K, (head_combine_kernel<KK><<<(unsigned)rb, 256, 0, st>>>(partial, M, bh, softmax, out)))
+        return launch_ok();
+    }
     MPU_HEAD_DISPATCH_K(K, (head_combine_kernel<KK><<<(unsigned)rb, 256, 0, st>>>(partial, M, bh, softmax, out)))
     return launch_ok();
 }

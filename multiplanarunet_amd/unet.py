@@ -45,6 +45,19 @@ METRICS = ("sparse_categorical_accuracy", "sparse_fg_recall", "sparse_fg_precisi
            "sparse_mean_fg_recall", "sparse_mean_fg_f1")
 
 
+# Class limits (include/mpunet_hip.h, mpu_unet_config): a model with up to MAX_CLASSES classes is built and predicts; training and
+# evaluation stop at TRAIN_MAX_CLASSES. The message is the library guard's (csrc/unet_model.hip: require_trainable).
+MAX_CLASSES, TRAIN_MAX_CLASSES = 16, 8
+INFERENCE_ONLY_MSG = "U-Net training and evaluation support 1..8 classes; 9..16 are inference-only"
+
+
+def require_trainable(n_classes, what):
+    """NotImplementedError for an entry point of the training / evaluation side on a model with more than TRAIN_MAX_CLASSES
+    classes: raised up front, before any launch or allocation of training state."""
+    if int(n_classes) > TRAIN_MAX_CLASSES:
+        raise NotImplementedError("%s: %s (this model has %d)" % (what, INFERENCE_ONLY_MSG, int(n_classes)))
+
+
 def mean_metric(total, count):
     """Keras Mean.result(): total / count, 0 where count == 0 (div_no_nan); a NaN total stays NaN."""
     return float(total) / float(count) if count else 0.0
@@ -130,6 +143,9 @@ class UNet:
     See mpunet/models/unet.py:26-79 for the meaning of the arguments. Extra
     keyword arguments (model_class_name, l1_reg, biased_output_layer, ...) are
     accepted and ignored, as the reference does (unet.py:41).
+
+    n_classes: 1..8 trains, evaluates and predicts; 9..16 is inference-only (predict, predict_on_batch, weight I/O): everything
+               of the training / evaluation side raises NotImplementedError up front.
 
     Additions that have no counterpart in the reference:
       dtype  : "bf16" (default; bf16 storage + MFMA, f32 accumulate), "f32" (exact-f32 MFMA: the parity mode) or
@@ -415,7 +431,12 @@ class UNet:
             raise ValueError("expected input [B,%d,%d,%d], got %s" % (self.img_shape + (tuple(X.shape),)))
         return X
 
+    def _require_trainable(self, what):
+        require_trainable(self.n_classes, what)
+
     def _forward(self, X, training, out=None):
+        if training:
+            self._require_trainable("training-mode forward")
         if self.device.type != "cuda":
             raise _lib.MpuError("UNet needs a HIP device (MI355X); there is no CPU execution path")
         B = X.shape[0]
@@ -552,6 +573,8 @@ class UNet:
         """
         opt_name, opt_kw = _resolve_optimizer(optimizer, optimizer_kwargs)     # (all three raise before anything is changed)
         metric_names = _resolve_metrics(metrics)
+        if metric_names:
+            self._require_trainable("compile(metrics=...)")
         same = opt_name == self.optimizer_name  # another optimizer starts from its own defaults
         new_kw = dict(self.optimizer_kwargs if same else _OPTIMIZERS[opt_name][1])
         new_kw.update(opt_kw)
@@ -563,6 +586,7 @@ class UNet:
                     raise NotImplementedError("one loss per model (the reference's U-Net has one output)")
                 lname = loss[0] if isinstance(loss[0], str) else type(loss[0]).__name__
             if lname in _CUSTOM_LOSSES:
+                self._require_trainable("compile(loss=%r)" % lname)
                 self._set_loss(lname, dict(loss_kwargs or {}))
             elif "sparsecategoricalcrossentropy" in lname.lower().replace("_", ""):
                 self._set_loss(None, {})
@@ -720,6 +744,7 @@ class UNet:
         on the current stream when that part of the gradient buffer is final (data-parallel overlap).
         adam: (t, step_dev) -- ALSO apply the optimizer inside the same library call (mpu_unet_backward_adam: the
         update of the deep levels' parameters runs beside the weight gradients of the high-resolution levels)."""
+        self._require_trainable("forward_backward")
         X = self._as_input(x)
         B = X.shape[0]
         if not torch.is_tensor(y):
@@ -820,6 +845,7 @@ class UNet:
         DEVICE (`mp train` reads it once per epoch, pipeline.TrainPipeline). warmup=False: capture only (a re-capture after
         a learning-rate change -- the rate is a kernel argument of the captured launches); `replay.warmup_ran` tells.
         """
+        self._require_trainable("make_graphed_train_step")
         if self._grad_hook is not None:
             raise NotImplementedError("graphed train step is single-GPU (gradient all-reduce is eager)")
         for t in (x, y):
@@ -897,6 +923,7 @@ class UNet:
 
     def train_step(self, x, y, sample_weight=None, want_loss=True):
         """One Model.fit inner step. Returns the per-pixel loss [B,H*W] (device) or None."""
+        self._require_trainable("train_step")
         hook = self._grad_hook
         if hook is None and not self.l2_reg and self._plain_adam():     # single GPU, no l2 term: backward + optimizer as one library call
             self._ensure_slots()
@@ -919,6 +946,7 @@ class UNet:
         """Scalar Keras reports for the step: mean of the weighted per-pixel loss (+ the l2 term when l2_reg is set). With compiled
         metrics: [loss, m1, ...] of THIS batch in the order of metrics_names (Keras' default reset_metrics=True: the state holds
         this batch alone afterwards)."""
+        self._require_trainable("train_on_batch")
         self.reset_metrics()
         loss = self._batch_loss(x, y, sample_weight)
         if not self._metric_names:
@@ -947,6 +975,7 @@ class UNet:
         device accumulators, no host read: the compiled loss of the batch by mpu_eval_loss (csrc/eval_loss.hip) -- acc[0] += mean
         over the batch of w_b * L_b, acc[1] += 1; loss_out f32 [B] receives w_b * L_b -- and the compiled metrics by
         mpu_train_metrics_update into metrics_state (unweighted). The Validation callback feeds its batches through here."""
+        self._require_trainable("evaluation_update")
         K = int(self.n_classes)
         B = int(probs.shape[0])
         p = probs.reshape(B, -1, K)
@@ -1045,6 +1074,7 @@ class UNet:
         calls before. Nothing of the model changes: no gradient, no optimizer state, no moving statistic, and not the metric
         state of the running training epoch (the forward refreshes the folded BatchNorm coefficients at the tail of `packed`
         after a weight change, exactly as predict_on_batch does)."""
+        self._require_trainable("test_on_batch")
         res = self._evaluate_chunks(x, y, sample_weight, max(1, int(x.shape[0])), reset_metrics)
         return self._evaluation_output(res, return_dict)
 
@@ -1052,12 +1082,14 @@ class UNet:
         """Keras Model.evaluate on arrays: test_on_batch's computation in chunks of batch_size. The loss is the Mean over the batches
         weighted by batch size (= the mean over the images of w_b * L_b; the cross-entropy: over all pixels), the metrics follow
         the accumulator semantics of compile()'s docstring over the chunks."""
+        self._require_trainable("evaluate")
         res = self._evaluate_chunks(x, y, sample_weight, 32 if batch_size is None else int(batch_size), True)
         return self._evaluation_output(res, return_dict)
 
     def fit(self, data, steps_per_epoch, epochs=1, callbacks=None, initial_epoch=0, verbose=0, **kwargs):
         """Minimal Model.fit over an iterator of (x, y, w) batches (trainer.py:246-257). The compiled metrics run over the whole
         epoch (reset at its start); `verbose` reports them beside the loss."""
+        self._require_trainable("fit")
         it = iter(data)
         history = []
         for ep in range(initial_epoch, epochs):
