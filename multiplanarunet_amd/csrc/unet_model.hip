@@ -30,8 +30,25 @@ struct Tensor {                 // one entry of the flat parameter / BN-state ta
     int lshape[4];              // logical Keras shape
 };
 
-struct Conv { int mode, Cin, Cout; long w, b; long wf, wd; int lCin, lCout; };        // offsets
-struct BN { int C; long g, b, mm, mv; long st; };                    // st: mean,invstd,scale,shift (4*C)
+// Activation buffers of the workspace: one id per buffer = role * T_SLOTS + k (k = encoder level i or up block j; 0 for the
+// single ones). Plan::act resolves an id to its offset; the layer table and the passes name a buffer by nothing else.
+enum { T_XIN, T_C1, T_C2, T_N, T_P, T_DSKIP, T_C1B, T_C2B, T_NB, T_U1, T_N1, T_C2U, T_C3U, T_N2, T_ROLES };
+constexpr int T_SLOTS = 8;
+constexpr int T(int role, int k = 0) { return role * T_SLOTS + k; }
+
+// The layer table: one row per conv and per BatchNorm, in Keras creation order (built by mpu_unet_create)
+struct Conv {
+    int mode, Cin, Cout; long w, b; long wf, wd; int lCin, lCout;    // offsets
+    int lvl, lvl_in;            // resolution level of the output / of the input (the up-conv reads the level below)
+    int in0, C0, in1, C1;       // input tensor(s) and their channels; in1 = -1, C1 = 0 except for the concat conv of an up block
+    int out;                    // output tensor (-1: the head writes the probabilities)
+    int bn;                     // the BatchNorm that follows it, or -1
+    int block;                  // gradient-ready point of its block (mpu_unet_grad_ready_points)
+};
+struct BN {
+    int C; long g, b, mm, mv; long st;                               // st: mean,invstd,scale,shift (4*C)
+    int conv, lvl, x, y, pooled;    // the conv in front of it, its level, input (= that conv's out) and output tensors; pooled: the
+};                                  // 2x2 max pooling of y (encoder levels), or -1
 
 }  // namespace
 
@@ -53,15 +70,12 @@ struct mpu_unet {
     mutable int head_fused_fwd = 0;
     mpu_loss_config loss{};                  // mpu_unet_set_loss; kind 0 = MPU_LOSS_SPARSE_CE: everything as without one
 
-    // indices into conv / bn
+    // indices into conv
     int enc_c1(int i) const { return 2 * i; }
     int enc_c2(int i) const { return 2 * i + 1; }
     int bot_c1() const { return 2 * cfg.depth; }
     int bot_c2() const { return 2 * cfg.depth + 1; }
     int up_c(int j, int k) const { return 2 * cfg.depth + 2 + 3 * j + k; }       // k = 0,1,2
-    int enc_bn(int i) const { return i; }
-    int bot_bn() const { return cfg.depth; }
-    int up_bn(int j, int k) const { return cfg.depth + 1 + 2 * j + k; }          // k = 0,1
 };
 
 namespace {
@@ -74,10 +88,13 @@ void add_tensor(mpu_unet* m, const std::string& name, int kind, long off, std::i
     m->tensors.push_back(t);
 }
 
-void add_conv(mpu_unet* m, const std::string& name, int mode, int Cin, int Cout, int lCin, int lCout) {
+void add_conv(mpu_unet* m, const std::string& name, int mode, int Cin, int Cout, int lCin, int lCout, int lvl, int block, int in0,
+              int out, int in1 = -1) {
     const int esz = 1;
     const int k = mode == UPCONV2 ? 2 : (mode == CONV1 ? 1 : 3);
     Conv c; c.mode = mode; c.Cin = Cin; c.Cout = Cout; c.lCin = lCin; c.lCout = lCout;
+    c.lvl = lvl; c.lvl_in = mode == UPCONV2 ? lvl + 1 : lvl; c.block = block; c.bn = -1;
+    c.in0 = in0; c.in1 = in1; c.out = out; c.C0 = in1 < 0 ? Cin : Cin / 2; c.C1 = Cin - c.C0;      // (concat: two equal halves)
     c.w = m->n_params; m->n_params += (long)k * k * Cin * Cout;
     c.b = m->n_params; m->n_params += Cout;
     add_tensor(m, name + "/kernel", 0, c.w, {k, k, Cin, Cout}, {k, k, lCin, lCout});
@@ -91,8 +108,11 @@ void add_conv(mpu_unet* m, const std::string& name, int mode, int Cin, int Cout,
     m->conv.push_back(c);
 }
 
-void add_bn(mpu_unet* m, const std::string& name, int C, int lC) {
+// (follows the conv it normalises: creation order)
+void add_bn(mpu_unet* m, const std::string& name, int C, int lC, int y, int pooled = -1) {
     BN b; b.C = C;
+    Conv& c = m->conv.back();
+    c.bn = (int)m->bn.size(); b.conv = (int)m->conv.size() - 1; b.lvl = c.lvl; b.x = c.out; b.y = y; b.pooled = pooled;
     b.g = m->n_params; m->n_params += C;
     b.b = m->n_params; m->n_params += C;
     b.mm = m->n_state; m->n_state += C;
@@ -109,10 +129,7 @@ void add_bn(mpu_unet* m, const std::string& name, int C, int lC) {
 
 // ---- workspace plan --------------------------------------------------------
 struct Plan {
-    long xin;
-    std::vector<long> c1, c2, n, p, dskip;          // encoder levels
-    long c1b, c2b, nb;
-    std::vector<long> u1, n1, c2u, c3u, n2;         // up levels
+    long act[T_ROLES * T_SLOTS];                    // activation buffers by tensor id (T(role, k))
     long loss_scratch = -1, loss_coef = -1;         // a per-image loss (mpu_unet_set_loss): f64 sums / the (a, c) table; else absent
     long probs, loss_mean, gA, gB, partial, partial_floats, partial2, wpartial, wpartial_floats, cpartial, cpartial_floats, coeffs, stats, total;
     std::vector<long> wscratch;                     // per conv: float offset of its weight-gradient scratch inside wpartial
@@ -130,18 +147,15 @@ Plan make_plan(const mpu_unet* m, int B) {
     Plan P; long off = 0;
     auto take = [&](long bytes) { long o = off; off += (bytes + 255) / 256 * 256; return o; };
     auto act = [&](int lvl, int C) { return take((long)B * (m->cfg.H >> lvl) * (m->cfg.W >> lvl) * C * esz); };
-    P.xin = act(0, m->cin_pad);
+    for (long& a : P.act) a = -1;
+    P.act[T(T_XIN)] = act(0, m->cin_pad);
     for (int i = 0; i < D; ++i) {
-        P.c1.push_back(act(i, m->F[i])); P.c2.push_back(act(i, m->F[i])); P.n.push_back(act(i, m->F[i]));
-        P.p.push_back(act(i + 1, m->F[i])); P.dskip.push_back(act(i, m->F[i]));
+        for (int role : {T_C1, T_C2, T_N}) P.act[T(role, i)] = act(i, m->F[i]);
+        P.act[T(T_P, i)] = act(i + 1, m->F[i]); P.act[T(T_DSKIP, i)] = act(i, m->F[i]);
     }
-    P.c1b = act(D, m->F[D]); P.c2b = act(D, m->F[D]); P.nb = act(D, m->F[D]);
-    for (int j = 0; j < D; ++j) {
-        const int lvl = D - 1 - j;
-        P.u1.push_back(act(lvl, m->F[lvl])); P.n1.push_back(act(lvl, m->F[lvl]));
-        P.c2u.push_back(act(lvl, m->F[lvl])); P.c3u.push_back(act(lvl, m->F[lvl]));
-        P.n2.push_back(act(lvl, m->F[lvl]));
-    }
+    for (int role : {T_C1B, T_C2B, T_NB}) P.act[T(role)] = act(D, m->F[D]);
+    for (int j = 0; j < D; ++j)
+        for (int role : {T_U1, T_N1, T_C2U, T_C3U, T_N2}) P.act[T(role, j)] = act(D - 1 - j, m->F[D - 1 - j]);
     const long M0 = (long)B * m->cfg.H * m->cfg.W;
     P.probs = take(M0 * m->cfg.n_classes * 4);
     P.loss_mean = take(16);                          // the last backward pass's mean weighted per-pixel loss (one float)
@@ -152,12 +166,8 @@ Plan make_plan(const mpu_unet* m, int B) {
     }
     P.gA = take(gmax * esz); P.gB = take(gmax * esz);   // (every conv has its own dz buffer below: Plan::dz)
     P.dz.assign(m->conv.size(), -1);
-    for (size_t i = 0; i < m->conv.size(); ++i) {
-        if (m->conv[i].mode == CONV1) continue;
-        const int nenc = 2 * D;
-        const int l = (int)i < nenc ? (int)i / 2 : ((int)i < nenc + 2 ? D : D - 1 - ((int)i - nenc - 2) / 3);
-        P.dz[i] = act(l, m->conv[i].Cout);
-    }
+    for (size_t i = 0; i < m->conv.size(); ++i)
+        if (m->conv[i].mode != CONV1) P.dz[i] = act(m->conv[i].lvl, m->conv[i].Cout);
     long pe = (long)RED_MAX_BLOCKS * 2 * m->cmax;
     const long he = (long)HEAD_BWD_MAX_BLOCKS * (m->head_C * m->cfg.n_classes + m->cfg.n_classes + 1);
     if (he > pe) pe = he;
@@ -169,36 +179,24 @@ Plan make_plan(const mpu_unet* m, int B) {
     // second-stage reductions are deferred and run batched (flush_wgrad_reduces); sized exactly per layer.
     long we = 0;
     {
-        auto level_of = [&](size_t i) -> int {          // output resolution level of conv i (creation order)
-            const int nenc = 2 * D;
-            if ((int)i < nenc) return (int)i / 2;
-            if ((int)i < nenc + 2) return D;
-            const int j = ((int)i - nenc - 2) / 3;
-            return j < D ? D - 1 - j : 0;
-        };
         P.wscratch.assign(m->conv.size(), 0);
         for (size_t i = 0; i < m->conv.size(); ++i) {
             const Conv& c = m->conv[i];
             if (c.mode == CONV1) continue;
-            const int l = level_of(i);
-            const bool concat = c.mode == CONV3 && (int)i >= 2 * D + 2 && ((int)i - 2 * D - 2) % 3 == 1;
-            const int C0 = concat ? c.Cin / 2 : c.Cin, C1 = concat ? c.Cin / 2 : 0;
             P.wscratch[i] = we;
             // (dtype "bf16x3": the weight gradient runs on the bf16 kernels over three plane pairs = a batch of 3 B)
-            we += wgrad_scratch_need(m->x3 ? MPU_BF16 : m->cfg.dtype, c.mode, m->x3 ? 3 * B : B, m->cfg.H >> l, m->cfg.W >> l, C0, C1,
-                                     c.Cout, i == 0 ? c.lCin : 0);
+            we += wgrad_scratch_need(m->x3 ? MPU_BF16 : m->cfg.dtype, c.mode, m->x3 ? 3 * B : B, m->cfg.H >> c.lvl, m->cfg.W >> c.lvl,
+                                     c.C0, c.C1, c.Cout, i == 0 ? c.lCin : 0);
         }
         if (m->x3) {
             P.x3x0.assign(m->conv.size(), -1); P.x3x1.assign(m->conv.size(), -1); P.x3dz.assign(m->conv.size(), -1);
             for (size_t i = 0; i < m->conv.size(); ++i) {
                 const Conv& c = m->conv[i];
                 if (c.mode == CONV1) continue;
-                const int l = level_of(i), li = c.mode == UPCONV2 ? l + 1 : l;      // (the up-conv reads the level below)
-                const bool concat = c.mode == CONV3 && (int)i >= 2 * D + 2 && ((int)i - 2 * D - 2) % 3 == 1;
-                const long pin = (long)B * (m->cfg.H >> li) * (m->cfg.W >> li), pout = (long)B * (m->cfg.H >> l) * (m->cfg.W >> l);
-                const int C0 = concat ? c.Cin / 2 : c.Cin;
-                P.x3x0[i] = take(3 * pin * C0 * 2);
-                if (concat) P.x3x1[i] = take(3 * pin * (c.Cin - C0) * 2);
+                const long pin = (long)B * (m->cfg.H >> c.lvl_in) * (m->cfg.W >> c.lvl_in);
+                const long pout = (long)B * (m->cfg.H >> c.lvl) * (m->cfg.W >> c.lvl);
+                P.x3x0[i] = take(3 * pin * c.C0 * 2);
+                if (c.in1 >= 0) P.x3x1[i] = take(3 * pin * c.C1 * 2);
                 P.x3dz[i] = take(3 * pout * c.Cout * 2);
             }
         }
@@ -243,12 +241,15 @@ struct Run {
     const mpu_unet* m; int B; hipStream_t st; unsigned char* ws; Plan P;
     const float* params; const unsigned char* packed; float* state; float* grads;
     void* const* ready_events = nullptr; int n_ready = 0;        // gradient-ready points (mpu_unet_backward_events)
-    mutable ReduceQueue rq;                                      // deferred weight-gradient reductions (one launch per flush)
-    mutable WgradGroup grp;                                      // deferred weight-gradient kernels (grouped launches at the end)
-    mutable std::vector<char> late;                              // per conv: its weight gradient sits in the wgrad_taps group (final only after that launch)
+    ReduceQueue rq;                                              // deferred weight-gradient reductions (one launch per flush)
+    WgradGroup grp;                                              // deferred weight-gradient kernels (grouped launches at the end)
+    std::vector<char> late;                                      // per conv: its weight gradient sits in the wgrad_taps group (final only after that launch)
     bool group = false;
     int esz;
     void* at(long off) const { return ws + off; }
+    void* t(int id) const { return id < 0 ? nullptr : ws + P.act[id]; }          // activation buffer by tensor id
+    void* dz(size_t ci) const { return ws + P.dz[ci]; }                          // every conv's dz lives in its own buffer until the pass ends
+    long pix(int lvl) const { return (long)B * (m->cfg.H >> lvl) * (m->cfg.W >> lvl); }
     const void* wf(const Conv& c) const { return packed + c.wf * esz; }
     const void* wd(const Conv& c) const { return packed + c.wd * esz; }
     float* stat(const BN& b, int k) const { return (float*)(ws + P.stats) + b.st + (long)k * b.C; }
@@ -256,28 +257,53 @@ struct Run {
     long long* acc_b(const BN& b) const { return (long long*)(ws + P.bnacc) + P.bnacc_b[&b - &m->bn[0]]; }
     long long* acc_db(size_t ci) const { return (long long*)(ws + P.bnacc) + P.dbacc[ci]; }
     bool acc_mode = false;                                       // fused BatchNorm sums into fixed-point accumulators (MPU_BN_ATOMIC)
-    mutable DbAccTable dbq;                                      // dtype "bf16x3": bias gradients waiting in their accumulators
-    mutable std::vector<char> x3_presplit;                       //   per conv: its input planes were written by the pass's first launch
-    mutable std::vector<char> x3_two;                            //   per conv: two stored planes (hi | lo): its weight gradient is a wgrad_taps job
+    DbAccTable dbq;                                              // dtype "bf16x3": bias gradients waiting in their accumulators
+    std::vector<char> x3_presplit;                               //   per conv: its input planes were written by the pass's first launch
+    std::vector<char> x3_two;                                    //   per conv: two stored planes (hi | lo): its weight gradient is a wgrad_taps job
 };
 
 #define RC(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
-// algorithmic FLOPs of one pass over conv `c` at its OUTPUT resolution level `lvl`
+// algorithmic FLOPs of one pass over conv `c` at its OUTPUT resolution level
 // (2*M*N*K with the logical channel counts; the 2x2 up-conv counted at output resolution)
-double conv_flops(const Run& r, const Conv& c, int lvl, int n_cnt_logical = -1) {
-    const double M = (double)r.B * (r.m->cfg.H >> lvl) * (r.m->cfg.W >> lvl);
+double conv_flops(const Run& r, const Conv& c) {
     const int taps = c.mode == UPCONV2 ? 4 : (c.mode == CONV1 ? 1 : 9);
-    return 2.0 * M * taps * c.lCin * c.lCout;
+    return 2.0 * (double)r.pix(c.lvl) * taps * c.lCin * c.lCout;
+}
+
+// test aid: report a launch to the tap -- the one writer of mpu_launch_info (kinds 0-2: the convs; 3-7: see tap_aux)
+void tap(const Run& r, int kind, int index, int mode, int lvl, int C0, int C1, int Cout, const void* in0, const void* in1, const void* dz,
+         const void* mask, const void* out, long w_off, long b_off, int n_off = 0, int n_cnt = 0, int relu = 0,
+         const void* aux0 = nullptr, const void* aux1 = nullptr) {
+    if (!r.m->tap) return;
+    mpu_launch_info li{};
+    li.kind = kind; li.conv_index = index; li.mode = mode; li.dtype = r.m->cfg.dtype;
+    li.B = r.B; li.H = r.m->cfg.H >> lvl; li.W = r.m->cfg.W >> lvl; li.C0 = C0; li.C1 = C1; li.Cout = Cout;
+    li.n_off = n_off; li.n_cnt = n_cnt; li.relu = relu;
+    li.in0 = in0; li.in1 = in1; li.dz = dz; li.mask = mask; li.out = out; li.w_off = w_off; li.b_off = b_off;
+    li.aux0 = aux0; li.aux1 = aux1;
+    r.m->tap(r.m->tap_user, &li);
+}
+// ... a conv launch of layer `c` (kind 0 forward, 1 data gradient, 2 weight gradient) at level `lvl`
+void tap_conv(const Run& r, int kind, const Conv& c, int lvl, int C0, int C1, const void* in0, const void* in1, const void* dz,
+              const void* mask, const void* out, int n_off, int n_cnt, int relu) {
+    tap(r, kind, (int)(&c - &r.m->conv[0]), c.mode, lvl, C0, C1, c.Cout, in0, in1, dz, mask, out, c.w, c.b, n_off, n_cnt, relu);
+}
+// ... a non-convolution launch (kinds 3-7 of mpu_launch_info)
+void tap_aux(const Run& r, int kind, int index, int lvl, int C0, int Cout, const void* in0, const void* in1, const void* dz,
+             const void* mask, const void* out, long w_off, long b_off, const void* aux0 = nullptr, const void* aux1 = nullptr) {
+    tap(r, kind, index, 0, lvl, C0, 0, Cout, in0, in1, dz, mask, out, w_off, b_off, 0, 0, 0, aux0, aux1);
 }
 
 // fused head request of the last conv (inference): weights, class count, scratch for the partial logits [2][M][k]
 struct HeadFuse { const float* w; int k, ldw; float* partial; int* done; };
 
-int conv_fwd(const Run& r, const Conv& c, const void* in0, int C0, const void* in1, int C1, void* out, int lvl,
-             const float* post_scale = nullptr, const float* post_shift = nullptr, int* stats_rows = nullptr,
-             void* pooled = nullptr, int* pooled_done = nullptr, const HeadFuse* head = nullptr, long long* stats_acc = nullptr) {
+// forward of conv `c` on the inputs the layer table names, into `out`
+int conv_fwd(const Run& r, const Conv& c, void* out, const float* post_scale = nullptr, const float* post_shift = nullptr,
+             int* stats_rows = nullptr, void* pooled = nullptr, int* pooled_done = nullptr, const HeadFuse* head = nullptr,
+             long long* stats_acc = nullptr) {
     ConvArgs a;
+    const void* in0 = r.t(c.in0); const void* in1 = r.t(c.in1);
     const bool fused_head = env(ENV_FUSED_HEAD) != 0;   // inference: 1x1 head out of the last conv's epilogue (partial logits)
     if (head && head->done) *head->done = 0;
     if (head && fused_head && head->done) {
@@ -292,34 +318,30 @@ int conv_fwd(const Run& r, const Conv& c, const void* in0, int C0, const void* i
     a.stats = stats_rows ? (float*)r.at(r.P.partial) : nullptr; a.stats_rows = stats_rows; a.stats_cap = r.P.partial_floats;
     if (stats_rows && stats_acc) { a.stats_acc = stats_acc; a.stats_scale[0] = BN_ACC_F[0]; a.stats_scale[1] = BN_ACC_F[1]; }
     a.bn_x = nullptr; a.bn_mean = nullptr; a.bn_invstd = nullptr;
-    a.flops = conv_flops(r, c, lvl); a.w_elems = 0;
+    a.flops = conv_flops(r, c); a.w_elems = 0;
     a.partial = r.P.cpartial_floats ? (float*)r.at(r.P.cpartial) : nullptr; a.partial_cap = r.P.cpartial_floats; a.ksplit = 1;
     a.post_scale = post_scale; a.post_shift = post_shift;
-    a.in0 = in0; a.in1 = in1; a.C0 = C0; a.C1 = C1;
+    a.in0 = in0; a.in1 = in1; a.C0 = c.C0; a.C1 = c.C1;
     a.w = r.wf(c); a.w_tap_stride = (long)c.Cin * c.Cout; a.w_row_stride = c.Cin;
     a.bias = r.params + c.b; a.mask = nullptr; a.out = out;
-    a.B = r.B; a.Ho = r.m->cfg.H >> lvl; a.Wo = r.m->cfg.W >> lvl; a.Cout = c.Cout; a.relu = 1;
+    a.B = r.B; a.Ho = r.m->cfg.H >> c.lvl; a.Wo = r.m->cfg.W >> c.lvl; a.Cout = c.Cout; a.relu = 1;
     a.x3 = r.m->x3;
     const int rc = launch_conv(r.m->cfg.dtype, c.mode, a, r.st);
-    if (!rc && r.m->tap && !post_scale) {
-        mpu_launch_info li{};
-        li.kind = 0; li.conv_index = (int)(&c - &r.m->conv[0]); li.mode = c.mode; li.dtype = r.m->cfg.dtype;
-        li.B = a.B; li.H = a.Ho; li.W = a.Wo; li.C0 = C0; li.C1 = C1; li.Cout = c.Cout; li.n_off = 0; li.n_cnt = c.Cin; li.relu = 1;
-        li.in0 = in0; li.in1 = in1; li.dz = nullptr; li.mask = nullptr; li.out = out; li.w_off = c.w; li.b_off = c.b;
-        r.m->tap(r.m->tap_user, &li);
-    }
+    if (!rc && !post_scale) tap_conv(r, 0, c, c.lvl, c.C0, c.C1, in0, in1, nullptr, nullptr, out, 0, c.Cin, 1);
     return rc;
 }
 
-// data gradient of conv `c` w.r.t. input channels [n_off, n_off + n_cnt); out_lvl = resolution of the result
-// bn (optional): the output is the dn of that BatchNorm (input bn_x); the epilogue then also produces the partial sums
+// data gradient of conv `c` (dz: its own buffer) w.r.t. input channels [n_off, n_off + n_cnt), at the conv's input level
+// bn (optional): the output is the dn of that BatchNorm; the epilogue then also produces the partial sums
 // of its backward pass and *bn_rows (> 0) tells bn_bwd to skip the column reduction (column-major layout).
-int conv_dgrad(const Run& r, const Conv& c, const void* dz, const void* mask, void* out, int out_lvl,
-               int n_off, int n_cnt, const BN* bn = nullptr, const void* bn_x = nullptr, int* bn_rows = nullptr) {
+int conv_dgrad(const Run& r, const Conv& c, const void* mask, void* out, int n_off, int n_cnt, const BN* bn = nullptr,
+               int* bn_rows = nullptr) {
     ConvArgs a;
+    const void* dz = r.dz(&c - &r.m->conv[0]);
+    const void* bn_x = bn ? r.t(bn->x) : nullptr;
     const bool fused_bwd = env(ENV_FUSED_BN_BWD_CONV) != 0;
     if (bn_rows) *bn_rows = 0;
-    const bool want = fused_bwd && bn && bn_x && bn_rows && !mask;
+    const bool want = fused_bwd && bn && bn_rows && !mask;
     a.stats = want ? (float*)r.at(r.P.partial) : nullptr; a.stats_rows = want ? bn_rows : nullptr;
     a.stats_cap = want ? r.P.partial_floats : 0;
     a.bn_x = want ? bn_x : nullptr; a.bn_mean = want ? r.stat(*bn, 0) : nullptr; a.bn_invstd = want ? r.stat(*bn, 1) : nullptr;
@@ -330,45 +352,17 @@ int conv_dgrad(const Run& r, const Conv& c, const void* dz, const void* mask, vo
     a.w = (const unsigned char*)r.wd(c) + (long)n_off * c.Cout * r.esz;
     a.w_tap_stride = (long)c.Cin * c.Cout; a.w_row_stride = c.Cout;
     a.bias = nullptr; a.mask = mask; a.out = out;
-    a.B = r.B; a.Ho = r.m->cfg.H >> out_lvl; a.Wo = r.m->cfg.W >> out_lvl; a.Cout = n_cnt; a.relu = 0;
+    a.B = r.B; a.Ho = r.m->cfg.H >> c.lvl_in; a.Wo = r.m->cfg.W >> c.lvl_in; a.Cout = n_cnt; a.relu = 0;
     // the data gradient costs the forward's FLOPs (at the conv's own output level), pro rata of the slice
-    a.flops = conv_flops(r, c, c.mode == UPCONV2 ? out_lvl - 1 : out_lvl) * ((double)n_cnt / c.Cin);
+    a.flops = conv_flops(r, c) * ((double)n_cnt / c.Cin);
     a.x3 = r.m->x3;
     const int rc = launch_conv(r.m->cfg.dtype, c.mode == UPCONV2 ? CONV3S2 : CONV3, a, r.st);
-    if (!rc && r.m->tap) {
-        mpu_launch_info li{};
-        li.kind = 1; li.conv_index = (int)(&c - &r.m->conv[0]); li.mode = c.mode; li.dtype = r.m->cfg.dtype;
-        li.B = a.B; li.H = a.Ho; li.W = a.Wo; li.C0 = c.Cout; li.C1 = 0; li.Cout = c.Cout; li.n_off = n_off; li.n_cnt = n_cnt;
-        li.relu = 0; li.in0 = nullptr; li.in1 = nullptr; li.dz = dz; li.mask = mask; li.out = out; li.w_off = c.w; li.b_off = c.b;
-        r.m->tap(r.m->tap_user, &li);
-    }
+    if (!rc) tap_conv(r, 1, c, c.lvl_in, c.Cout, 0, nullptr, nullptr, dz, mask, out, n_off, n_cnt, 0);
     return rc;
 }
 
-// The tensors the weight gradient of conv ci reads as its input (what run_backward passes to conv_wgrad; checked there)
-struct WgradIn { const void* x0; int C0; const void* x1; int C1; long pin; int lvl_out; };
-WgradIn wgrad_inputs(const Run& r, int ci) {
-    const mpu_unet* m = r.m; const int D = m->cfg.depth; const Plan& P = r.P;
-    WgradIn w{nullptr, 0, nullptr, 0, 0, 0};
-    int lvl_in;
-    if (ci < 2 * D) {
-        const int i = ci / 2; lvl_in = i;
-        if (ci % 2 == 0) { w.x0 = i > 0 ? r.at(P.p[i - 1]) : r.at(P.xin); w.C0 = i > 0 ? m->F[i - 1] : m->cin_pad; }
-        else { w.x0 = r.at(P.c1[i]); w.C0 = m->F[i]; }
-    } else if (ci == 2 * D) { w.x0 = D > 0 ? r.at(P.p[D - 1]) : r.at(P.xin); w.C0 = D > 0 ? m->F[D - 1] : m->cin_pad; lvl_in = D; }
-    else if (ci == 2 * D + 1) { w.x0 = r.at(P.c1b); w.C0 = m->F[D]; lvl_in = D; }
-    else {
-        const int j = (ci - 2 * D - 2) / 3, k = (ci - 2 * D - 2) % 3, lvl = D - 1 - j, f = m->F[lvl];
-        if (k == 0) { w.x0 = j > 0 ? r.at(P.n2[j - 1]) : r.at(P.nb); w.C0 = j > 0 ? m->F[lvl + 1] : m->F[D]; lvl_in = lvl + 1; }
-        else if (k == 1) { w.x0 = r.at(P.n[lvl]); w.C0 = f; w.x1 = r.at(P.n1[j]); w.C1 = f; lvl_in = lvl; }
-        else { w.x0 = r.at(P.c2u[j]); w.C0 = f; lvl_in = lvl; }
-    }
-    w.pin = (long)r.B * (m->cfg.H >> lvl_in) * (m->cfg.W >> lvl_in);
-    w.lvl_out = (ci >= 2 * D + 2 && (ci - 2 * D - 2) % 3 == 0) ? lvl_in - 1 : lvl_in;      // (the up-conv writes the level above its input)
-    return w;
-}
 // dtype "bf16x3": the bf16 planes of every conv's input in ONE launch at the start of the backward pass
-int x3_presplit_inputs(const Run& r) {
+int x3_presplit_inputs(Run& r) {
     const mpu_unet* m = r.m;
     Split3Table t;
     r.x3_presplit.assign(m->conv.size(), 0);
@@ -381,20 +375,21 @@ int x3_presplit_inputs(const Run& r) {
         for (size_t ci = 1; ci < m->conv.size(); ++ci) {
             const Conv& c = m->conv[ci];
             if (c.mode == CONV1) continue;
-            const WgradIn w = wgrad_inputs(r, (int)ci);
-            const int Ho = m->cfg.H >> w.lvl_out, Wo = m->cfg.W >> w.lvl_out;
             ++njobs;
-            if (wgrad_taps_plan(MPU_BF16, c.mode, 3 * r.B, Ho, Wo, w.C0, w.C1, c.Cout, true).use) { r.x3_two[ci] = 1; ++ntaps; }
+            if (wgrad_taps_plan(MPU_BF16, c.mode, 3 * r.B, m->cfg.H >> c.lvl, m->cfg.W >> c.lvl, c.C0, c.C1, c.Cout, true).use) {
+                r.x3_two[ci] = 1; ++ntaps;
+            }
         }
         if (ntaps > TAPS_GROUP_MAX || njobs + 1 >= REDUCE_MAX_JOBS) r.x3_two.assign(m->conv.size(), 0);
     }
     for (size_t ci = 0; ci < m->conv.size(); ++ci) {
-        if (m->conv[ci].mode == CONV1 || r.P.x3x0[ci] < 0) continue;
-        const WgradIn w = wgrad_inputs(r, (int)ci);
+        const Conv& c = m->conv[ci];
+        if (c.mode == CONV1 || r.P.x3x0[ci] < 0) continue;
         if (t.n + 2 > SPLIT3_MAX_JOBS) break;                    // (the rest is split layer by layer in conv_wgrad)
         const int order = r.x3_two[ci] ? 2 : 0;
-        t.job[t.n++] = Split3Job{(const float*)w.x0, (uint16_t*)r.at(r.P.x3x0[ci]), w.pin * w.C0, 0, order};
-        if (w.x1) t.job[t.n++] = Split3Job{(const float*)w.x1, (uint16_t*)r.at(r.P.x3x1[ci]), w.pin * w.C1, 0, order};
+        const long pin = r.pix(c.lvl_in);
+        t.job[t.n++] = Split3Job{(const float*)r.t(c.in0), (uint16_t*)r.at(r.P.x3x0[ci]), pin * c.C0, 0, order};
+        if (c.in1 >= 0) t.job[t.n++] = Split3Job{(const float*)r.t(c.in1), (uint16_t*)r.at(r.P.x3x1[ci]), pin * c.C1, 0, order};
         r.x3_presplit[ci] = 1;
     }
     return launch_split3_all(t, r.st);
@@ -404,7 +399,7 @@ int x3_presplit_inputs(const Run& r) {
 constexpr float DB_ACC_SCALE = 17592186044416.f;                 // 2^44: quantum 6e-14 per workgroup sum; |sum dz| up to 2^50 (a sum of
                                                                  //   the loss over pixels: 0.1-0.2 * B * H * W * w at most, past 2^19 at
                                                                  //   B = 16, 128^2 from w ~ 10)
-int flush_db(const Run& r) {
+int flush_db(Run& r) {
     if (r.dbq.n == 0) return MPU_OK;
     r.dbq.inv_scale = 1.f / DB_ACC_SCALE;
     const int rc = launch_db_from_acc(r.dbq, r.st);
@@ -412,41 +407,32 @@ int flush_db(const Run& r) {
     return rc;
 }
 
-int conv_wgrad(const Run& r, const Conv& c, const void* x0, int C0, const void* x1, int C1, const void* dz, int lvl) {
+// weight (and bias) gradient of conv ci_: its inputs from the layer table, its dz from the conv's own buffer
+int conv_wgrad(Run& r, size_t ci_) {
+    const Conv& c = r.m->conv[ci_];
+    const void* x0 = r.t(c.in0); const void* x1 = r.t(c.in1); const void* dz = r.dz(ci_);
     WgradArgs a;
-    a.x0 = x0; a.x1 = x1; a.C0 = C0; a.C1 = C1; a.dz = dz; a.Cout = c.Cout;
-    const size_t ci_ = &c - &r.m->conv[0];
+    a.x0 = x0; a.x1 = x1; a.C0 = c.C0; a.C1 = c.C1; a.dz = dz; a.Cout = c.Cout;
     a.partial = (float*)r.at(r.P.wpartial) + r.P.wscratch[ci_];                     // this layer's own scratch
     a.partial_cap = (ci_ + 1 < r.P.wscratch.size() ? r.P.wscratch[ci_ + 1] : r.P.wpartial_floats) - r.P.wscratch[ci_];
-    a.B = r.B; a.Ho = r.m->cfg.H >> lvl; a.Wo = r.m->cfg.W >> lvl;
-    a.flops = conv_flops(r, c, lvl);
-    const long M = (long)a.B * a.Ho * a.Wo;
+    a.B = r.B; a.Ho = r.m->cfg.H >> c.lvl; a.Wo = r.m->cfg.W >> c.lvl;
+    a.flops = conv_flops(r, c);
+    const long M = r.pix(c.lvl);
     wgrad_partial_elems(c.mode, c.Cin, c.Cout, M, &a.ksplit, &a.mchunk, r.group);
     a.db = r.grads + c.b; a.db_partial = nullptr; a.colsum_scratch = (float*)r.at(r.P.partial2); a.fuse_db = 0;
-    a.c0_logical = (C1 == 0 && C0 == c.Cin) ? c.lCin : 0;
+    a.c0_logical = c.C1 == 0 ? c.lCin : 0;
     a.x3 = r.m->x3;
     const bool defer = env(ENV_WGRAD_BATCHED_REDUCE) != 0;   // 0: reduce right behind every weight-gradient kernel (A/B)
     ReduceQueue* q = defer ? &r.rq : nullptr;
-    if (r.m->tap) {
-        mpu_launch_info li{};
-        li.kind = 2; li.conv_index = (int)ci_; li.mode = c.mode; li.dtype = r.m->cfg.dtype;
-        li.B = a.B; li.H = a.Ho; li.W = a.Wo; li.C0 = C0; li.C1 = C1; li.Cout = c.Cout; li.n_off = 0; li.n_cnt = c.Cin; li.relu = 0;
-        li.in0 = x0; li.in1 = x1; li.dz = dz; li.mask = nullptr; li.out = nullptr; li.w_off = c.w; li.b_off = c.b;
-        r.m->tap(r.m->tap_user, &li);                  // (before the launch: x and dz are final, dW is read after the pass)
-    }
+    tap_conv(r, 2, c, c.lvl, c.C0, c.C1, x0, x1, dz, nullptr, nullptr, 0, c.Cin, 0);   // (before the launch: x and dz are final, dW is read after the pass)
     const int ntaps_before = r.grp.ntaps;
     if (r.m->x3) {
         // dtype "bf16x3": split x and dz into bf16 plane triples (batch 3 B) and run the bf16 weight-gradient schedules on them
         // (unet_ops.hip: launch_split3); the bias gradient, which is no product, is the plain column sum of the f32 dz
-        const int Hi = c.mode == UPCONV2 ? a.Ho / 2 : a.Ho, Wi = c.mode == UPCONV2 ? a.Wo / 2 : a.Wo;
-        const long pin = (long)r.B * Hi * Wi;
-        if (ci_ < r.x3_presplit.size() && r.x3_presplit[ci_]) {  // (planes written by x3_presplit_inputs: same tensors?)
-            const WgradIn w = wgrad_inputs(r, (int)ci_);
-            if (w.x0 != x0 || w.x1 != x1 || w.C0 != C0 || w.C1 != C1 || w.pin != pin)
-                return fail(MPU_EINVAL, "%s", "conv_wgrad: the pre-split input planes belong to other tensors (wgrad_inputs out of date)");
-        } else {
-            RC(launch_split3((const float*)x0, pin * C0, r.at(r.P.x3x0[ci_]), 0, r.st));
-            if (x1) RC(launch_split3((const float*)x1, pin * C1, r.at(r.P.x3x1[ci_]), 0, r.st));
+        const long pin = r.pix(c.lvl_in);
+        if (!(ci_ < r.x3_presplit.size() && r.x3_presplit[ci_])) {   // (else: planes written by x3_presplit_inputs)
+            RC(launch_split3((const float*)x0, pin * c.C0, r.at(r.P.x3x0[ci_]), 0, r.st));
+            if (x1) RC(launch_split3((const float*)x1, pin * c.C1, r.at(r.P.x3x1[ci_]), 0, r.st));
         }
         const bool two = r.acc_mode && ci_ < r.x3_presplit.size() && r.x3_presplit[ci_] && r.x3_two[ci_];   // (hi | lo planes: a wgrad_taps job)
         if (r.acc_mode) {                              // one pass over dz: its planes + its column sums (finalized by flush_db)
@@ -470,29 +456,19 @@ int conv_wgrad(const Run& r, const Conv& c, const void* x0, int C0, const void* 
     return rc;
 }
 
-// test aid: report a non-convolution launch to the tap (kinds 3-7 of mpu_launch_info)
-void tap_aux(const Run& r, int kind, int index, int lvl, int C0, int Cout, const void* in0, const void* in1, const void* dz,
-             const void* mask, const void* out, long w_off, long b_off, const void* aux0 = nullptr, const void* aux1 = nullptr) {
-    if (!r.m->tap) return;
-    mpu_launch_info li{};
-    li.kind = kind; li.conv_index = index; li.mode = 0; li.dtype = r.m->cfg.dtype;
-    li.B = r.B; li.H = r.m->cfg.H >> lvl; li.W = r.m->cfg.W >> lvl; li.C0 = C0; li.C1 = 0; li.Cout = Cout;
-    li.in0 = in0; li.in1 = in1; li.dz = dz; li.mask = mask; li.out = out; li.w_off = w_off; li.b_off = b_off;
-    li.aux0 = aux0; li.aux1 = aux1;
-    r.m->tap(r.m->tap_user, &li);
-}
-
 // Round 6: the training step's head as the three head_bn_* passes (unet_ops.hip): bf16 or bf16x3 (accumulator mode), a 64-channel last block
 // feeding a softmax head, no launch tap (the replay tests check the unfused kernels launch by launch)
 bool head_train_fused_wanted(const Run& r) {
     const mpu_unet* m = r.m;
-    return env(ENV_HEAD_TRAIN_FUSED) != 0 && r.acc_mode && !m->tap && m->cfg.depth > 0 && m->cfg.softmax &&
+    return env(ENV_HEAD_TRAIN_FUSED) != 0 && r.acc_mode && !m->tap && m->cfg.softmax &&
            m->F[0] == 64 && head_train_fused_shape_ok(m->cfg.dtype, m->head_C, m->cfg.n_classes);
 }
 
-int bn_fwd(const Run& r, const BN& b, const void* x, int lvl, int training, void* y, void* pooled, int stats_rows = 0) {
-    const int H = r.m->cfg.H >> lvl, W = r.m->cfg.W >> lvl;
-    const long M = (long)r.B * H * W;
+// BatchNorm `b` on the tensors the layer table names: its conv's output -> y (and its 2x2 max pooling, encoder levels)
+int bn_fwd(const Run& r, const BN& b, int training, int stats_rows = 0) {
+    const void* x = r.t(b.x); void* y = r.t(b.y); void* pooled = r.t(b.pooled);
+    const int lvl = b.lvl, H = r.m->cfg.H >> lvl, W = r.m->cfg.W >> lvl;
+    const long M = r.pix(lvl);
     int rc;
     if (training && stats_rows == -1) { // the producer added its sums to this BatchNorm's accumulator: no finalize at all
         rc = launch_bn_fold_fwd(r.m->cfg.dtype, x, r.B, H, W, b.C, nullptr, -1, r.params + b.g, r.params + b.b, r.state + b.mm,
@@ -526,9 +502,11 @@ int bn_fwd(const Run& r, const BN& b, const void* x, int lvl, int training, void
     return rc;
 }
 
-int bn_bwd(const Run& r, const BN& b, const void* dn, const void* x, int lvl, void* dz, int ready_rows = 0,
-           int ready_colmajor = 0) {
-    const long M = (long)r.B * (r.m->cfg.H >> lvl) * (r.m->cfg.W >> lvl);
+// ... its backward pass: dn -> the dz of the conv in front of it
+int bn_bwd(const Run& r, const BN& b, const void* dn, int ready_rows = 0, int ready_colmajor = 0) {
+    const void* x = r.t(b.x); void* dz = r.dz(b.conv);
+    const int lvl = b.lvl;
+    const long M = r.pix(lvl);
     const int rc = launch_bn_backward(r.m->cfg.dtype, dn, x, M, b.C, (float*)r.at(r.P.partial), r.params + b.g, r.stat(b, 0),
                                       r.stat(b, 1), r.grads + b.g, r.grads + b.b, (float*)r.at(r.P.coeffs), dz, ready_rows,
                                       ready_colmajor, r.st, (r.acc_mode && !(b.C & 63)) ? r.acc_b(b) : nullptr, BN_ACC_B);
@@ -543,44 +521,40 @@ int run_forward_infer(const Run& r, const float* d_x, float* d_out) {
     const mpu_unet* m = r.m; const int D = m->cfg.depth; const Plan& P = r.P;
     const int dt = m->cfg.dtype;
     const long M0 = (long)r.B * m->cfg.H * m->cfg.W;
-    const float* co = (const float*)(r.packed + m->infer_off);
-    auto sc = [&](const BN& b) { return co + b.st + 2L * b.C; };
-    auto sh = [&](const BN& b) { return co + b.st + 3L * b.C; };
-    RC(launch_cast_pad(dt, d_x, M0, m->cfg.n_channels, m->cin_pad, r.at(P.xin), r.st));
-    const void* cur = r.at(P.xin); int Ccur = m->cin_pad;
+    const float* co = (const float*)(r.packed + m->infer_off);         // per BatchNorm: scale at 2 C, shift at 3 C of its statistics
+    RC(launch_cast_pad(dt, d_x, M0, m->cfg.n_channels, m->cin_pad, r.t(T(T_XIN)), r.st));
+    // a conv in front of a BatchNorm writes that BatchNorm's output (and, where asked for, its pooling) from its epilogue
+    auto conv = [&](int ci, int* pooled_done = nullptr, const HeadFuse* head = nullptr) {
+        const Conv& c = m->conv[ci];
+        if (c.bn < 0) return conv_fwd(r, c, r.t(c.out));
+        const BN& b = m->bn[c.bn];
+        return conv_fwd(r, c, r.t(b.y), co + b.st + 2L * b.C, co + b.st + 3L * b.C, nullptr, pooled_done ? r.t(b.pooled) : nullptr,
+                        pooled_done, head);
+    };
     for (int i = 0; i < D; ++i) {
-        const BN& b = m->bn[m->enc_bn(i)];
-        RC(conv_fwd(r, m->conv[m->enc_c1(i)], cur, Ccur, nullptr, 0, r.at(P.c1[i]), i));
+        RC(conv(m->enc_c1(i)));
         int pooled_done = 0;
-        RC(conv_fwd(r, m->conv[m->enc_c2(i)], r.at(P.c1[i]), m->F[i], nullptr, 0, r.at(P.n[i]), i, sc(b), sh(b), nullptr,
-                    r.at(P.p[i]), &pooled_done));
-        if (!pooled_done) RC(launch_maxpool(dt, r.at(P.n[i]), r.B, m->cfg.H >> i, m->cfg.W >> i, m->F[i], r.at(P.p[i]), r.st));
-        cur = r.at(P.p[i]); Ccur = m->F[i];
+        RC(conv(m->enc_c2(i), &pooled_done));
+        const BN& b = m->bn[m->conv[m->enc_c2(i)].bn];
+        if (!pooled_done) RC(launch_maxpool(dt, r.t(b.y), r.B, m->cfg.H >> i, m->cfg.W >> i, b.C, r.t(b.pooled), r.st));
     }
-    {
-        const BN& b = m->bn[m->bot_bn()];
-        RC(conv_fwd(r, m->conv[m->bot_c1()], cur, Ccur, nullptr, 0, r.at(P.c1b), D));
-        RC(conv_fwd(r, m->conv[m->bot_c2()], r.at(P.c1b), m->F[D], nullptr, 0, r.at(P.nb), D, sc(b), sh(b)));
-    }
-    const void* prev = r.at(P.nb); int Cprev = m->F[D];
+    RC(conv(m->bot_c1()));
+    RC(conv(m->bot_c2()));
     for (int j = 0; j < D; ++j) {
-        const int lvl = D - 1 - j, f = m->F[lvl];
-        const BN& b1 = m->bn[m->up_bn(j, 0)]; const BN& b2 = m->bn[m->up_bn(j, 1)];
-        RC(conv_fwd(r, m->conv[m->up_c(j, 0)], prev, Cprev, nullptr, 0, r.at(P.n1[j]), lvl, sc(b1), sh(b1)));
-        RC(conv_fwd(r, m->conv[m->up_c(j, 1)], r.at(P.n[lvl]), f, r.at(P.n1[j]), f, r.at(P.c2u[j]), lvl));
+        RC(conv(m->up_c(j, 0)));
+        RC(conv(m->up_c(j, 1)));
         // the last conv of the up path: the 1x1 head rides in its epilogue when the schedule can (conv_ws); the partial
         // logits [2][M][K] f32 go to the level-0 conv1 buffer, which is dead by now (128 B per pixel >= 8 K bytes)
         int head_done = 0;
-        HeadFuse hf{r.params + m->head_w, m->cfg.n_classes, m->cfg.n_classes, (float*)r.at(P.c1[0]), &head_done};
-        const bool last = j == D - 1 && D > 0 && m->head_C == f && (long)m->cfg.n_classes * 8 <= (long)m->F[0] * r.esz;
-        RC(conv_fwd(r, m->conv[m->up_c(j, 2)], r.at(P.c2u[j]), f, nullptr, 0, r.at(P.n2[j]), lvl, sc(b2), sh(b2), nullptr,
-                    nullptr, nullptr, last ? &hf : nullptr));
-        prev = r.at(P.n2[j]); Cprev = f;
+        HeadFuse hf{r.params + m->head_w, m->cfg.n_classes, m->cfg.n_classes, (float*)r.t(T(T_C1, 0)), &head_done};
+        const bool last = j == D - 1 && m->head_C == m->conv[m->up_c(j, 2)].Cout && (long)m->cfg.n_classes * 8 <= (long)m->F[0] * r.esz;
+        RC(conv(m->up_c(j, 2), nullptr, last ? &hf : nullptr));
         if (head_done) {
             float* out = d_out ? d_out : (float*)r.at(P.probs);
             return launch_head_combine(hf.partial, M0, m->cfg.n_classes, r.params + m->head_b, m->cfg.softmax, out, r.st);
         }
     }
+    const void* prev = r.t(m->conv.back().in0);             // (the head reads the last up block's output)
     float* out = d_out ? d_out : (float*)r.at(P.probs);
     return launch_head_forward(dt, prev, M0, m->head_C, m->cfg.n_classes, r.params + m->head_w, m->cfg.n_classes,
                                r.params + m->head_b, m->cfg.softmax, out, r.st);
@@ -593,61 +567,47 @@ int run_forward(const Run& r, const float* d_x, int training, float* d_out) {
     m->head_fused_fwd = 0;
     // accumulator mode of the fused BatchNorm statistics: offered where the folded kernel takes the shape; the accumulators of BOTH
     // passes are zeroed by the step's first launch (a backward pass belongs to exactly one training forward)
-    RC(launch_cast_pad(m->cfg.dtype, d_x, M0, m->cfg.n_channels, m->cin_pad, r.at(P.xin), r.st,
+    RC(launch_cast_pad(m->cfg.dtype, d_x, M0, m->cfg.n_channels, m->cin_pad, r.t(T(T_XIN)), r.st,
                        r.acc_mode ? (long long*)r.at(P.bnacc) : nullptr, P.bnacc_elems));
-    auto accf = [&](const BN& b, int lvl, bool pooled) -> long long* {
-        return (r.acc_mode && bn_fold_shape_ok(b.C, m->cfg.H >> lvl, m->cfg.W >> lvl, pooled)) ? r.acc_f(b) : nullptr;
+    // a conv in front of a BatchNorm (rows != null) also produces the sums of its output: rows of partial sums, or -1 = in the accumulator
+    auto conv = [&](int ci, int* rows = nullptr) {
+        const Conv& c = m->conv[ci];
+        if (!rows) return conv_fwd(r, c, r.t(c.out));
+        const BN& b = m->bn[c.bn];
+        const bool acc = r.acc_mode && bn_fold_shape_ok(b.C, m->cfg.H >> b.lvl, m->cfg.W >> b.lvl, b.pooled >= 0);
+        return conv_fwd(r, c, r.t(c.out), nullptr, nullptr, rows, nullptr, nullptr, nullptr, acc ? r.acc_f(b) : nullptr);
     };
-    const void* cur = r.at(P.xin); int Ccur = m->cin_pad;
-    for (int i = 0; i < D; ++i) {
-        RC(conv_fwd(r, m->conv[m->enc_c1(i)], cur, Ccur, nullptr, 0, r.at(P.c1[i]), i));
-        int rows = 0;
-        RC(conv_fwd(r, m->conv[m->enc_c2(i)], r.at(P.c1[i]), m->F[i], nullptr, 0, r.at(P.c2[i]), i, nullptr, nullptr, &rows,
-                    nullptr, nullptr, nullptr, accf(m->bn[m->enc_bn(i)], i, true)));
-        RC(bn_fwd(r, m->bn[m->enc_bn(i)], r.at(P.c2[i]), i, training, r.at(P.n[i]), r.at(P.p[i]), rows));
-        cur = r.at(P.p[i]); Ccur = m->F[i];
-    }
-    RC(conv_fwd(r, m->conv[m->bot_c1()], cur, Ccur, nullptr, 0, r.at(P.c1b), D));
-    {
-        int rows = 0;
-        RC(conv_fwd(r, m->conv[m->bot_c2()], r.at(P.c1b), m->F[D], nullptr, 0, r.at(P.c2b), D, nullptr, nullptr, &rows,
-                    nullptr, nullptr, nullptr, accf(m->bn[m->bot_bn()], D, false)));
-        RC(bn_fwd(r, m->bn[m->bot_bn()], r.at(P.c2b), D, training, r.at(P.nb), nullptr, rows));
-    }
-    const void* prev = r.at(P.nb); int Cprev = m->F[D];
+    auto conv_bn = [&](int ci) { int rows = 0; RC(conv(ci, &rows)); return bn_fwd(r, m->bn[m->conv[ci].bn], training, rows); };
+    for (int i = 0; i < D; ++i) { RC(conv(m->enc_c1(i))); RC(conv_bn(m->enc_c2(i))); }
+    RC(conv(m->bot_c1())); RC(conv_bn(m->bot_c2()));
     for (int j = 0; j < D; ++j) {
-        const int lvl = D - 1 - j, f = m->F[lvl];
-        int rows = 0;
-        RC(conv_fwd(r, m->conv[m->up_c(j, 0)], prev, Cprev, nullptr, 0, r.at(P.u1[j]), lvl, nullptr, nullptr, &rows,
-                    nullptr, nullptr, nullptr, accf(m->bn[m->up_bn(j, 0)], lvl, false)));
-        RC(bn_fwd(r, m->bn[m->up_bn(j, 0)], r.at(P.u1[j]), lvl, training, r.at(P.n1[j]), nullptr, rows));
-        RC(conv_fwd(r, m->conv[m->up_c(j, 1)], r.at(P.n[lvl]), f, r.at(P.n1[j]), f, r.at(P.c2u[j]), lvl));
-        rows = 0;
-        RC(conv_fwd(r, m->conv[m->up_c(j, 2)], r.at(P.c2u[j]), f, nullptr, 0, r.at(P.c3u[j]), lvl, nullptr, nullptr, &rows,
-                    nullptr, nullptr, nullptr, accf(m->bn[m->up_bn(j, 1)], lvl, false)));
+        RC(conv_bn(m->up_c(j, 0)));
+        RC(conv(m->up_c(j, 1)));
+        const int i3 = m->up_c(j, 2); int rows = 0;
+        RC(conv(i3, &rows));
         if (j == D - 1 && rows == -1 && head_train_fused_wanted(r)) { m->head_fused_fwd = 1; break; }     // (no n2 of the last block)
-        RC(bn_fwd(r, m->bn[m->up_bn(j, 1)], r.at(P.c3u[j]), lvl, training, r.at(P.n2[j]), nullptr, rows));
-        prev = r.at(P.n2[j]); Cprev = f;
+        RC(bn_fwd(r, m->bn[m->conv[i3].bn], training, rows));
     }
     float* out = d_out ? d_out : (float*)r.at(P.probs);
     if (m->head_fused_fwd) {
-        const BN& b = m->bn[m->up_bn(D - 1, 1)];
-        RC(launch_head_bn_forward(m->cfg.dtype, r.at(P.c3u[D - 1]), M0, r.acc_f(b), BN_ACC_F, r.params + b.g, r.params + b.b, r.state + b.mm,
+        const BN& b = m->bn.back();                             // (the last block's second BatchNorm, on c3 of that block)
+        RC(launch_head_bn_forward(m->cfg.dtype, r.t(b.x), M0, r.acc_f(b), BN_ACC_F, r.params + b.g, r.params + b.b, r.state + b.mm,
                                   r.state + b.mv, r.stat(b, 0), r.stat(b, 1), r.stat(b, 2), r.stat(b, 3), BN_EPS, BN_MOM,
                                   m->cfg.n_classes, r.params + m->head_w, m->cfg.n_classes, r.params + m->head_b, m->cfg.softmax, out, r.st));
     } else {
+        const void* prev = r.t(m->conv.back().in0);
         RC(launch_head_forward(m->cfg.dtype, prev, M0, m->head_C, m->cfg.n_classes, r.params + m->head_w,
                                m->cfg.n_classes, r.params + m->head_b, m->cfg.softmax, out, r.st));
         tap_aux(r, 6, -1, 0, m->head_C, m->cfg.n_classes, prev, nullptr, nullptr, nullptr, out, m->head_w, m->head_b);
     }
-    if (training && d_out)     // keep a copy for the backward pass
+    if (d_out)     // keep a copy for the backward pass
         MPU_CHECK_HIP(hipMemcpyAsync(r.at(P.probs), d_out, M0 * m->cfg.n_classes * 4, hipMemcpyDeviceToDevice, r.st));
     return MPU_OK;
 }
 
 // gradient-ready point k (see mpu_unet_grad_ready_points): everything the backward pass will write at or
 // above that offset of the flat gradient buffer has been enqueued; record the caller's event there
-int mark_ready(const Run& r, int k) {
+int mark_ready(Run& r, int k) {
     if (!r.ready_events || k >= r.n_ready || !r.ready_events[k]) return MPU_OK;
     int rc = flush_wgrad_group(r.m->x3 ? MPU_BF16 : r.m->cfg.dtype, r.grp, r.st);     // the gradients above this point must be final before the event
     if (rc) return rc;
@@ -661,18 +621,18 @@ int mark_ready(const Run& r, int k) {
 
 // The optimizer of mpu_unet_backward_adam (Keras Adam on the flat buffers + refresh of the packed operands)
 struct AdamOpt { float* params; void* packed; float* am; float* av; long long* step; long long t; double lr, b1, b2; float eps; };
-int finish_backward(const Run& r, const AdamOpt* opt);
+int finish_backward(Run& r, const AdamOpt* opt);
 // the overlapped tail is decided BEFORE the pass (the device step counter then moves at its start): the switch, the dtype
 // and the grouped weight gradients it rides beside; whether a layer actually takes wgrad_taps is known only at the end --
 // finish_backward handles "none did" with the same pre-advanced counter
 bool tail_overlap_wanted(const Run& r) { return env(ENV_TAIL_OVERLAP) != 0 && r.m->cfg.dtype == MPU_BF16 && r.group; }
 
-int run_backward(const Run& r, const uint8_t* d_y, const float* d_sw, float* d_loss, const AdamOpt* opt = nullptr) {
+int run_backward(Run& r, const uint8_t* d_y, const float* d_sw, float* d_loss, const AdamOpt* opt = nullptr) {
     const mpu_unet* m = r.m; const int D = m->cfg.depth; const Plan& P = r.P;
     const int dt = m->cfg.dtype;
     const long M0 = (long)r.B * m->cfg.H * m->cfg.W;
     void* gA = r.at(P.gA); void* gB = r.at(P.gB);
-    const void* last = D > 0 ? r.at(P.n2[D - 1]) : r.at(P.nb);
+    const void* last = r.t(m->conv.back().in0);                 // (the head's input: the last up block's output)
     const bool head_fused = m->head_fused_fwd != 0;
     // A per-image loss (mpu_unet_set_loss): statistics pass + coefficient step first -- they write d_loss [B] and the logged mean --
     // then the same head kernels in that loss's form, which produce neither
@@ -688,8 +648,8 @@ int run_backward(const Run& r, const uint8_t* d_y, const float* d_sw, float* d_l
         hl = &hlv; d_loss = nullptr; loss_mean = nullptr;
     }
     if (head_fused) {           // (the forward pass left no n2 of the last block: head_bn_* passes over c3 instead)
-        const BN& b = m->bn[m->up_bn(D - 1, 1)];
-        const void* c3 = r.at(P.c3u[D - 1]);
+        const BN& b = m->bn.back();
+        const void* c3 = r.t(b.x);
         float* tsum = (float*)r.at(P.partial) + P.partial_floats;
         const long ppi = (long)m->cfg.H * m->cfg.W;
         RC(launch_head_bn_backward(dt, c3, (const float*)r.at(P.probs), d_y, d_sw, M0, ppi, m->cfg.n_classes, r.stat(b, 0), r.stat(b, 1),
@@ -698,7 +658,7 @@ int run_backward(const Run& r, const uint8_t* d_y, const float* d_sw, float* d_l
         RC(launch_head_bn_bwd_apply(dt, c3, (const float*)r.at(P.probs), d_y, d_sw, M0, ppi, m->cfg.n_classes, r.params + m->head_w,
                                     m->cfg.n_classes, tsum, r.grads + m->head_b, r.params + b.g, r.params + b.b, r.stat(b, 0), r.stat(b, 1),
                                     r.grads + b.g, r.grads + b.b, r.grads + m->head_w, (float*)r.at(P.coeffs),
-                                    r.at(P.dz[m->up_c(D - 1, 2)]), r.st, hl));
+                                    r.dz(b.conv), r.st, hl));
     } else {
         RC(launch_head_backward(dt, last, (const float*)r.at(P.probs), d_y, d_sw, M0, (long)m->cfg.H * m->cfg.W,
                                 m->head_C, m->cfg.n_classes, r.params + m->head_w, m->cfg.n_classes,
@@ -707,52 +667,45 @@ int run_backward(const Run& r, const uint8_t* d_y, const float* d_sw, float* d_l
         tap_aux(r, 7, -1, 0, m->head_C, m->cfg.n_classes, last, r.at(P.probs), d_y, d_sw, gA, m->head_w, m->head_b);
     }
     if (m->x3) RC(x3_presplit_inputs(r));
-    int point = 0;
-    RC(mark_ready(r, point++));                                                            // head
+    RC(mark_ready(r, m->conv.back().block));                                               // head
     // (weight gradients on a side stream next to the data gradients were measured twice -- 3.08 vs 3.03 ms in round 2 --
     // and removed in round 3: both kernels need a whole CU's LDS, so they never share one)
     int rowsA = 0;       // partial rows of BN-backward sums already produced for the dn in gA (0: head_backward wrote it)
-    auto DZ = [&](int ci) { return r.at(P.dz[ci]); };            // every conv's dz lives in its own buffer until the pass ends
     for (int j = D - 1; j >= 0; --j) {
-        const int lvl = D - 1 - j, f = m->F[lvl];
         const int iu = m->up_c(j, 0), i2 = m->up_c(j, 1), i3 = m->up_c(j, 2);
         const Conv& cu = m->conv[iu]; const Conv& c2 = m->conv[i2]; const Conv& c3 = m->conv[i3];
-        const void* prev = j > 0 ? r.at(P.n2[j - 1]) : r.at(P.nb);
-        const int Cprev = j > 0 ? m->F[lvl + 1] : m->F[D];
+        const BN& b1 = m->bn[cu.bn];
         if (!(head_fused && j == D - 1))                                                   // (fused head: dz3 of the last block is written)
-            RC(bn_bwd(r, m->bn[m->up_bn(j, 1)], gA, r.at(P.c3u[j]), lvl, DZ(i3), rowsA, 1));   // dz3
-        RC(conv_wgrad(r, c3, r.at(P.c2u[j]), f, nullptr, 0, DZ(i3), lvl));
-        RC(conv_dgrad(r, c3, DZ(i3), r.at(P.c2u[j]), DZ(i2), lvl, 0, f));                  // dz2
-        RC(conv_wgrad(r, c2, r.at(P.n[lvl]), f, r.at(P.n1[j]), f, DZ(i2), lvl));
-        RC(conv_dgrad(r, c2, DZ(i2), nullptr, r.at(P.dskip[lvl]), lvl, 0, f));             // d skip
+            RC(bn_bwd(r, m->bn[c3.bn], gA, rowsA, 1));                                     // dz3
+        RC(conv_wgrad(r, i3));
+        RC(conv_dgrad(r, c3, r.t(c3.in0), r.dz(i2), 0, c3.Cin));                           // dz2
+        RC(conv_wgrad(r, i2));
+        RC(conv_dgrad(r, c2, nullptr, r.t(T(T_DSKIP, c2.lvl)), 0, c2.C0));                 // d skip
         int rowsB = 0;                                                                     // (BN-backward sums from the epilogue)
-        RC(conv_dgrad(r, c2, DZ(i2), nullptr, gB, lvl, f, f, &m->bn[m->up_bn(j, 0)], r.at(P.u1[j]), &rowsB));   // d n1 -> gB
-        RC(bn_bwd(r, m->bn[m->up_bn(j, 0)], gB, r.at(P.u1[j]), lvl, DZ(iu), rowsB, 1));    // dz of the up-conv
-        RC(conv_wgrad(r, cu, prev, Cprev, nullptr, 0, DZ(iu), lvl));
-        // d prev -> gA: the dn of the previous block's second BatchNorm (or of the bottom one)
-        const BN& pbn = j > 0 ? m->bn[m->up_bn(j - 1, 1)] : m->bn[m->bot_bn()];
-        const void* pbx = j > 0 ? r.at(P.c3u[j - 1]) : r.at(P.c2b);
-        RC(conv_dgrad(r, cu, DZ(iu), nullptr, gA, lvl + 1, 0, Cprev, &pbn, pbx, &rowsA));
-        RC(mark_ready(r, point++));                                                        // up block j
+        RC(conv_dgrad(r, c2, nullptr, gB, c2.C0, c2.C1, &b1, &rowsB));                     // d n1 -> gB
+        RC(bn_bwd(r, b1, gB, rowsB, 1));                                                   // dz of the up-conv
+        RC(conv_wgrad(r, iu));
+        // d prev -> gA: the dn of the BatchNorm that wrote the up-conv's input (the previous block's second, or the bottom one)
+        RC(conv_dgrad(r, cu, nullptr, gA, 0, cu.Cin, &m->bn[m->conv[iu - 1].bn], &rowsA));
+        RC(mark_ready(r, cu.block));                                                       // up block j
     }
     {   // bottom
         const int i1 = m->bot_c1(), i2 = m->bot_c2();
         const Conv& c1 = m->conv[i1]; const Conv& c2 = m->conv[i2];
-        const void* xin = D > 0 ? r.at(P.p[D - 1]) : r.at(P.xin);
-        const int Cx = D > 0 ? m->F[D - 1] : m->cin_pad;
-        RC(bn_bwd(r, m->bn[m->bot_bn()], gA, r.at(P.c2b), D, DZ(i2), D > 0 ? rowsA : 0, 1));
-        RC(conv_wgrad(r, c2, r.at(P.c1b), m->F[D], nullptr, 0, DZ(i2), D));
-        RC(conv_dgrad(r, c2, DZ(i2), r.at(P.c1b), DZ(i1), D, 0, m->F[D]));
-        RC(conv_wgrad(r, c1, xin, Cx, nullptr, 0, DZ(i1), D));
-        if (D > 0) RC(conv_dgrad(r, c1, DZ(i1), nullptr, gB, D, 0, Cx));                   // d pooled -> gB
-        RC(mark_ready(r, point++));                                                        // bottom
+        RC(bn_bwd(r, m->bn[c2.bn], gA, rowsA, 1));
+        RC(conv_wgrad(r, i2));
+        RC(conv_dgrad(r, c2, r.t(c2.in0), r.dz(i1), 0, c2.Cin));
+        RC(conv_wgrad(r, i1));
+        RC(conv_dgrad(r, c1, nullptr, gB, 0, c1.Cin));                                     // d pooled -> gB
+        RC(mark_ready(r, c1.block));                                                       // bottom
     }
     for (int i = D - 1; i >= 0; --i) {
         const int i1 = m->enc_c1(i), i2 = m->enc_c2(i);
         const Conv& c1 = m->conv[i1]; const Conv& c2 = m->conv[i2];
         const int H = m->cfg.H >> i, W = m->cfg.W >> i;
         // skip gradient + un-pooled gradient, and in the same pass the BN-backward sums of the result
-        const BN& eb = m->bn[m->enc_bn(i)];
+        const BN& eb = m->bn[c2.bn];
+        const void* dskip = r.t(T(T_DSKIP, i));
         int bwd_rows = 0;
         // Round 6 (MPU_POOL_BWD_RECOMPUTE): neither the post-BatchNorm tensor n is read nor the summed gradient written -- both
         // passes recompute them from the BatchNorm input, the skip gradient and the pooled gradient (same bits; no launch tap:
@@ -761,26 +714,24 @@ int run_backward(const Run& r, const uint8_t* d_y, const float* d_sw, float* d_l
         // (from 4 M elements: measured R6av at configs[1] -- levels 0 / 1 / 2 50.0 -> 41.6, 28.7 -> 26.4, 17.2 -> 16.2 us; the
         //  2 M elements x 512 channels of level 3 lose 1.6 us to the all-channel coefficient prologue of the second pass)
         if (env(ENV_POOL_BWD_RECOMPUTE) != 0 && r.acc_mode && !(eb.C & 63) && !m->tap &&
-            (long)r.B * H * W * m->F[i] >= (env(ENV_POOL_BWD_RECOMPUTE) > 1 ? 0L : 4L << 20)) {
-            fused_pool = launch_maxpool_bwd_bn(dt, r.at(P.dskip[i]), gB, r.B, H, W, m->F[i], r.at(P.c2[i]), r.stat(eb, 0), r.stat(eb, 1),
+            r.pix(i) * eb.C >= (env(ENV_POOL_BWD_RECOMPUTE) > 1 ? 0L : 4L << 20)) {
+            fused_pool = launch_maxpool_bwd_bn(dt, dskip, gB, r.B, H, W, eb.C, r.t(eb.x), r.stat(eb, 0), r.stat(eb, 1),
                                                r.stat(eb, 2), r.stat(eb, 3), r.params + eb.g, r.grads + eb.g, r.grads + eb.b,
-                                               (float*)r.at(P.coeffs), DZ(i2), r.acc_b(eb), BN_ACC_B, r.st);
+                                               (float*)r.at(P.coeffs), r.dz(i2), r.acc_b(eb), BN_ACC_B, r.st);
             if (fused_pool < 0) return fused_pool;
         }
         if (!fused_pool) {
-            RC(launch_maxpool_bwd_add_stats(dt, r.at(P.n[i]), r.at(P.dskip[i]), gB, r.B, H, W, m->F[i], gA, r.at(P.c2[i]),
+            RC(launch_maxpool_bwd_add_stats(dt, r.t(eb.y), dskip, gB, r.B, H, W, eb.C, gA, r.t(eb.x),
                                             r.stat(eb, 0), r.stat(eb, 1), (float*)r.at(P.partial), P.partial_floats, &bwd_rows,
                                             r.st, (r.acc_mode && !(eb.C & 63)) ? r.acc_b(eb) : nullptr, BN_ACC_B));
-            tap_aux(r, 5, m->enc_bn(i), i, m->F[i], m->F[i], r.at(P.n[i]), r.at(P.dskip[i]), gB, nullptr, gA, 0, 0);
-            RC(bn_bwd(r, eb, gA, r.at(P.c2[i]), i, DZ(i2), bwd_rows));
+            tap_aux(r, 5, c2.bn, i, eb.C, eb.C, r.t(eb.y), dskip, gB, nullptr, gA, 0, 0);
+            RC(bn_bwd(r, eb, gA, bwd_rows));
         }
-        RC(conv_wgrad(r, c2, r.at(P.c1[i]), m->F[i], nullptr, 0, DZ(i2), i));
-        RC(conv_dgrad(r, c2, DZ(i2), r.at(P.c1[i]), DZ(i1), i, 0, m->F[i]));
-        const void* xin = i > 0 ? r.at(P.p[i - 1]) : r.at(P.xin);
-        const int Cx = i > 0 ? m->F[i - 1] : m->cin_pad;
-        RC(conv_wgrad(r, c1, xin, Cx, nullptr, 0, DZ(i1), i));
-        if (i > 0) RC(conv_dgrad(r, c1, DZ(i1), nullptr, gB, i, 0, Cx));
-        RC(mark_ready(r, point++));                                                        // encoder level i
+        RC(conv_wgrad(r, i2));
+        RC(conv_dgrad(r, c2, r.t(c2.in0), r.dz(i1), 0, c2.Cin));
+        RC(conv_wgrad(r, i1));
+        if (i > 0) RC(conv_dgrad(r, c1, nullptr, gB, 0, c1.Cin));
+        RC(mark_ready(r, c1.block));                                                       // encoder level i
     }
     // the deferred weight-gradient kernels of the whole pass as grouped launches, then their reductions in one more
     // (with an optimizer: the part of it whose gradients are final early runs BESIDE the last grouped launch)
@@ -838,7 +789,7 @@ int pack_jobs_of(const mpu_unet* m, PackTable& tab) {
 // parameters] -> join -> step counter. Same kernels' arithmetic, disjoint parameter ranges: bit-identical to the serial
 // order (tests/test_gpu_unet.py); MPU_TAIL_OVERLAP=0 runs the serial order. Under stream capture the fork / join become
 // parallel branches of the graph.
-int finish_backward(const Run& r, const AdamOpt* opt) {
+int finish_backward(Run& r, const AdamOpt* opt) {
     const mpu_unet* m = r.m; const int dt = m->cfg.dtype;
     const int wdt = m->x3 ? MPU_BF16 : dt;                       // (dtype "bf16x3": the grouped weight gradients are bf16 jobs)
     RC(flush_db(r));
@@ -954,30 +905,34 @@ mpu_unet* mpu_unet_create(const mpu_unet_config* cfg) {
     // gamma/beta directly follow that block's convs, so that a block's whole gradient (convs AND BN) is final
     // at the block's gradient-ready point (mpu_unet_grad_ready_points; the backward pass completes the buffer
     // from its end towards its start).
+    // This walk is also the layer table: each add_conv states the conv's level, ready-point block (head 0, up blocks last -> first,
+    // bottom, encoder levels last -> first: the order the backward pass finishes them), input and output tensors; each add_bn the
+    // output (and pooled output) of the BatchNorm behind the conv just added. `src` is the tensor the next block reads.
     char buf[64];
-    int cin = m->cin_pad, lcin = cfg->n_channels;
+    int cin = m->cin_pad, lcin = cfg->n_channels, src = T(T_XIN);
     for (int i = 0; i < D; ++i) {
         snprintf(buf, sizeof(buf), "encoder_L%d", i);
-        add_conv(m, std::string(buf) + "_conv1", CONV3, cin, m->F[i], lcin, m->Fl[i]);
-        add_conv(m, std::string(buf) + "_conv2", CONV3, m->F[i], m->F[i], m->Fl[i], m->Fl[i]);
-        add_bn(m, std::string(buf) + "_BN", m->F[i], m->Fl[i]);
-        cin = m->F[i]; lcin = m->Fl[i];
+        add_conv(m, std::string(buf) + "_conv1", CONV3, cin, m->F[i], lcin, m->Fl[i], i, 2 * D + 1 - i, src, T(T_C1, i));
+        add_conv(m, std::string(buf) + "_conv2", CONV3, m->F[i], m->F[i], m->Fl[i], m->Fl[i], i, 2 * D + 1 - i, T(T_C1, i), T(T_C2, i));
+        add_bn(m, std::string(buf) + "_BN", m->F[i], m->Fl[i], T(T_N, i), T(T_P, i));
+        cin = m->F[i]; lcin = m->Fl[i]; src = T(T_P, i);
     }
-    add_conv(m, "bottom_conv1", CONV3, cin, m->F[D], lcin, m->Fl[D]);
-    add_conv(m, "bottom_conv2", CONV3, m->F[D], m->F[D], m->Fl[D], m->Fl[D]);
-    add_bn(m, "bottom_BN", m->F[D], m->Fl[D]);
-    cin = m->F[D]; lcin = m->Fl[D];
+    add_conv(m, "bottom_conv1", CONV3, cin, m->F[D], lcin, m->Fl[D], D, D + 1, src, T(T_C1B));
+    add_conv(m, "bottom_conv2", CONV3, m->F[D], m->F[D], m->Fl[D], m->Fl[D], D, D + 1, T(T_C1B), T(T_C2B));
+    add_bn(m, "bottom_BN", m->F[D], m->Fl[D], T(T_NB));
+    cin = m->F[D]; lcin = m->Fl[D]; src = T(T_NB);
     for (int j = 0; j < D; ++j) {
         const int lvl = D - 1 - j;
         snprintf(buf, sizeof(buf), "upsample_L%d", j);
-        add_conv(m, std::string(buf) + "_conv1", UPCONV2, cin, m->F[lvl], lcin, m->Fl[lvl]);
-        add_bn(m, std::string(buf) + "_BN1", m->F[lvl], m->Fl[lvl]);
-        add_conv(m, std::string(buf) + "_conv2", CONV3, 2 * m->F[lvl], m->F[lvl], 2 * m->Fl[lvl], m->Fl[lvl]);
-        add_conv(m, std::string(buf) + "_conv3", CONV3, m->F[lvl], m->F[lvl], m->Fl[lvl], m->Fl[lvl]);
-        add_bn(m, std::string(buf) + "_BN2", m->F[lvl], m->Fl[lvl]);
-        cin = m->F[lvl]; lcin = m->Fl[lvl];
+        add_conv(m, std::string(buf) + "_conv1", UPCONV2, cin, m->F[lvl], lcin, m->Fl[lvl], lvl, D - j, src, T(T_U1, j));
+        add_bn(m, std::string(buf) + "_BN1", m->F[lvl], m->Fl[lvl], T(T_N1, j));
+        add_conv(m, std::string(buf) + "_conv2", CONV3, 2 * m->F[lvl], m->F[lvl], 2 * m->Fl[lvl], m->Fl[lvl], lvl, D - j, T(T_N, lvl),
+                 T(T_C2U, j), T(T_N1, j));                                    // concat: skip | up-sampled
+        add_conv(m, std::string(buf) + "_conv3", CONV3, m->F[lvl], m->F[lvl], m->Fl[lvl], m->Fl[lvl], lvl, D - j, T(T_C2U, j), T(T_C3U, j));
+        add_bn(m, std::string(buf) + "_BN2", m->F[lvl], m->Fl[lvl], T(T_N2, j));
+        cin = m->F[lvl]; lcin = m->Fl[lvl]; src = T(T_N2, j);
     }
-    add_conv(m, "conv2d", CONV1, cin, cfg->n_classes, lcin, cfg->n_classes);
+    add_conv(m, "conv2d", CONV1, cin, cfg->n_classes, lcin, cfg->n_classes, 0, 0, src, -1);
     m->head_C = cin; m->head_w = m->conv.back().w; m->head_b = m->conv.back().b;
     m->infer_off = (m->n_packed * (cfg->dtype == MPU_BF16 ? 2 : 4) + 255) / 256 * 256;
     return m;
@@ -1127,12 +1082,8 @@ int mpu_debug_tail_events(int32_t on, float* ms_out) {
 
 int32_t mpu_unet_grad_ready_points(const mpu_unet* m, int64_t* offsets, int32_t cap) {
     if (!m) return 0;
-    const int D = m->cfg.depth;
-    std::vector<long> pts;
-    pts.push_back(m->head_w < m->head_b ? m->head_w : m->head_b);
-    for (int j = D - 1; j >= 0; --j) pts.push_back(m->conv[m->up_c(j, 0)].w);
-    pts.push_back(m->conv[m->bot_c1()].w);
-    for (int i = D - 1; i >= 0; --i) pts.push_back(m->conv[m->enc_c1(i)].w);
+    std::vector<long> pts(m->conv[0].block + 1, -1);         // a block's point: where its first tensor (a conv kernel) starts
+    for (const Conv& c : m->conv) if (pts[c.block] < 0) pts[c.block] = c.w;
     for (size_t k = 0; k < pts.size() && (int)k < cap; ++k) offsets[k] = pts[k];
     return (int32_t)pts.size();
 }

@@ -203,6 +203,56 @@ def _replay_conv_launches(B, dim, cf, dtype="bf16", tol_act=1.2e-2, tol_w=2e-3):
     print("replay: weight / bias gradients of the 22 layers: worst rel-to-max error %.3g" % worst_w)
 
 
+@pytest.mark.parametrize("dtype", ["bf16", "bf16x3"])
+def test_weight_gradient_reads_the_tensors_its_forward_read(dtype):
+    """A conv's inputs are stated once, in the driver's layer table, and both passes resolve them from it. Depth 2 (the smallest
+    network with both a first and a later encoder level and up block), 2 images of 16 x 16, 32 / 64 / 128 filters: for every conv
+    the weight-gradient launch reports the input pointers, channel counts and output size of its forward launch, and every forward
+    input is a tensor an earlier launch wrote -- a conv output, a BatchNorm output or its pooling -- or, for the first conv, the
+    channel-padded input at the start of the workspace. Pointer and integer equality only."""
+    from multiplanarunet_amd import _lib
+    from multiplanarunet_amd.unet import UNet
+    B, dim, K, depth = 2, 16, 3, 2
+    rng = np.random.RandomState(7)
+    x = rng.randn(B, dim, dim, 1).astype(np.float32)
+    y = rng.randint(0, K, (B, dim * dim, 1)).astype(np.uint8)
+    m = UNet(n_classes=K, dim=dim, n_channels=1, depth=depth, complexity_factor=0.25, dtype=dtype, logger=quiet, seed=3)
+    recs = []
+
+    def on_launch(_user, pinfo):
+        recs.append({f: getattr(pinfo.contents, f) for f, _t in _lib.LaunchInfo._fields_})
+
+    cb = _lib.LAUNCH_TAP_FN(on_launch)
+    _lib.call("mpu_unet_set_launch_tap", m._h, C.cast(cb, C.c_void_p), None)
+    try:
+        m.forward_backward(x, y, None)
+        torch.cuda.synchronize()
+    finally:
+        _lib.call("mpu_unet_set_launch_tap", m._h, None, None)
+    n_conv = 2 * depth + 2 + 3 * depth                     # every conv but the 1x1 head
+    fwd = {r["conv_index"]: r for r in recs if r["kind"] == 0}
+    wg = {r["conv_index"]: r for r in recs if r["kind"] == 2}
+    assert sorted(fwd) == sorted(wg) == list(range(n_conv))
+    assert sum(r["kind"] == 0 for r in recs) == sum(r["kind"] == 2 for r in recs) == n_conv
+    for ci in range(n_conv):
+        for f in ("in0", "in1", "C0", "C1", "H", "W"):
+            assert wg[ci][f] == fwd[ci][f], (ci, f, wg[ci][f], fwd[ci][f])
+        assert fwd[ci]["in0"] and bool(fwd[ci]["in1"]) == (fwd[ci]["C1"] > 0), ci
+    assert sum(fwd[ci]["C1"] > 0 for ci in fwd) == depth    # the concat conv of every up block
+    written = set()
+    for r in recs:
+        if r["kind"] == 0:
+            for f in ("in0", "in1"):
+                if r[f] is None:
+                    continue
+                if r["conv_index"] == 0:
+                    assert r[f] == m._ws.data_ptr(), (f, r[f])
+                else:
+                    assert r[f] in written, (r["conv_index"], f)
+        if r["kind"] in (0, 3):
+            written.update(p for p in (r["out"], r["mask"]) if p)
+
+
 def test_cfg1_bf16_step_every_non_conv_launch_against_fp64_on_its_own_inputs():
     """the launch tap also reports the BatchNormalization forward / backward launches, the max-pool
     backward + skip add, the 1x1 head forward and the head backward of the benchmarked bf16 step; each is recomputed in fp64
