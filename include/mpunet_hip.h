@@ -700,6 +700,18 @@ int mpu_debug_stamps_read(uint64_t* host_out, int32_t n);
  *   kind 7  head backward (Keras sparse CE on clipped probabilities, sum gradient): in0 = n, in1 = probabilities (f32),
  *           dz = labels (u8 [B,H*W]), mask = per-image sample weights (f32 [B]) or NULL, out = dn [B,H,W,C0]; dWh / dbh land
  *           at w_off / b_off of the gradient buffer.
+ * The inference forward (mpu_unet_forward, training = 0) reports as well: a conv without a BatchNorm as kind 0, the separate
+ * head kernel as kind 6, and
+ *   kind 8  conv forward with the folded BatchNormalization of inference: fields as kind 0 (relu = 1) and
+ *           out = post_scale * relu(conv(in0|in1) + bias) + post_shift; aux0 / aux1 = the device post_scale / post_shift
+ *           (f32 [Cout], written by mpu_unet_prepare_inference), n_off = index of that BatchNorm; mask = the 2x2 max pooling
+ *           of out [B,H/2,W/2,Cout] if the schedule wrote it from its epilogue (else NULL); dz = the partial logits
+ *           (f32 [2][B*H*W][n_classes]: the 1x1 head, without its bias, over channels 0..31 / 32..63 of the rounded output) if
+ *           the head rode in the epilogue (else NULL) -- then out = NULL: the output tensor is not stored;
+ *   kind 9  separate MaxPooling2D forward: in0 = y [B,H,W,C0], out = its 2x2 max pooling [B,H/2,W/2,C0]; conv_index = the
+ *           BatchNorm whose output y is;
+ *   kind 10 head combine: in0 = the partial logits f32 [2][B*H*W][Cout] of a kind-8 launch, out = probabilities f32
+ *           [B,H,W,Cout] (softmax of partial[0] + partial[1] + bh; bh at b_off, Wh at w_off).
  * The callback runs on the calling thread; NULL removes the tap. Not for use under graph capture. */
 typedef struct mpu_launch_info {
     int32_t kind, conv_index, mode, dtype;      /* mode: 0 3x3, 1 up-conv 2x2, 3 1x1 (the LAYER's mode); kinds >= 3: conv_index = BN index */
@@ -707,7 +719,7 @@ typedef struct mpu_launch_info {
     int32_t n_off, n_cnt, relu, _pad;
     const void* in0; const void* in1; const void* dz; const void* mask; const void* out;
     int64_t w_off, b_off;                       /* float offsets of the layer's kernel / bias in the flat buffers */
-    const void* aux0; const void* aux1;         /* kinds 3, 4: batch mean, 1/sqrt(var + eps) */
+    const void* aux0; const void* aux1;         /* kinds 3, 4: batch mean, 1/sqrt(var + eps); kind 8: post_scale, post_shift */
 } mpu_launch_info;
 typedef void (*mpu_launch_tap_fn)(void* user, const mpu_launch_info* info);
 int mpu_unet_set_launch_tap(mpu_unet* m, mpu_launch_tap_fn fn, void* user);

@@ -328,6 +328,11 @@ int conv_fwd(const Run& r, const Conv& c, void* out, const float* post_scale = n
     a.x3 = r.m->x3;
     const int rc = launch_conv(r.m->cfg.dtype, c.mode, a, r.st);
     if (!rc && !post_scale) tap_conv(r, 0, c, c.lvl, c.C0, c.C1, in0, in1, nullptr, nullptr, out, 0, c.Cin, 1);
+    if (!rc && post_scale) {    // inference, folded BatchNorm (kind 8): what the schedule took on -- the pooling, the head -- is known by now
+        const bool hd = a.head_done && *a.head_done, pd = a.pooled_done && *a.pooled_done;
+        tap(r, 8, (int)(&c - &r.m->conv[0]), c.mode, c.lvl, c.C0, c.C1, c.Cout, in0, in1, hd ? a.head_partial : nullptr,
+            pd ? pooled : nullptr, hd ? nullptr : out, c.w, c.b, c.bn, c.Cin, 1, post_scale, post_shift);
+    }
     return rc;
 }
 
@@ -536,7 +541,10 @@ int run_forward_infer(const Run& r, const float* d_x, float* d_out) {
         int pooled_done = 0;
         RC(conv(m->enc_c2(i), &pooled_done));
         const BN& b = m->bn[m->conv[m->enc_c2(i)].bn];
-        if (!pooled_done) RC(launch_maxpool(dt, r.t(b.y), r.B, m->cfg.H >> i, m->cfg.W >> i, b.C, r.t(b.pooled), r.st));
+        if (!pooled_done) {
+            RC(launch_maxpool(dt, r.t(b.y), r.B, m->cfg.H >> i, m->cfg.W >> i, b.C, r.t(b.pooled), r.st));
+            tap_aux(r, 9, (int)(&b - &m->bn[0]), i, b.C, b.C, r.t(b.y), nullptr, nullptr, nullptr, r.t(b.pooled), 0, 0);
+        }
     }
     RC(conv(m->bot_c1()));
     RC(conv(m->bot_c2()));
@@ -551,13 +559,17 @@ int run_forward_infer(const Run& r, const float* d_x, float* d_out) {
         RC(conv(m->up_c(j, 2), nullptr, last ? &hf : nullptr));
         if (head_done) {
             float* out = d_out ? d_out : (float*)r.at(P.probs);
-            return launch_head_combine(hf.partial, M0, m->cfg.n_classes, r.params + m->head_b, m->cfg.softmax, out, r.st);
+            RC(launch_head_combine(hf.partial, M0, m->cfg.n_classes, r.params + m->head_b, m->cfg.softmax, out, r.st));
+            tap_aux(r, 10, -1, 0, m->head_C, m->cfg.n_classes, hf.partial, nullptr, nullptr, nullptr, out, m->head_w, m->head_b);
+            return MPU_OK;
         }
     }
     const void* prev = r.t(m->conv.back().in0);             // (the head reads the last up block's output)
     float* out = d_out ? d_out : (float*)r.at(P.probs);
-    return launch_head_forward(dt, prev, M0, m->head_C, m->cfg.n_classes, r.params + m->head_w, m->cfg.n_classes,
-                               r.params + m->head_b, m->cfg.softmax, out, r.st);
+    RC(launch_head_forward(dt, prev, M0, m->head_C, m->cfg.n_classes, r.params + m->head_w, m->cfg.n_classes,
+                           r.params + m->head_b, m->cfg.softmax, out, r.st));
+    tap_aux(r, 6, -1, 0, m->head_C, m->cfg.n_classes, prev, nullptr, nullptr, nullptr, out, m->head_w, m->head_b);
+    return MPU_OK;
 }
 
 int run_forward(const Run& r, const float* d_x, int training, float* d_out) {

@@ -13,6 +13,22 @@ bias gradient 2e-3 of the tensor max (fp32 sums of exact bf16 products).
 
 Forward and data-gradient references are evaluated on the first CMP images of the batch (a convolution's output for
 an image depends on that image only); weight gradients sum over the whole batch and are evaluated on all of it.
+
+The INFERENCE forward (run_forward_infer: every `mp predict`, the benchmark's predict leg) is replayed the same way
+(_replay_inference, four small networks and three schedule switches). Its launches report as kind 0 (conv without a BatchNorm),
+kind 8 (conv with the folded BatchNorm: out = s * relu(conv + b) + t, optionally its 2x2 max pooling as a second output, optionally
+the 1x1 head's partial logits INSTEAD of the output), kind 9 (separate max pooling), kind 10 (head combine) and kind 6 (separate
+head). References and bounds (tests/replay_ref.py; checked against a torch-f32 emulation in tests/test_replay_bounds_host.py):
+  convs, on the first and the last image      1.2e-2 of the tensor max AND, per output channel, 1.2e-2 of the channel max (a channel
+                                              below 1e-3 of the tensor max: 1.2e-5 of the tensor max) -- a wrong scale or shift on a
+                                              small channel cannot hide under a large one
+  s, t of every kind-8 launch                 1e-6 of the vector max against fp64 gamma / sqrt(var + eps), beta - mean * s
+  pooled outputs, fused or kind 9             equal to the 2x2 max of the stored tensor (negative gammas: the pool follows the affine)
+  partial logits of the fused head            p0 + p1 and each half of 32 channels against bf16round(ref) @ Wh:
+                                              sum_c |Wh| * 2^-8 * |ref_c| + 1e-5 * sum_c |Wh * ref_c| per pixel and class
+  probabilities (kind 10, kind 6)             2e-5 absolute against the fp64 softmax of the launch's own inputs
+and completeness: 5 * depth + 2 conv launches, each conv once; exactly one head; `depth` pooled tensors; the returned
+probabilities are the last head launch's output.
 """
 import ctypes as C
 
@@ -21,7 +37,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _devcopy import hip as _hip, d2h_bf16 as _d2h_bf16, d2h_f32 as _d2h_f32, d2h_u8 as _d2h_u8
+from _devcopy import hip as _hip, d2h_bf16 as _d2h_bf16, d2h_f32 as _d2h_f32, d2h_u8 as _d2h_u8, d2h_rows as _d2h_rows
+
+C_ = C                                                           # (the inference replay calls a channel count C)
 
 pytestmark = pytest.mark.gpu
 quiet = lambda *a, **k: None
@@ -380,3 +398,217 @@ def test_cfg1_bf16_step_every_non_conv_launch_against_fp64_on_its_own_inputs():
         assert ew <= 2e-3 and eb <= 2e-3, (kind, w_off, ew, eb)
     print("replay (non-conv): bn fwd %.3g, bn bwd %.3g, pool bwd %.3g, head fwd %.3g (abs), head bwd %.3g; fp32 reductions %.3g"
           % (worst[3], worst[4], worst[5], worst[6], worst[7], worst_red))
+
+
+# ---- the inference forward (run_forward_infer), launch by launch -------------------------------------------------------------
+def _replay_inference(K, C, depth, cf, B, H, W, tag="", seed=21):
+    """One bf16 inference forward with the launch tap and the schedule log on. Every launch it reports (kinds 0, 6, 8, 9, 10 of
+    mpu_launch_info) is recomputed on torch-CPU / NumPy in fp64 from the launch's own inputs and compared under the bounds of
+    tests/replay_ref.py; conv outputs on the first and the last image of the batch (the last one sits in the ragged tail of the
+    tile walk), everything else on the whole batch. Returns what the callers assert their schedules from."""
+    import replay_ref as R
+    from multiplanarunet_amd import _lib
+    from multiplanarunet_amd.unet import UNet
+    from oracle import unet_ref as U
+    from test_gpu_unet import rand_weights
+    hip = _hip()
+    w0 = rand_weights(U, K, C, depth, cf, seed=seed)
+    x = np.random.RandomState(seed + 2).randn(B, H, W, C).astype(np.float32)
+    m = UNet(n_classes=K, img_rows=H, img_cols=W, n_channels=C, depth=depth, complexity_factor=cf, dtype="bf16", logger=quiet)
+    m.set_weights_dict(w0)
+    params = m.params.cpu().numpy().astype(np.float64)
+    state = m.bn_state.cpu().numpy().astype(np.float64)
+    bn_names = [n[:-len("/gamma")] for n in m._keras_order() if n.endswith("/gamma")]
+    _k, hw_off, hps, _l = m._tensors["conv2d/kernel"]
+    head_C = hps[2]
+    Wh_all = params[hw_off:hw_off + head_C * K].reshape(head_C, K)
+    bh_off = m._tensors["conv2d/bias"][1]
+    imgs = sorted({0, B - 1})
+    lib = _lib.load()
+    EPS = 1e-3
+
+    def rows(ptr, shape):                                   # the compared images of a device bf16 tensor, fp64
+        return torch.cat([_d2h_rows(hip, ptr, shape, True, i, i + 1) for i in imgs])
+
+    recs, failures = [], []
+    worst = {"tensor": 0.0, "channel": 0.0, "coeff": 0.0, "head_partial": 0.0, "combine": 0.0, "head": 0.0}
+    last_head_out = [None]
+
+    def check(li):
+        kind = li.kind
+        rec = {"kind": kind, "conv_index": li.conv_index, "pooled": bool(li.mask) if kind == 8 else kind == 9,
+               "head": kind == 8 and bool(li.dz), "bn": li.n_off if kind == 8 else -1}
+        recs.append(rec)
+        Hh, Ww = li.H, li.W
+        if kind in (0, 8):
+            kk = 2 if li.mode == 1 else 3
+            Hi, Wi = (Hh // 2, Ww // 2) if li.mode == 1 else (Hh, Ww)
+            Cin, Co = li.C0 + li.C1, li.Cout
+            xin = rows(li.in0, (B, Hi, Wi, li.C0))
+            if li.C1:
+                xin = torch.cat([xin, rows(li.in1, (B, Hi, Wi, li.C1))], -1)
+            wk = _bf16_round(params[li.w_off:li.w_off + kk * kk * Cin * Co].reshape(kk, kk, Cin, Co))
+            bk = torch.tensor(params[li.b_off:li.b_off + Co])
+            if kind == 8:
+                assert li.aux0 and li.aux1 and 0 <= li.n_off < len(bn_names), ("kind 8 fields", li.conv_index, li.n_off)
+                s, t = _d2h_f32(hip, li.aux0, (Co,)), _d2h_f32(hip, li.aux1, (Co,))
+                tn = lambda v: m._tensors[bn_names[li.n_off] + "/" + v]
+                assert tn("gamma")[2] == (Co,), (li.conv_index, li.n_off, tn("gamma")[2], Co)
+                g, bt = params[tn("gamma")[1]:][:Co], params[tn("beta")[1]:][:Co]
+                mm, mv = state[tn("moving_mean")[1]:][:Co], state[tn("moving_variance")[1]:][:Co]
+                s_ref = g / np.sqrt(mv + EPS); t_ref = bt - mm * s_ref
+                e = max(np.abs(s - s_ref).max() / np.abs(s_ref).max(), np.abs(t - t_ref).max() / np.abs(t_ref).max())
+                worst["coeff"] = max(worst["coeff"], float(e))
+                assert e <= 1e-6, ("folded BatchNorm coefficients", li.conv_index, li.n_off, e)
+            else:
+                s, t = np.ones(Co), np.zeros(Co)
+            ref = R.affine_relu_conv(li.mode, xin, wk, bk, torch.tensor(s), torch.tensor(t)).numpy()
+            if li.out:
+                got = rows(li.out, (B, Hh, Ww, Co)).numpy()
+                e_t, e_c, c = R.conv_bound_ratios(got, ref)
+                rec["e_t"], rec["e_c"] = e_t, e_c
+                worst["tensor"], worst["channel"] = max(worst["tensor"], e_t), max(worst["channel"], e_c)
+                assert e_t <= R.CONV_TOL, ("conv, tensor-wise", kind, li.conv_index, e_t, ref.shape)
+                assert e_c <= 1.0, ("conv, per channel (fraction of its bound)", kind, li.conv_index, c, e_c, ref.shape)
+            else:
+                assert kind == 8 and li.dz, ("a conv launch without an output", kind, li.conv_index)
+            if kind == 8 and li.mask:                       # pooled = 2x2 max of the STORED output, exactly
+                assert li.out, ("pooled output without the tensor it pools", li.conv_index)
+                full = _d2h_bf16(hip, li.out, (B, Hh, Ww, Co))
+                assert np.array_equal(_d2h_bf16(hip, li.mask, (B, Hh // 2, Ww // 2, Co)), R.pool2x2(full)), \
+                    ("fused pool", li.conv_index)
+            if kind == 8 and li.dz:                         # the head out of the epilogue: two halves of 32 channels, no bias
+                assert Co == head_C == 64 and li.out is None, ("fused head", Co, head_C, li.out)
+                part = _d2h_f32(hip, li.dz, (2, B, Hh, Ww, K))[:, imgs]
+                e = max(R.head_partial_ratio(part[0] + part[1], ref, Wh_all),
+                        R.head_partial_ratio(part[0], ref[..., :32], Wh_all[:32]),
+                        R.head_partial_ratio(part[1], ref[..., 32:], Wh_all[32:]))
+                worst["head_partial"] = max(worst["head_partial"], e)
+                assert e <= 1.0, ("fused head partial logits (fraction of the bound)", e)
+        elif kind == 9:
+            yy = _d2h_bf16(hip, li.in0, (B, Hh, Ww, li.C0))
+            assert np.array_equal(_d2h_bf16(hip, li.out, (B, Hh // 2, Ww // 2, li.C0)), R.pool2x2(yy)), ("maxpool", li.conv_index)
+        elif kind in (6, 10):
+            bh = params[li.b_off:li.b_off + li.Cout]
+            assert li.Cout == K and li.b_off == bh_off and li.w_off == hw_off, ("head fields", li.Cout, li.w_off, li.b_off)
+            got = _d2h_f32(hip, li.out, (B, Hh, Ww, K))
+            if kind == 10:
+                part = _d2h_f32(hip, li.in0, (2, B, Hh, Ww, K))
+                e = float(np.abs(got - R.softmax64(part[0] + part[1] + bh)).max())
+                worst["combine"] = max(worst["combine"], e)
+            else:
+                n_ = _d2h_bf16(hip, li.in0, (B, Hh, Ww, li.C0))
+                e = float(np.abs(got - R.softmax64(n_ @ Wh_all + bh)).max())
+                worst["head"] = max(worst["head"], e)
+            assert e <= 2e-5, ("head probabilities", kind, e)
+            last_head_out[0] = got
+
+    def on_launch(_user, pinfo):                            # (an exception cannot cross the C frame: kept for the caller)
+        try:
+            torch.cuda.synchronize()
+            check(pinfo.contents)
+        except BaseException as e:
+            import traceback
+            failures.append("%r\n%s" % (e, traceback.format_exc(limit=3)))
+
+    cb = _lib.LAUNCH_TAP_FN(on_launch)
+    _lib.call("mpu_unet_set_launch_tap", m._h, C_.cast(cb, C_.c_void_p), None)
+    lib.mpu_schedule_log_enable(1)
+    try:
+        probs = m._forward(m._as_input(x), training=False)
+        torch.cuda.synchronize()
+        nlog = lib.mpu_schedule_log_read(None, 0)
+        lbuf = C_.create_string_buffer(int(nlog) + 1)
+        lib.mpu_schedule_log_read(lbuf, nlog + 1)
+    finally:
+        lib.mpu_schedule_log_enable(0)
+        _lib.call("mpu_unet_set_launch_tap", m._h, None, None)
+    assert not failures, "%d launches failed; the first:\n%s" % (len(failures), failures[0])
+
+    # completeness: every conv exactly once, one head, `depth` pooled tensors, and the returned probabilities are the head's
+    convs = [r for r in recs if r["kind"] in (0, 8)]
+    lines = [l for l in lbuf.value.decode().splitlines() if l.startswith("conv ")]
+    assert sorted(r["conv_index"] for r in convs) == list(range(5 * depth + 2)), sorted(r["conv_index"] for r in convs)
+    assert len(lines) == len(convs), (len(lines), len(convs))
+    for r, l in zip(convs, lines):
+        r["sched"] = l.split()[1]
+        assert ("pool=1" in l) == r["pooled"] and ("head=1" in l) == r["head"], (l, r)
+    assert sum(r["kind"] == 8 for r in recs) == 3 * depth + 1 and sum(r["kind"] == 0 for r in recs) == 2 * depth + 1
+    heads = [r["kind"] for r in recs if r["kind"] in (6, 10) or r["head"]]
+    assert heads in ([6], [8, 10]), heads
+    assert recs[-1]["kind"] in (6, 10)
+    assert sum(r["pooled"] for r in recs) == depth, [(r["kind"], r["conv_index"]) for r in recs if r["pooled"]]
+    assert np.array_equal(probs.cpu().numpy().astype(np.float64), last_head_out[0])
+    by = {}
+    for r in recs:
+        key = "%d:%s" % (r["kind"], r.get("sched", "-")) + ("+pool" if r["kind"] == 8 and r["pooled"] else "") + \
+              ("+head" if r["head"] else "")
+        by[key] = by.get(key, 0) + 1
+    print("replay (inference %s): %d conv launches worst %.3g of the tensor max, per channel %.3g of its bound, coefficients %.3g; "
+          "head partials %.3g of their bound, combine %.3g abs, head kernel %.3g abs; kind:schedule %s"
+          % (tag, len(convs), worst["tensor"], worst["channel"], worst["coeff"], worst["head_partial"], worst["combine"],
+             worst["head"], " ".join("%s=%d" % kv for kv in sorted(by.items()))))
+    return {"recs": recs, "lines": lines, "worst": worst, "depth": depth}
+
+
+def _kinds(res):
+    return [r["kind"] for r in res["recs"]]
+
+
+def test_inference_net_a_ws_fused_pool_and_head_halo_splitk_every_launch_against_fp64():
+    """Network A: K 3, depth 3, cf 1, 8 images of 128 x 160 -- 1280 tiles at level 0: conv_ws with the fused pool and the fused
+    head (K <= 8); levels 1-2 on the halo kernels with a ragged W tile (80 = 2.5 x 32); the deep levels on the split-K / glds
+    schedules. The schedule switches of test_inference_net_a_under_schedule_switches_subprocess are read from the environment
+    (once per process by the library): what each forces is asserted here."""
+    import os
+    res = _replay_inference(3, 1, 3, 1, 8, 128, 160, tag="A")
+    lines, kinds = res["lines"], _kinds(res)
+    unfused = os.environ.get("MPU_FUSED_POOL") == "0" and os.environ.get("MPU_FUSED_HEAD") == "0"
+    if unfused:
+        assert kinds.count(9) == 3 and kinds.count(6) == 1 and kinds.count(10) == 0, kinds
+        assert not any("pool=1" in l or "head=1" in l for l in lines), lines
+    else:
+        assert any(l.split()[1] == "ws" and "head=1" in l for l in lines), lines
+        assert sum("pool=1" in l for l in lines) >= 2, lines
+        assert kinds.count(10) == 1 and kinds.count(6) == 0, kinds
+    if os.environ.get("MPU_HALO16_MIN") == "1" and os.environ.get("MPU_HALO16P_WGS") == "5":
+        p = [l for l in lines if l.split()[1] == "halo16p"]
+        assert len(p) >= 6 and any("pool=1" in l for l in p), lines
+
+
+def test_inference_net_b_channel_tails_unfused_head_every_launch_against_fp64():
+    """Network B: K 5, 2 input channels, depth 2, cf 2 (90 / 181 / 362 filters: channel tails in every layer and in the scale /
+    shift vectors), 3 images of 48 x 40; the head runs as its own kernel (kind 6)."""
+    res = _replay_inference(5, 2, 2, 2, 3, 48, 40, tag="B")
+    assert _kinds(res).count(6) == 1 and _kinds(res).count(10) == 0, _kinds(res)
+
+
+def test_inference_net_c_wide_fused_head_every_launch_against_fp64():
+    """Network C: K 16, depth 1, 8 images of 128 x 128 (1024 tiles: exactly conv_ws's bound): the wide (K <= 16) fused head."""
+    res = _replay_inference(16, 1, 1, 1, 8, 128, 128, tag="C")
+    assert any(l.split()[1] == "ws" and "head=1" in l for l in res["lines"]), res["lines"]
+    assert _kinds(res).count(10) == 1, _kinds(res)
+
+
+def test_inference_net_d_tiny_maps_separate_maxpool_every_launch_against_fp64():
+    """Network D: K 3, depth 4, cf 0.25, 5 images of 16 x 32: the bottom works on 1 x 2 maps, the last pooling goes 2 x 4 -> 1 x 2,
+    and W < 32 below level 0 keeps the layers off the patch kernels and the pooling mostly on the separate kernel (kind 9)."""
+    res = _replay_inference(3, 1, 4, 0.25, 5, 16, 32, tag="D")
+    assert _kinds(res).count(9) >= 1, _kinds(res)
+
+
+@pytest.mark.parametrize("switches", [{"MPU_HALO16_MIN": "1", "MPU_HALO16P_WGS": "5"},
+                                      {"MPU_FUSED_POOL": "0", "MPU_FUSED_HEAD": "0"},
+                                      {"MPU_HALO_UP8_MIN": "1"}], ids=["halo16p_5wgs", "unfused_pool_and_head", "halo_up8"])
+def test_inference_net_a_under_schedule_switches_subprocess(switches):
+    """The library reads a schedule switch once per process, hence a fresh interpreter per set, one at a time: network A's replay
+    under the persistent 16-row kernel on every eligible layer with 5 workgroups (each walks many tiles), with the separate
+    max-pool and head kernels, and with the 8-row up-conv schedule from the smallest grid on."""
+    import os, subprocess, sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_gpu_replay.py"), "-x", "-q", "-s", "-k",
+                        "test_inference_net_a_ws_fused_pool_and_head"], env=dict(os.environ, **switches), capture_output=True,
+                       text=True, cwd=os.path.dirname(here))
+    print("\n".join(l for l in r.stdout.splitlines() if l.startswith("replay (inference")))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "1 passed" in r.stdout, r.stdout[-2000:]
