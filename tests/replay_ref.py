@@ -1,5 +1,6 @@
-"""Reference arithmetic and bounds of the inference replay (tests/test_gpu_replay.py), NumPy / torch-CPU only, so that the bounds
-themselves can be checked without a GPU (tests/test_replay_bounds_host.py).
+"""Reference arithmetic and bounds of the inference replay and of the train-step replay's non-conv launches
+(tests/test_gpu_replay.py), NumPy / torch-CPU only, so that the bounds themselves can be checked without a GPU
+(tests/test_replay_bounds_host.py).
 
 An inference conv launch stores  y = s * relu(conv(x, w) + b) + t  rounded ONCE to bf16 (s, t: the folded BatchNormalization of
 mpu_unet_prepare_inference; s = 1, t = 0 for a conv without one); x and w are bf16, the sums and the affine are f32.
@@ -41,14 +42,15 @@ def affine_relu_conv(mode, x, w, b, s, t):
     return s * torch.relu(layer_forward(mode, x, w, b)) + t
 
 
-def conv_bound_ratios(got, ref):
-    """(max |got - ref| / max |ref|, worst per-channel error as a fraction of ITS bound, that channel) of [..., C] arrays."""
+def conv_bound_ratios(got, ref, tol=CONV_TOL):
+    """(max |got - ref| / max |ref|, worst per-channel error as a fraction of ITS bound, that channel) of [..., C] arrays; `tol`:
+    the relative bound, of the tensor's and of a channel's maximum alike (CONV_TOL for bf16 storage)."""
     got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64)
     Cn = ref.shape[-1]
     err = np.abs(got - ref).reshape(-1, Cn).max(0)
     cmax = np.abs(ref).reshape(-1, Cn).max(0)
     tmax = float(cmax.max()) + 1e-300
-    lim = np.where(cmax >= DEAD * tmax, CONV_TOL * cmax, CONV_TOL * DEAD * tmax)
+    lim = np.where(cmax >= DEAD * tmax, tol * cmax, tol * DEAD * tmax)
     ratio = err / lim
     c = int(ratio.argmax())
     return float(err.max() / tmax), float(ratio[c]), c
@@ -75,3 +77,116 @@ def pool2x2(y):
     """MaxPooling2D(2) of [B, H, W, C] (an odd last row / column is dropped)."""
     B, H, W, Cn = y.shape
     return y[:, :H // 2 * 2, :W // 2 * 2].reshape(B, H // 2, 2, W // 2, 2, Cn).max((2, 4))
+
+
+# ---- the training step's non-conv launches (kinds 3-7 of mpu_launch_info) ------------------------------------------------------
+# Each formula is written once, on torch tensors, in the dtype of its arguments: fp64 is the reference of the GPU replay, f32 the
+# emulation that sets the f32-storage bounds (tests/test_replay_bounds_host.py).
+BN_EPS = 1e-3                                    # Keras BatchNormalization default
+
+
+def bn_stats(x):
+    """Batch statistics of [..., C]: (mean, 1 / sqrt(var + eps)), var = E[x^2] - mean^2 clamped at 0 (the kernels' formula)."""
+    Cn = x.shape[-1]
+    xf = x.reshape(-1, Cn)
+    M = xf.shape[0]
+    mu = xf.sum(0) / M
+    var = ((xf * xf).sum(0) / M - mu * mu).clamp_min(0.0)
+    return mu, 1.0 / torch.sqrt(var + BN_EPS)
+
+
+def bn_out(x, mean, inv, gamma, beta, affine=False):
+    """gamma * (x - mean) * inv + beta; affine=True: the same value as x * scale + shift, scale = gamma * inv,
+    shift = beta - mean * scale (the form the kernels evaluate)."""
+    if affine:
+        scale = gamma * inv
+        return x * scale + (beta - mean * scale)
+    return gamma * (x - mean) * inv + beta
+
+
+def bn_bwd(dn, x, mean, inv, gamma, affine=False):
+    """BatchNorm backward through the ReLU in front of it, from the statistics given: (dz, dgamma, dbeta);
+    dz = [x > 0] * gamma * inv * (dn - dbeta / M - xhat * dgamma / M). affine=True: dz as k1 * dn + k2 * x + k3 (the kernels' form)."""
+    Cn = x.shape[-1]
+    M = x.numel() // Cn
+    xh = (x - mean) * inv
+    red = tuple(range(x.dim() - 1))
+    dbeta = dn.sum(red); dgamma = (dn * xh).sum(red)
+    if affine:
+        k1 = gamma * inv
+        k2 = -k1 * (dgamma / M) * inv
+        dxx = k1 * dn + k2 * x + (-k1 * (dbeta / M) - k2 * mean)
+    else:
+        dxx = gamma * inv * (dn - dbeta / M - xh * dgamma / M)
+    return torch.where(x > 0, dxx, torch.zeros((), dtype=x.dtype)), dgamma, dbeta
+
+
+def pool_bwd_skip(n, dskip, dp):
+    """dskip + the pooled gradient dp routed to the FIRST maximum (row-major) of every 2 x 2 window of n; NumPy [B, H, W, C]."""
+    B, H, W, Cn = n.shape
+    win = n.reshape(B, H // 2, 2, W // 2, 2, Cn).transpose(0, 1, 3, 5, 2, 4).reshape(B, H // 2, W // 2, Cn, 4)
+    first = win.argmax(-1)                                           # np.argmax: the first maximum
+    routed = np.zeros_like(win)
+    np.put_along_axis(routed, first[..., None], dp[..., None], -1)
+    routed = routed.reshape(B, H // 2, W // 2, Cn, 2, 2).transpose(0, 1, 4, 2, 5, 3).reshape(B, H, W, Cn)
+    return dskip + routed
+
+
+def head_fwd(n, Wh, bh):
+    return torch.softmax(n @ Wh + bh, -1)
+
+
+def head_bwd(n, y, w, Wh, bh, loss):
+    """(dn, dWh, dbh) of sum(loss(softmax(n @ Wh + bh), y, w)) by autograd; loss: oracle/unet_ref.py keras_sparse_ce."""
+    n = n.detach().clone().requires_grad_(True)
+    Wh = Wh.detach().clone().requires_grad_(True)
+    bh = bh.detach().clone().requires_grad_(True)
+    loss(head_fwd(n, Wh, bh), y, w.to(n.dtype)).sum().backward()
+    return n.grad, Wh.grad, bh.grad
+
+
+def rel_max(got, ref):
+    got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64)
+    return float(np.abs(got - ref).max() / (np.abs(ref).max() + 1e-30))
+
+
+# Bounds of the non-conv kinds. bf16 storage: the numbers of the project's per-launch replay (tests/test_gpu_replay.py). f32 storage
+# (dtypes "bf16x3", "f32"): 3 x (the suite's noise_mult) the worst error of a torch-f32 evaluation of the formulas above -- both
+# forms -- against fp64 on the BatchNorm / head shapes of networks T1-T3, measured by tests/test_replay_bounds_host.py
+# (test_f32_emulation_sets_the_f32_storage_bounds_of_the_non_conv_kinds holds each number between 3 x and 10 x its measurement);
+# the pool backward stores ONE rounding of an exact two-term sum, so its bound is the unit roundoff of the format. Probabilities
+# are f32 sums and an f32 softmax whatever the storage type of the head's input: 2e-5 absolute in every dtype.
+TOL_BF16 = {"out": CONV_TOL, "stats": 1e-4, "reduce": 2e-3, "pool": 2.0 ** -8, "probs": 2e-5, "conv": CONV_TOL, "wgrad": 2e-3}
+TOL_F32 = {"out": 4.2e-5, "stats": 5.5e-7, "reduce": 7e-7, "pool": 2.0 ** -24, "probs": 2e-5, "conv": 5e-5, "wgrad": 5e-5}
+
+# dtype "bf16x3": an operand is hi + lo, two bf16 numbers: x = hi + r with |r| <= u |x| (u = U_BF16), lo = bf16(r) with
+# |r - lo| <= u^2 |x|. A product is hi hi' + hi lo' + lo hi': the dropped lo lo' and the two representation errors are each
+# <= u^2 |x w| (to first order), so |error of a product| <= 3 u^2 |x w| = 4.6e-5 |x w|; plus 1e-5 |x w| for the f32 sums, the share
+# head_partial_ratio gives them. Per output element: |got - ref| <= X3_PRODUCT * (sum |x| |w| + |b|).
+X3_PRODUCT = 3 * U_BF16 ** 2 + 1e-5
+
+# Fixed-point accumulators (multiplanarunet_amd/csrc/unet_model.hip): units per 1.0
+BN_ACC_F = (2.0 ** 24, 2.0 ** 16)                # forward sum x, sum x^2
+BN_ACC_B = 2.0 ** 40                             # backward sum dn, sum dn * xhat (dbeta, dgamma)
+DB_ACC_SCALE = 2.0 ** 44                         # bias gradient of dtype "bf16x3"
+
+
+def acc_adds(M):
+    """Upper bound of the addends one (statistic, channel) of an accumulator receives from M pixels: a producer adds ONE rounded
+    column sum per workgroup (kernels.h: stats_acc_add, __double2ll_rn), and a workgroup covers at least one pixel. (The conv
+    epilogues cover 64 and more; the split-K finish and the column reductions are sized by elements, a few pixels each at the
+    widest layers -- so no tighter count is claimed here.)"""
+    return int(M)
+
+
+def acc_sum_error(M, units):
+    """Absolute error of a SUM that came out of a fixed-point accumulator: half a unit (round to nearest) per workgroup add."""
+    return acc_adds(M) * 0.5 / units
+
+
+def acc_stats_error(M, mean, inv):
+    """Absolute errors (d_mean, d_inv) per channel that the forward units add to mean and 1 / sqrt(var + eps) over M values:
+    d_mean = adds * 2^-25 / M; d_var = adds * 2^-17 / M + 2 |mean| d_mean; d_inv = inv^3 / 2 * d_var (first order)."""
+    d_mean = acc_sum_error(M, BN_ACC_F[0]) / M
+    d_var = acc_sum_error(M, BN_ACC_F[1]) / M + 2.0 * np.abs(mean) * d_mean
+    return d_mean, 0.5 * np.asarray(inv, np.float64) ** 3 * d_var

@@ -19,8 +19,6 @@ no NaN and no error.
     the forward does not depend on the sample weight and the backward is linear in it, so scaling w by a power of two scales every
     gradient by exactly that power (every bf16 / f32 rounding scales with it).
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -82,7 +80,6 @@ RANGE_CASES = [
                          ids=["bf16x3_b16_128_w32_16", "bf16x3_b32_256_w8_4", "bf16_b32_256_w128_64", "bf16_b16_128_w2e-20"])
 def test_accumulator_sums_at_stressed_ranges_against_fp64_on_each_launchs_inputs(dtype, B, dim, w, premise):
     """Per-image weights alternate between images, so that a wrong image index in the weighting shows."""
-    from multiplanarunet_amd import _lib
     h = hip()
     m, x, y = _setup(dtype, B, dim, seed=SEED)
     sw = np.where(np.arange(B) % 2 == 0, w[0], w[1]).astype(np.float32)
@@ -91,7 +88,7 @@ def test_accumulator_sums_at_stressed_ranges_against_fp64_on_each_launchs_inputs
     torch.set_num_threads(max(1, torch.get_num_threads()))
     seen = {2: 0, 3: 0, 4: 0}
     margin = {"forward": 0.0, "backward": 0.0, "bias": 0.0}      # largest |sum| * units / 2^63 per family
-    stat_err, dz_err, bn_sums, db_sums, errors = [], [], [], [], []
+    stat_err, dz_err, bn_sums, db_sums = [], [], [], []
 
     def chunks(ptr, shape):
         for lo in range(0, B, CHUNK):
@@ -137,26 +134,15 @@ def test_accumulator_sums_at_stressed_ranges_against_fp64_on_each_launchs_inputs
             if not bf16:                                             # (bf16: the bias gradients are fp32 partial rows)
                 grow("bias", float(db.abs().max()) * UNITS_DB / TWO63)
 
-    def on_launch(_user, pinfo):
-        li = pinfo.contents
-        if li.kind not in seen:
-            return
-        torch.cuda.synchronize()
-        seen[li.kind] += 1
-        try:
+    def on_launch(li):
+        if li.kind in seen:
+            seen[li.kind] += 1
             replay(li)
-        except BaseException as ex:                                  # (an exception cannot cross the ctypes callback)
-            errors.append(ex)
 
-    cb = _lib.LAUNCH_TAP_FN(on_launch)
-    _lib.call("mpu_unet_set_launch_tap", m._h, C.cast(cb, C.c_void_p), None)
-    try:
+    from replay_tap import tapped
+    with tapped(m, on_launch):                                       # (an exception cannot cross the ctypes callback: replay_tap.py)
         m.forward_backward(x, y, sw, want_loss=False)
         torch.cuda.synchronize()
-    finally:
-        _lib.call("mpu_unet_set_launch_tap", m._h, None, None)
-    if errors:
-        raise errors[0]
     g = m.grads.cpu().numpy().astype(np.float64)
     assert seen == {2: 22, 3: 13, 4: 13}, seen
 
