@@ -268,19 +268,38 @@ __global__ __launch_bounds__(256) void sample_view_planes_kernel(A a) {
     }
 }
 
+// ---- the work list of a straight-line kernel, as its fix-up kernel reads it ---------------------------------
+// `count` entries of `list` are to be redone, or all `total` elements when the list overflowed (count > cap). Every
+// fix-up kernel also zeroes the counter of the stream's next call (run_with_fixup).
+struct WorkList { const unsigned* list; long m; bool all; };
+__device__ __forceinline__ WorkList worklist_open(const unsigned* list, const unsigned* count, unsigned cap, unsigned* next_count,
+                                                  long total) {
+    const unsigned n = *count;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *next_count = 0;
+    const bool all = n > cap;
+    return {list, all ? total : (long)n, all};
+}
+__device__ __forceinline__ long worklist_at(const WorkList& w, long i) { return w.all ? i : (long)w.list[i]; }
+// the straight-line kernel's side: append element t (the count goes on past cap: that is the overflow mark)
+__device__ __forceinline__ void worklist_push(unsigned* list, unsigned* count, unsigned cap, long t) {
+    const unsigned idx = atomicAdd(count, 1u);
+    if (idx < cap) list[idx] = (unsigned)t;
+}
+// row-major element index t of an [n0, n1, n2] array -> (i0, i1, i2)
+__device__ __forceinline__ void split3(long t, int n1, int n2, int& i0, int& i1, int& i2) {
+    i2 = (int)(t % n2); i1 = (int)((t / n2) % n1); i0 = (int)(t / ((long)n2 * n1));
+}
+
 // exact recomputation of the samples on the straight-line kernel's work list (all samples if the list overflowed)
 template <typename A>
 __global__ __launch_bounds__(256) void sample_fixup_kernel(A a, const unsigned* list, const unsigned* count, unsigned cap,
                                                            unsigned* next_count) {
     const double* tab = stage_scaler(a);
-    const unsigned n = *count;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *next_count = 0;
-    const long total = (long)a.P * a.dim * a.dim;
-    const bool all = n > cap;
-    const long m = all ? total : (long)n;
-    for (long k = (long)blockIdx.x * 256 + threadIdx.x; k < m; k += (long)gridDim.x * 256) {
-        const long t = all ? k : (long)list[k];
-        sample_one(a, (int)(t / ((long)a.dim * a.dim)), (int)((t / a.dim) % a.dim), (int)(t % a.dim), tab);
+    const WorkList wl = worklist_open(list, count, cap, next_count, (long)a.P * a.dim * a.dim);
+    for (long k = (long)blockIdx.x * 256 + threadIdx.x; k < wl.m; k += (long)gridDim.x * 256) {
+        int p, i, j;
+        split3(worklist_at(wl, k), a.dim, a.dim, p, i, j);
+        sample_one(a, p, i, j, tab);
     }
 }
 
@@ -366,8 +385,7 @@ __global__ __launch_bounds__(256) void sample_fast_kernel(A a, unsigned* list, u
     const CellF c2 = cell_uniform<KIND>(a.az, rz, oob, risky);
     const long t = ((long)p * a.dim + i) * a.dim + j;
     if (__builtin_expect(risky, 0)) {                  // redone (and stored) by sample_fixup_kernel
-        const unsigned idx = atomicAdd(count, 1u);
-        if (idx < cap) list[idx] = (unsigned)t;
+        worklist_push(list, count, cap, t);
         return;
     }
     // the two z-neighbours of an (x, y) corner are contiguous: one 8-byte (C == 1) / 16-byte (C == 2) load per corner,
@@ -488,6 +506,28 @@ __device__ __forceinline__ void softmax_argmax_store(float (&z)[K], bool do_soft
     }
 }
 
+// ---- FusionModel on one voxel (models/fusion_model.py:38-39): z = sum_v W[v] * x_v + b, softmax; sum_fusion: z = sum_v x_v.
+// Views are accumulated in order, one f32 multiply and one f32 add per view and class; every fused kernel uses these.
+// The accumulate step is a unit per CLASS and the finish is the pair fuse_add_bias + softmax_argmax_store at the call site:
+// with the class loop, or both halves of the finish, inside one unit the compiler simplified that unit on its own before
+// inlining it and the register allocation of several instantiations moved (an occupancy step at K >= 10, 20 bytes of
+// scratch in two fp64-screen kernels; compiles for gfx950, resource usage compared kernel by kernel).
+// fuse_add reads its weight W[i] only when !sum_fusion (W may be NULL otherwise): W is the weight matrix itself where a
+// lane has one voxel, a register copy of the view's row (fuse_weight) where it has four.
+__device__ __forceinline__ float fuse_weight(const float* W, int i, int sum_fusion) { return sum_fusion ? 1.f : W[i]; }
+__device__ __forceinline__ float fuse_add(float z, const float* W, int i, float x, int sum_fusion) {
+    return sum_fusion ? (z + x) : (z + W[i] * x);
+}
+template <int K>
+__device__ __forceinline__ void fuse_add_bias(float (&z)[K], const float* b, int sum_fusion) {
+    if (!sum_fusion) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) z[k] = z[k] + b[k];
+    }
+}
+// class k of the K-vector of a voxel outside a view's box
+__device__ __forceinline__ float background(int k) { return k == 0 ? 1.f : 0.f; }
+
 constexpr int MAX_VIEWS = 16;
 struct FuseArgs {
     GridDev grid; ViewDev views[MAX_VIEWS]; int V;
@@ -545,27 +585,24 @@ __global__ __launch_bounds__(256) void map_fuse_kernel(FuseArgs a) {
         }
         float w[K];
 #pragma unroll
-        for (int k = 0; k < K; ++k) w[k] = a.sum_fusion ? 1.f : a.W[v * K + k];
+        for (int k = 0; k < K; ++k) w[k] = fuse_weight(a.W, v * K + k, a.sum_fusion);
 #pragma unroll
         for (int u = 0; u < FZ; ++u) {
             float x[K];                                   // one K-wide gather per voxel and view: unconditional (clamped
             __builtin_memcpy(x, vw.pred + (off[u] >= 0 ? off[u] : 0), K * sizeof(float));   // offset), the four of a view in
             if (off[u] < 0) {                                                              // flight together
 #pragma unroll
-                for (int k = 0; k < K; ++k) x[k] = k == 0 ? 1.f : 0.f;
+                for (int k = 0; k < K; ++k) x[k] = background(k);
             }
 #pragma unroll
-            for (int k = 0; k < K; ++k) z[u][k] = a.sum_fusion ? (z[u][k] + x[k]) : (z[u][k] + w[k] * x[k]);
+            for (int k = 0; k < K; ++k) z[u][k] = fuse_add(z[u][k], w, k, x[k], a.sum_fusion);
         }
     }
 #pragma unroll
     for (int u = 0; u < FZ; ++u) {
         const int vz = vz0 + 16 * u;
         if (vz >= g.Z) continue;
-        if (!a.sum_fusion) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) z[u][k] = z[u][k] + a.b[k];
-        }
+        fuse_add_bias<K>(z[u], a.b, a.sum_fusion);
         softmax_argmax_store<K>(z[u], !a.sum_fusion, ((long)vx * g.Y + vy) * g.Z + vz, a.probs, a.labels);
     }
 }
@@ -579,15 +616,93 @@ __global__ __launch_bounds__(256) void map_fuse_kernel(FuseArgs a) {
 // the view is not eligible), so a lookup that is not risky equals the exact one. Risky voxels (~1e-7 of them) are
 // appended to a work list and recomputed from scratch by map_fuse_fixup_kernel with the exact search.
 struct AffView { double M[9], t[3]; const float* pred; int dim, P; int S[3], _pad; };   // S: fixed-point z step (FX kernels)
+// base = u of the lane's (x, y, 0)
+__device__ __forceinline__ void affine_base(const AffView& w, int vx, int vy, double (&base)[3]) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) base[r] = fma(w.M[3 * r + 1], (double)vy, fma(w.M[3 * r], (double)vx, w.t[r]));
+}
+// One axis of the screened nearest lookup in fp64 (the round-2 form; a lookup is this for r = 0, 1, 2 with m = M[3 r + 2]):
+// z the voxel's z coordinate, h half the last index of the axis. Returns the rounded index coordinate; ORs into sure_out
+// "beyond an axis end by more than GEOM_TAU" and into risky "within GEOM_TAU of a tie or of an axis end (or NaN)": the
+// exact search decides those. (Per axis, the loop in the kernels: as one unit over the three axes it moved the single-view
+// kernels' register allocation by 4 to 8 VGPRs, an occupancy step at K = 12, 15, 16.)
+__device__ __forceinline__ int affine_axis(double m, double base, double z, double h, bool& sure_out, bool& risky) {
+    const double uu = fma(m, z, base);
+    const double rr = rint(uu);
+    risky |= !(fabs(fabs(uu - rr) - 0.5) > GEOM_TAU);                 // tie (or NaN)
+    const double e = fabs(uu - h);
+    const bool in = e < h - GEOM_TAU, out = e > h + GEOM_TAU;
+    sure_out |= out; risky |= !(in | out);
+    return (int)rr;
+}
+// element offset of the K-vector (plane n2, row n0, column n1) of a view's prediction
+__device__ __forceinline__ unsigned affine_offset(const AffView& w, int n0, int n1, int n2, int K) {
+    return (((unsigned)n2 * (unsigned)w.dim + (unsigned)n0) * (unsigned)w.dim + (unsigned)n1) * K;
+}
+
+// ---- the brick walk of the straight-line back-mapping kernels -----------------------------------------------
+// One workgroup = one 8x8x16 (x, y, z) brick: a WAVE covers a 4x4x16 block, lane (tx, ty, tz) owns the 4 consecutive
+// voxels z = 4 tz .. 4 tz + 3, the 4 waves tile the brick. Each of a view's 4 gather instructions then has a compact
+// 4x4x(4 strided) footprint and the four together touch the lines of a 4x4x16 block once (fewest L2 requests per voxel
+// for an arbitrary view).
+// (Round 5, call R5t: a lane owning z = tz, tz + 4, tz + 8, tz + 12 instead -- every gather instruction then covers a
+//  COMPACT 4x4x4 cube, labels exchanged inside the quad by DPP -- measured 0.416 vs 0.424 ms: the number of distinct lines
+//  per gather instruction is not what bounds this kernel; not kept.)
+// Workgroups with equal blockIdx % 8 share an XCD (one L2): each XCD walks its own contiguous run of nblk8 bricks. A
+// 128-byte line of a view's predictions (10.7 voxels) straddles neighbouring bricks: the brick columns (x, y) are walked
+// in Morton order (px2, py2: log2 of the padded column grid) so that x- and y-neighbours follow within a few columns
+// (while the line is still in this XCD's L2).
+// order 1: z fastest, one whole column of bricks after the other.
+// order 2: z SLOWEST inside the XCD's run (its cpx consecutive Morton columns) -- the run's columns are swept slab by
+//          slab, so the x- and y-neighbours that share a view's 128-byte lines follow each other within a few bricks (z
+//          fastest put 16 bricks = ~3 MB of lines between them): FETCH_SIZE 2.04 -> 1.33 GB per 256^3 launch (algorithmic
+//          1.21), kernel 354 -> 336 us (round 3, call R3i). Needs a padded brick count that is a multiple of 8 nz.
+constexpr int FBX = 8, FBY = 8, FBZ = 16;
+struct BrickWalk { unsigned nblk8; int px2, py2, order; };
+// ORDER2 = false: the kernel is only ever given order 1 (the single-view kernel; it keeps the code it had).
+template <bool ORDER2>
+__device__ __forceinline__ bool walk_brick(const BrickWalk& w, int nx, int ny, int nz, int& bx, int& by, int& bz) {
+    auto compact = [](unsigned v) { v &= 0x55555555u; v = (v | (v >> 1)) & 0x33333333u; v = (v | (v >> 2)) & 0x0f0f0f0fu;
+                                    v = (v | (v >> 4)) & 0x00ff00ffu; v = (v | (v >> 8)) & 0x0000ffffu; return v; };
+    unsigned col;
+    if (!ORDER2 || w.order == 1) {
+        const unsigned L = (blockIdx.x & 7u) * w.nblk8 + (blockIdx.x >> 3);
+        col = L / (unsigned)nz;
+        bz = (int)(L % (unsigned)nz);
+    } else {
+        const unsigned cpx = w.nblk8 / (unsigned)nz, Lr = blockIdx.x >> 3, xcd = blockIdx.x & 7u;
+        col = xcd * cpx + Lr % cpx;
+        bz = (int)(Lr / cpx);
+    }
+    const int mb = w.px2 < w.py2 ? w.px2 : w.py2;
+    const unsigned lo = col & ((1u << (2 * mb)) - 1u), hi = col >> (2 * mb);
+    unsigned cx = compact(lo), cy = compact(lo >> 1);
+    if (w.px2 > w.py2) cx |= hi << mb; else cy |= hi << mb;
+    if (cx >= (unsigned)nx || cy >= (unsigned)ny || bz >= nz) return false;
+    bx = (int)cx; by = (int)cy;
+    return true;
+}
+// the first of this lane's four voxels (x, y, z0 .. z0 + 3); false: the workgroup has no brick or the lane no voxel
+template <bool ORDER2>
+__device__ __forceinline__ bool walk_voxel(const BrickWalk& w, int X, int Y, int Z, int& vx, int& vy, int& vz0) {
+    int bx, by, bz;
+    if (!walk_brick<ORDER2>(w, (X + FBX - 1) / FBX, (Y + FBY - 1) / FBY, (Z + FBZ - 1) / FBZ, bx, by, bz)) return false;
+    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+    vx = bx * FBX + (wv & 1) * 4 + (ln >> 4);
+    vy = by * FBY + (wv >> 1) * 4 + ((ln >> 2) & 3);
+    vz0 = bz * FBZ + (ln & 3) * 4;
+    return vx < X && vy < Y && vz0 < Z;
+}
+
 struct FuseFastArgs {
     AffView v[MAX_VIEWS]; int V, X, Y, Z;
     const float* W; const float* b; int sum_fusion;
     float* probs; uint8_t* labels;
-    unsigned* list; unsigned* count; unsigned cap, nblk8;
-    int morton, px2, py2;        // brick columns (x, y) in Morton order (log2 of the padded column grid), z fastest
+    unsigned* list; unsigned* count; unsigned cap;
+    BrickWalk walk;
 };
 
-// FX (round 4, CFG 2 only): the index coordinates of a lane's four consecutive z voxels in 32-bit FIXED POINT. Only a rounded
+// FX (round 4): the index coordinates of a lane's four consecutive z voxels in 32-bit FIXED POINT. Only a rounded
 // index and three range / tie decisions are needed per axis, not a value: voxel 0's coordinate u0 comes from the fp64 chain
 // as before, is truncated to Q11.20 (FP0 = trunc(u0 * 2^20), clamped to +-1.5 * 2^30), and voxels 1..3 add the host-rounded
 // step S = rint(M_z * 2^20). Error against the fp64 coordinate: < 2^-20 (truncation) + 3 * 2^-21 (steps) = 2.4e-6 index
@@ -600,77 +715,15 @@ struct FuseFastArgs {
 // what that flags (|u - lattice| < GEOM_TAU, ~1e-7) goes to the exact fix-up as before. Host-side eligibility: every
 // axis <= 1024 nodes and |M_z| <= 8 (compose_view fills S).
 constexpr int FX_T = 16, FX_SH = 20;
-template <int K, int CFG, bool FX = false>
+template <int K, bool FX>
 __global__ __launch_bounds__(256) void map_fuse_fast_kernel(FuseFastArgs a) {
-    static_assert(!FX || CFG == 2, "fixed-point screening: the 4-consecutive-z lane layout");
-    // lanes: 16 along z, LY along y, the rest along x; a thread owns FZ voxels strided along z (CFG 0: brick
-    // 4x4x64) or along x (CFG 1: brick 8x8x16)
-    // CFG 2: a WAVE covers a 4x4x16 block, lane (tx, ty, tz) owns the 4 consecutive voxels z = 4 tz .. 4 tz + 3; the 4
-    //        waves tile a 8x8x16 brick. Each of a view's 4 gather instructions then has a compact 4x4x(4 strided) footprint and
-    //        the four together touch the lines of a 4x4x16 block once (fewest L2 requests per voxel for an arbitrary view).
-    // (Round 5, gpurun R5t: a lane owning z = tz, tz + 4, tz + 8, tz + 12 instead -- every gather instruction then covers a
-    //        COMPACT 4x4x4 cube, labels exchanged inside the quad by DPP -- measured 0.416 vs 0.424 ms: the number of distinct lines
-    //        per gather instruction is not what bounds this kernel; not kept.)
-    constexpr int LY = CFG == 1 ? 8 : 4, BX = CFG ? 8 : 4, BY = CFG ? 8 : 4, BZ = CFG ? 16 : 64, OWN = CFG == 1 ? 0 : 2,
-                  STRIDE = CFG == 1 ? 2 : (CFG == 2 ? 1 : 16);
-    const int nz = (a.Z + BZ - 1) / BZ, ny = (a.Y + BY - 1) / BY, nx = (a.X + BX - 1) / BX;
-    // workgroups with equal blockIdx % 8 share an XCD (one L2): each XCD walks its own contiguous run of bricks
-    const unsigned L = (blockIdx.x & 7u) * a.nblk8 + (blockIdx.x >> 3);
-    int bx, by, bz;
-    if (a.morton) {
-        // a 128-byte line of a view's predictions (10.7 voxels) straddles neighbouring bricks: walk the brick columns in
-        // Morton order so that x- and y-neighbours follow within a few columns (while the line is still in this XCD's L2)
-        auto compact = [](unsigned v) { v &= 0x55555555u; v = (v | (v >> 1)) & 0x33333333u; v = (v | (v >> 2)) & 0x0f0f0f0fu;
-                                        v = (v | (v >> 4)) & 0x00ff00ffu; v = (v | (v >> 8)) & 0x0000ffffu; return v; };
-        unsigned col;
-        if (a.morton == 1) {                                     // z fastest: one whole column of bricks after the other
-            col = L / (unsigned)nz;
-            bz = (int)(L % (unsigned)nz);
-        } else {
-            // order inside the XCD's run (its cpx consecutive Morton columns): a.morton == 2 (default): z SLOWEST -- the
-            // run's columns are swept slab by slab, so the x- and y-neighbours that share a view's 128-byte lines follow
-            // each other within a few bricks (z fastest put 16 bricks = ~3 MB of lines between them): FETCH_SIZE
-            // 2.04 -> 1.33 GB per 256^3 launch (algorithmic 1.21), kernel 354 -> 336 us (round 3, gpurun R3i);
-            // a.morton == 3: 2x2 columns x 4 z-bricks interleaved on two levels (1.50 GB, 333 us)
-            const unsigned cpx = a.nblk8 / (unsigned)nz, Lr = blockIdx.x >> 3, xcd = blockIdx.x & 7u;
-            unsigned colr, z;
-            if (a.morton == 2 || (nz & 15) || (cpx & 15)) { z = Lr / cpx; colr = Lr % cpx; }
-            else {
-                const unsigned grp = Lr / (16u * (unsigned)nz), w = Lr % (16u * (unsigned)nz);     // 16 columns x nz bricks
-                const unsigned c_lo = w & 3u, z_lo = (w >> 2) & 3u, c_mid = (w >> 4) & 3u, z_hi = w >> 6;
-                colr = grp * 16u + c_mid * 4u + c_lo; z = z_hi * 4u + z_lo;
-            }
-            col = xcd * cpx + colr; bz = (int)z;
-        }
-        const int mb = a.px2 < a.py2 ? a.px2 : a.py2;
-        const unsigned lo = col & ((1u << (2 * mb)) - 1u), hi = col >> (2 * mb);
-        unsigned cx = compact(lo), cy = compact(lo >> 1);
-        if (a.px2 > a.py2) cx |= hi << mb; else cy |= hi << mb;
-        if (cx >= (unsigned)nx || cy >= (unsigned)ny || bz >= nz) return;
-        bx = (int)cx; by = (int)cy;
-    } else {
-        if (L >= (unsigned)nz * (unsigned)ny * (unsigned)nx) return;
-        bz = (int)(L % (unsigned)nz); by = (int)((L / (unsigned)nz) % (unsigned)ny); bx = (int)(L / ((unsigned)nz * (unsigned)ny));
-    }
-    int vx0, vy, vz0;
-    if (CFG == 2) {
-        const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
-        vx0 = bx * BX + (wv & 1) * 4 + (ln >> 4);
-        vy = by * BY + (wv >> 1) * 4 + ((ln >> 2) & 3);
-        vz0 = bz * BZ + (ln & 3) * 4;
-    } else {
-        vx0 = bx * BX + (int)(threadIdx.x / (16 * LY));
-        vy = by * BY + (int)((threadIdx.x >> 4) % LY);
-        vz0 = bz * BZ + (int)(threadIdx.x & 15);
-    }
-    if (vx0 >= a.X || vy >= a.Y || vz0 >= a.Z) return;
-    const double cf0 = OWN == 0 ? (double)vz0 : (double)vx0, cy = (double)vy;      // the two coordinates all owned voxels share
-    const int own0 = OWN == 0 ? vx0 : vz0;
+    int vx, vy, vz0;
+    if (!walk_voxel<true>(a.walk, a.X, a.Y, a.Z, vx, vy, vz0)) return;
     double co[FZ];
     float z[FZ][K];
 #pragma unroll
     for (int u = 0; u < FZ; ++u) {
-        co[u] = (double)(own0 + STRIDE * u);
+        co[u] = (double)(vz0 + u);
 #pragma unroll
         for (int k = 0; k < K; ++k) z[u][k] = 0.f;
     }
@@ -684,36 +737,26 @@ __global__ __launch_bounds__(256) void map_fuse_fast_kernel(FuseFastArgs a) {
         const AffView& w = a.v[v];
         const double hg = 0.5 * (double)(w.dim - 1), ho = 0.5 * (double)(w.P - 1);
         double base[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) base[r] = fma(w.M[3 * r + 1], cy, fma(w.M[3 * r + (OWN == 0 ? 2 : 0)], cf0, w.t[r]));
+        affine_base(w, vx, vy, base);
         float wk[K];
 #pragma unroll
-        for (int k = 0; k < K; ++k) wk[k] = a.sum_fusion ? 1.f : a.W[v * K + k];
+        for (int k = 0; k < K; ++k) wk[k] = fuse_weight(a.W, v * K + k, a.sum_fusion);
         unsigned off[FZ]; bool out[FZ];
-        // one lookup in fp64 (the round-2 form): rounded indices, sure-out and "within GEOM_TAU of a decision" flags
+        // one lookup in fp64: the three axes of affine_axis, then this kernel's offset and flag arithmetic
         auto lookup64 = [&](int u, unsigned& offu, bool& outu) {
             int n[3]; bool o = false, rk = false;
 #pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const double uu = fma(w.M[3 * r + OWN], co[u], base[r]);
-                const double h = r == 2 ? ho : hg;
-                const double rr = rint(uu);
-                rk |= !(fabs(fabs(uu - rr) - 0.5) > GEOM_TAU);                 // tie (or NaN)
-                const double e = fabs(uu - h);
-                const bool in = e < h - GEOM_TAU, sure_out = e > h + GEOM_TAU;
-                o |= sure_out; rk |= !(in | sure_out);
-                n[r] = (int)rr;
-            }
+            for (int r = 0; r < 3; ++r) n[r] = affine_axis(w.M[3 * r + 2], base[r], co[u], r == 2 ? ho : hg, o, rk);
             outu = o;
             risky |= rk ? (1u << u) : 0u;
-            offu = (o | rk) ? 0u : (((unsigned)n[2] * (unsigned)w.dim + (unsigned)n[0]) * (unsigned)w.dim + (unsigned)n[1]) * K;
+            offu = (outu | rk) ? 0u : affine_offset(w, n[0], n[1], n[2], K);
         };
         if constexpr (FX) {
             constexpr int LIMC = 3 << 29;                            // clamp: 1.5 * 2^30 (+ 3 steps of <= 2^23 stays below 2^31)
             int fp0[3];
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
-                const double u0 = fma(w.M[3 * r + OWN], co[0], base[r]);
+                const double u0 = fma(w.M[3 * r + 2], co[0], base[r]);
                 const int q = (int)(u0 * (double)(1 << FX_SH));      // v_cvt_i32_f64: truncates, saturates
                 fp0[r] = q < -LIMC ? -LIMC : (q > LIMC ? LIMC : q);
             }
@@ -733,7 +776,7 @@ __global__ __launch_bounds__(256) void map_fuse_fast_kernel(FuseFastArgs a) {
                 const bool near = qmin < ((unsigned)(2 * FX_T) << (32 - (FX_SH - 1)));
                 band |= near ? (1u << u) : 0u;
                 out[u] = !in;
-                off[u] = (!in | near) ? 0u : (((unsigned)n[2] * (unsigned)w.dim + (unsigned)n[0]) * (unsigned)w.dim + (unsigned)n[1]) * K;
+                off[u] = (!in | near) ? 0u : affine_offset(w, n[0], n[1], n[2], K);
             }
             if (band) {                                              // ~2e-4 of the lookups: this view's fp64 form for those voxels
 #pragma unroll
@@ -750,30 +793,26 @@ __global__ __launch_bounds__(256) void map_fuse_fast_kernel(FuseFastArgs a) {
             __builtin_memcpy(x, w.pred + off[u], K * sizeof(float));
             if (out[u]) {
 #pragma unroll
-                for (int k = 0; k < K; ++k) x[k] = k == 0 ? 1.f : 0.f;
+                for (int k = 0; k < K; ++k) x[k] = background(k);
             }
 #pragma unroll
-            for (int k = 0; k < K; ++k) z[u][k] = a.sum_fusion ? (z[u][k] + x[k]) : (z[u][k] + wk[k] * x[k]);
+            for (int k = 0; k < K; ++k) z[u][k] = fuse_add(z[u][k], wk, k, x[k], a.sum_fusion);
         }
     }
-    // labels of the 4 consecutive voxels of a CFG-2 lane as one 32-bit store (risky ones are overwritten by the fix-up,
-    // which runs after this kernel)
-    const bool packed = CFG == 2 && a.labels && !a.probs && (a.Z & 3) == 0;
+    // labels of the lane's 4 consecutive voxels as one 32-bit store (risky ones are overwritten by the fix-up, which runs
+    // after this kernel)
+    const bool packed = a.labels && !a.probs && (a.Z & 3) == 0;
     unsigned pack = 0;
 #pragma unroll
     for (int u = 0; u < FZ; ++u) {
-        const int vx = OWN == 0 ? own0 + STRIDE * u : vx0, vz = OWN == 0 ? vz0 : own0 + STRIDE * u;
-        if (vx >= a.X || vz >= a.Z) continue;
+        const int vz = vz0 + u;
+        if (vz >= a.Z) continue;
         const long t = ((long)vx * a.Y + vy) * a.Z + vz;
         if ((risky >> u) & 1u) {                       // redone by the fix-up kernel (which also stores it)
-            const unsigned idx = atomicAdd(a.count, 1u);
-            if (idx < a.cap) a.list[idx] = (unsigned)t;
+            worklist_push(a.list, a.count, a.cap, t);
             continue;
         }
-        if (!a.sum_fusion) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) z[u][k] = z[u][k] + a.b[k];
-        }
+        fuse_add_bias<K>(z[u], a.b, a.sum_fusion);      // the finish, with the packed label store in the place of the plain one
         if (packed) {
             int best = 0; float bv = z[u][0];           // argmax is invariant under the softmax
 #pragma unroll
@@ -783,7 +822,7 @@ __global__ __launch_bounds__(256) void map_fuse_fast_kernel(FuseFastArgs a) {
             softmax_argmax_store<K>(z[u], !a.sum_fusion, t, a.probs, a.labels);
         }
     }
-    if (packed) *(unsigned*)(a.labels + (((long)vx0 * a.Y + vy) * a.Z + vz0)) = pack;
+    if (packed) *(unsigned*)(a.labels + (((long)vx * a.Y + vy) * a.Z + vz0)) = pack;
 }
 
 // exact recomputation of the voxels on the work list (all voxels if the list overflowed). The list is short and the exact
@@ -795,17 +834,14 @@ __global__ __launch_bounds__(512) void map_fuse_fixup_kernel(FuseArgs a, const u
                                                              unsigned* next_count) {
     __shared__ float xs[MAX_VIEWS][K][64];
     const GridDev& g = a.grid;
-    const unsigned n = *count;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *next_count = 0;
-    const long total = (long)g.X * g.Y * g.Z;
-    const bool all = n > cap;
-    const long m = all ? total : (long)n;
+    const WorkList wl = worklist_open(list, count, cap, next_count, (long)g.X * g.Y * g.Z);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    for (long i0 = (long)blockIdx.x * 64; i0 < m; i0 += (long)gridDim.x * 64) {       // uniform trip count per workgroup
+    for (long i0 = (long)blockIdx.x * 64; i0 < wl.m; i0 += (long)gridDim.x * 64) {    // uniform trip count per workgroup
         const long i = i0 + lane;
-        const bool live = i < m;
-        const long t = live ? (all ? i : (long)list[i]) : 0;
-        const int vz = (int)(t % g.Z), vy = (int)((t / g.Z) % g.Y), vx = (int)(t / ((long)g.Z * g.Y));
+        const bool live = i < wl.m;
+        const long t = live ? worklist_at(wl, i) : 0;
+        int vx, vy, vz;
+        split3(t, g.Y, g.Z, vx, vy, vz);
         double rx, ry, rz;
         voxel_real(g, vx, vy, vz, rx, ry, rz);
         for (int v = wave; v < a.V; v += 8) {                                         // (eight waves: six views = one round;
@@ -822,16 +858,9 @@ __global__ __launch_bounds__(512) void map_fuse_fixup_kernel(FuseArgs a, const u
             for (int k = 0; k < K; ++k) z[k] = 0.f;
             for (int v = 0; v < a.V; ++v) {
 #pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const float x = xs[v][k][lane];
-                    const float wv = a.sum_fusion ? 1.f : a.W[v * K + k];
-                    z[k] = a.sum_fusion ? (z[k] + x) : (z[k] + wv * x);
-                }
+                for (int k = 0; k < K; ++k) z[k] = fuse_add(z[k], a.W, v * K + k, xs[v][k][lane], a.sum_fusion);
             }
-            if (!a.sum_fusion) {
-#pragma unroll
-                for (int k = 0; k < K; ++k) z[k] = z[k] + a.b[k];
-            }
+            fuse_add_bias<K>(z, a.b, a.sum_fusion);
             softmax_argmax_store<K>(z, !a.sum_fusion, t, a.probs, a.labels);
         }
         __syncthreads();
@@ -842,33 +871,38 @@ struct MapArgs {
     GridDev grid; ViewDev view; const float* Wv; int p_lo, p_hi, owns_oob; float* out;
 };
 
-// ACCUM=false: mapped[t,:] = nearest (map_real_space_pred). ACCUM=true: z[t,:] += Wv*nearest
-// restricted to planes [p_lo,p_hi) (pred points at plane p_lo).
+// The exact nearest map of voxel (vx, vy, vz) = element t. ACCUM=false: mapped[t,:] = nearest (map_real_space_pred).
+// ACCUM=true: z[t,:] += Wv*nearest restricted to planes [p_lo,p_hi) (pred points at plane p_lo).
+template <int K, bool ACCUM>
+__device__ __forceinline__ void map_view_exact(const MapArgs& a, int vx, int vy, int vz, long t) {
+    double rx, ry, rz;
+    voxel_real(a.grid, vx, vy, vz, rx, ry, rz);
+    int pl;
+    const long off = view_lookup(a.view, rx, ry, rz, K, pl);
+    if (!ACCUM) {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            a.out[t * K + k] = (off >= 0) ? a.view.pred[off + k] : (k == 0 ? 1.f : 0.f);
+    } else {
+        if (off >= 0) {
+            if (pl >= a.p_lo && pl < a.p_hi) {
+                const long o2 = off - (long)a.p_lo * a.view.dim * a.view.dim * K;
+#pragma unroll
+                for (int k = 0; k < K; ++k) a.out[t * K + k] += a.Wv[k] * a.view.pred[o2 + k];
+            }
+        } else if (a.owns_oob) {
+            a.out[t * K] += a.Wv[0];
+        }
+    }
+}
+
 template <int K, bool ACCUM>
 __global__ __launch_bounds__(256) void map_view_kernel(MapArgs a) {
     const long nblk = brick_count(a.grid);
     for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         int vx, vy, vz; long t;
         if (!brick_voxel(a.grid, blk, vx, vy, vz, t)) continue;
-        double rx, ry, rz;
-        voxel_real(a.grid, vx, vy, vz, rx, ry, rz);
-        int pl;
-        const long off = view_lookup(a.view, rx, ry, rz, K, pl);
-        if (!ACCUM) {
-#pragma unroll
-            for (int k = 0; k < K; ++k)
-                a.out[t * K + k] = (off >= 0) ? a.view.pred[off + k] : (k == 0 ? 1.f : 0.f);
-        } else {
-            if (off >= 0) {
-                if (pl >= a.p_lo && pl < a.p_hi) {
-                    const long o2 = off - (long)a.p_lo * a.view.dim * a.view.dim * K;
-#pragma unroll
-                    for (int k = 0; k < K; ++k) a.out[t * K + k] += a.Wv[k] * a.view.pred[o2 + k];
-                }
-            } else if (a.owns_oob) {
-                a.out[t * K] += a.Wv[0];
-            }
-        }
+        map_view_exact<K, ACCUM>(a, vx, vy, vz, t);
     }
 }
 
@@ -877,33 +911,12 @@ template <int K, bool ACCUM>
 __global__ __launch_bounds__(256) void map_view_fixup_kernel(MapArgs a, const unsigned* list, const unsigned* count, unsigned cap,
                                                              unsigned* next_count) {
     const GridDev& g = a.grid;
-    const unsigned n = *count;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *next_count = 0;
-    const long total = (long)g.X * g.Y * g.Z;
-    const bool all = n > cap;
-    const long m = all ? total : (long)n;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < m; i += (long)gridDim.x * 256) {
-        const long t = all ? i : (long)list[i];
-        const int vz = (int)(t % g.Z), vy = (int)((t / g.Z) % g.Y), vx = (int)(t / ((long)g.Z * g.Y));
-        double rx, ry, rz;
-        voxel_real(g, vx, vy, vz, rx, ry, rz);
-        int pl;
-        const long off = view_lookup(a.view, rx, ry, rz, K, pl);
-        if (!ACCUM) {
-#pragma unroll
-            for (int k = 0; k < K; ++k)
-                a.out[t * K + k] = (off >= 0) ? a.view.pred[off + k] : (k == 0 ? 1.f : 0.f);
-        } else {
-            if (off >= 0) {
-                if (pl >= a.p_lo && pl < a.p_hi) {
-                    const long o2 = off - (long)a.p_lo * a.view.dim * a.view.dim * K;
-#pragma unroll
-                    for (int k = 0; k < K; ++k) a.out[t * K + k] += a.Wv[k] * a.view.pred[o2 + k];
-                }
-            } else if (a.owns_oob) {
-                a.out[t * K] += a.Wv[0];
-            }
-        }
+    const WorkList wl = worklist_open(list, count, cap, next_count, (long)g.X * g.Y * g.Z);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < wl.m; i += (long)gridDim.x * 256) {
+        const long t = worklist_at(wl, i);
+        int vx, vy, vz;
+        split3(t, g.Y, g.Z, vx, vy, vz);
+        map_view_exact<K, ACCUM>(a, vx, vy, vz, t);
     }
 }
 
@@ -998,12 +1011,9 @@ __global__ __launch_bounds__(256) void map_fuse_linear_kernel(FuseArgs a) {
             float x[K];
             view_linear<K>(vw, rx, ry, rz, 0, vw.P, x);
 #pragma unroll
-            for (int k = 0; k < K; ++k) z[k] = a.sum_fusion ? (z[k] + x[k]) : (z[k] + a.W[v * K + k] * x[k]);
+            for (int k = 0; k < K; ++k) z[k] = fuse_add(z[k], a.W, v * K + k, x[k], a.sum_fusion);
         }
-        if (!a.sum_fusion) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) z[k] = z[k] + a.b[k];
-        }
+        fuse_add_bias<K>(z, a.b, a.sum_fusion);
         softmax_argmax_store<K>(z, !a.sum_fusion, t, a.probs, a.labels);
     }
 }
@@ -1019,8 +1029,7 @@ __global__ __launch_bounds__(256) void fusion_forward_kernel(const float* __rest
         for (int v = 0; v < V; ++v)
 #pragma unroll
             for (int k = 0; k < K; ++k) z[k] = z[k] + W[v * K + k] * x[(t * V + v) * K + k];
-#pragma unroll
-        for (int k = 0; k < K; ++k) z[k] = z[k] + b[k];
+        fuse_add_bias<K>(z, b, 0);
         softmax_argmax_store<K>(z, true, t, probs, labels);
     }
 }
@@ -1032,7 +1041,8 @@ __global__ __launch_bounds__(256) void fusion_finalize_kernel(const float* __res
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) {
         float z[K];
 #pragma unroll
-        for (int k = 0; k < K; ++k) z[k] = zin[t * K + k] + (sum_fusion ? 0.f : b[k]);
+        for (int k = 0; k < K; ++k) z[k] = sum_fusion ? zin[t * K + k] + 0.f : zin[t * K + k];   // (+ 0.f as ever: a -0.0 leaves as +0.0)
+        fuse_add_bias<K>(z, b, sum_fusion);
         softmax_argmax_store<K>(z, !sum_fusion, t, probs, labels);
     }
 }
@@ -1044,31 +1054,17 @@ __global__ __launch_bounds__(256) void fusion_finalize_kernel(const float* __res
 struct MapFastArgs {
     AffView v; int X, Y, Z;
     const float* Wv; int p_lo, p_hi, owns_oob; float* out;
-    unsigned* list; unsigned* count; unsigned cap, nblk8; int px2, py2;
+    unsigned* list; unsigned* count; unsigned cap;
+    BrickWalk walk;                                               // order 1
 };
 template <int K, bool ACCUM>
 __global__ __launch_bounds__(256) void map_view_fast_kernel(MapFastArgs a) {
-    const int nz = (a.Z + 15) / 16, ny = (a.Y + 7) / 8, nx = (a.X + 7) / 8;
-    const unsigned L = (blockIdx.x & 7u) * a.nblk8 + (blockIdx.x >> 3);
-    auto compact = [](unsigned v) { v &= 0x55555555u; v = (v | (v >> 1)) & 0x33333333u; v = (v | (v >> 2)) & 0x0f0f0f0fu;
-                                    v = (v | (v >> 4)) & 0x00ff00ffu; v = (v | (v >> 8)) & 0x0000ffffu; return v; };
-    const unsigned col = L / (unsigned)nz;
-    const int bz = (int)(L % (unsigned)nz);
-    const int mb = a.px2 < a.py2 ? a.px2 : a.py2;
-    const unsigned lo = col & ((1u << (2 * mb)) - 1u), hi = col >> (2 * mb);
-    unsigned cx = compact(lo), cy = compact(lo >> 1);
-    if (a.px2 > a.py2) cx |= hi << mb; else cy |= hi << mb;
-    if (cx >= (unsigned)nx || cy >= (unsigned)ny) return;
-    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
-    const int vx = (int)cx * 8 + (wv & 1) * 4 + (ln >> 4);
-    const int vy = (int)cy * 8 + (wv >> 1) * 4 + ((ln >> 2) & 3);
-    const int vz0 = bz * 16 + (ln & 3) * 4;
-    if (vx >= a.X || vy >= a.Y || vz0 >= a.Z) return;
+    int vx, vy, vz0;
+    if (!walk_voxel<false>(a.walk, a.X, a.Y, a.Z, vx, vy, vz0)) return;
     const AffView& w = a.v;
     const double hg = 0.5 * (double)(w.dim - 1), ho = 0.5 * (double)(w.P - 1);
     double base[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) base[r] = fma(w.M[3 * r + 1], (double)vy, fma(w.M[3 * r], (double)vx, w.t[r]));
+    affine_base(w, vx, vy, base);
     // the lane's 4 voxels are 4 K contiguous floats of the output: one 16-byte-vector read-modify-write per lane (four
     // separate 12-byte accesses per lane cost more than the exact kernel's whole run)
     const long t0 = ((long)vx * a.Y + vy) * a.Z + vz0;
@@ -1088,20 +1084,10 @@ __global__ __launch_bounds__(256) void map_view_fast_kernel(MapFastArgs a) {
         if (vz >= a.Z) continue;
         int n[3]; bool o = false, rk = false;
 #pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const double uu = fma(w.M[3 * r + 2], (double)vz, base[r]);
-            const double h = r == 2 ? ho : hg;
-            const double rr = rint(uu);
-            rk |= !(fabs(fabs(uu - rr) - 0.5) > GEOM_TAU);                     // tie (or NaN)
-            const double e = fabs(uu - h);
-            const bool in = e < h - GEOM_TAU, sure_out = e > h + GEOM_TAU;
-            o |= sure_out; rk |= !(in | sure_out);
-            n[r] = (int)rr;
-        }
+        for (int r = 0; r < 3; ++r) n[r] = affine_axis(w.M[3 * r + 2], base[r], (double)vz, r == 2 ? ho : hg, o, rk);
         const long t = t0 + u;
         if (rk) {                                                // left as it is here; map_view_fixup_kernel handles it
-            const unsigned idx = atomicAdd(a.count, 1u);
-            if (idx < a.cap) a.list[idx] = (unsigned)t;
+            worklist_push(a.list, a.count, a.cap, t);
             if (!ACCUM && vec) {
 #pragma unroll
                 for (int k = 0; k < K; ++k) val[u][k] = 0.f;
@@ -1111,7 +1097,7 @@ __global__ __launch_bounds__(256) void map_view_fast_kernel(MapFastArgs a) {
         float* dst = a.out + t * K;
         if (!ACCUM) {
             float x[K];
-            const unsigned off = o ? 0u : (((unsigned)n[2] * (unsigned)w.dim + (unsigned)n[0]) * (unsigned)w.dim + (unsigned)n[1]) * K;
+            const unsigned off = o ? 0u : affine_offset(w, n[0], n[1], n[2], K);
             __builtin_memcpy(x, w.pred + off, K * sizeof(float));
 #pragma unroll
             for (int k = 0; k < K; ++k) {
@@ -1120,7 +1106,7 @@ __global__ __launch_bounds__(256) void map_view_fast_kernel(MapFastArgs a) {
             }
         } else if (!o) {
             if (n[2] >= a.p_lo && n[2] < a.p_hi) {            // (w.pred points at plane p_lo of the view)
-                const unsigned off = (((unsigned)(n[2] - a.p_lo) * (unsigned)w.dim + (unsigned)n[0]) * (unsigned)w.dim + (unsigned)n[1]) * K;
+                const unsigned off = affine_offset(w, n[0], n[1], n[2] - a.p_lo, K);
                 float x[K];
                 __builtin_memcpy(x, w.pred + off, K * sizeof(float));
 #pragma unroll
@@ -1249,7 +1235,7 @@ static bool compose_view(const GridDev& g, const ViewDev& v, int K, AffView& o) 
     o._pad = 0;
     return true;
 }
-// fixed-point screening (map_fuse_fast_kernel<K, 2, true>): every axis <= 1024 nodes, z step of every axis at most 8 index units
+// fixed-point screening (map_fuse_fast_kernel<K, true>): every axis <= 1024 nodes, z step of every axis at most 8 index units
 static bool fx_eligible(const AffView& o) {
     if (o.dim > 1024 || o.P > 1024) return false;
     for (int r = 0; r < 3; ++r) if (!(fabs(o.M[3 * r + 2]) <= 8.0)) return false;
@@ -1292,43 +1278,98 @@ struct FuseCounterGuard {
     ~FuseCounterGuard() { if (!done && list) (void)hipMemsetAsync(list - 16, 0, 16 * sizeof(unsigned), st); }
 };
 
+// A straight-line kernel and its fix-up under the counter protocol above -- the only place that knows it: take the
+// stream's scratch, launch `fast(list, count, cap)`, then `fixup(list, count, cap, next_count)`, check both launches.
+// Either callable returns an error code instead of launching when it cannot (unsupported class count).
+template <typename Fast, typename Fixup>
+static int run_with_fixup(hipStream_t st, Fast fast, Fixup fixup) {
+    unsigned *count = nullptr, *next_count = nullptr, *list = nullptr;
+    { const int rc_ = fuse_scratch(st, &count, &next_count, &list); if (rc_) return rc_; }
+    FuseCounterGuard guard{st, list};
+    { const int rc_ = fast(list, count, FUSE_LIST_CAP); if (rc_) return rc_; }
+    { const int rc_ = launch_ok(); if (rc_) return rc_; }
+    { const int rc_ = fixup(list, count, FUSE_LIST_CAP, next_count); if (rc_) return rc_; }
+    const int rc_ = launch_ok();
+    guard.done = rc_ == MPU_OK;
+    return rc_;
+}
+
+// The walk of the 8x8x16 bricks of an X x Y x Z grid (BrickWalk); false when the padded brick count does not fit the
+// kernels' 32-bit brick index (cannot happen below 2^32 voxels; such a grid takes the generic kernel).
+static bool brick_walk(int X, int Y, int Z, bool z_slowest, BrickWalk& w) {
+    const int nxb = cdiv(X, FBX), nyb = cdiv(Y, FBY), nzb = cdiv(Z, FBZ);
+    w.px2 = w.py2 = 0;
+    while ((1 << w.px2) < nxb) ++w.px2;
+    while ((1 << w.py2) < nyb) ++w.py2;
+    const long padded = (1L << w.px2) * (1L << w.py2) * nzb;
+    if (padded >= (1L << 31)) return false;
+    w.nblk8 = (unsigned)((padded + 7) / 8);
+    w.order = (z_slowest && padded % (8L * nzb) == 0) ? 2 : 1;
+    return true;
+}
+static bool fast_grid(const GridDev& g, int n_classes) {
+    return fast_path_host() && n_classes >= 1 && n_classes <= 16 && (long)g.X * g.Y * g.Z < (1L << 32);
+}
+
 // map_real_space_pred / sharded accumulate of one view: straight-line kernel + exact fix-up when the view is eligible
 static int launch_map_view(const MapArgs& a, int n_classes, bool accum, hipStream_t st) {
     MapFastArgs f;
-    const bool fast = fast_path_host() && n_classes >= 1 && n_classes <= 16 && (long)a.grid.X * a.grid.Y * a.grid.Z < (1L << 32) &&
-                      compose_view(a.grid, a.view, n_classes, f.v);
-    if (fast) {
-        unsigned* nxt = nullptr;
-        { const int rc_ = fuse_scratch(st, &f.count, &nxt, &f.list); if (rc_) return rc_; }
-        FuseCounterGuard guard{st, f.list};
-        f.cap = FUSE_LIST_CAP;
+    if (fast_grid(a.grid, n_classes) && compose_view(a.grid, a.view, n_classes, f.v) &&
+        brick_walk(a.grid.X, a.grid.Y, a.grid.Z, false, f.walk)) {
         f.X = a.grid.X; f.Y = a.grid.Y; f.Z = a.grid.Z;
         f.Wv = a.Wv; f.p_lo = a.p_lo; f.p_hi = a.p_hi; f.owns_oob = a.owns_oob; f.out = a.out;
-        const int nxb = cdiv(f.X, 8), nyb = cdiv(f.Y, 8), nzb = cdiv(f.Z, 16);
-        f.px2 = f.py2 = 0;
-        while ((1 << f.px2) < nxb) ++f.px2;
-        while ((1 << f.py2) < nyb) ++f.py2;
-        const long padded = (1L << f.px2) * (1L << f.py2) * nzb;
-        if (padded < (1L << 31)) {
-            f.nblk8 = (unsigned)((padded + 7) / 8);
-            const dim3 g(f.nblk8 * 8u), b(256);
-            if (accum) { MPU_DISPATCH_K(n_classes, (map_view_fast_kernel<KK, true><<<g, b, 0, st>>>(f))); }
-            else       { MPU_DISPATCH_K(n_classes, (map_view_fast_kernel<KK, false><<<g, b, 0, st>>>(f))); }
-            { const int rc_ = launch_ok(); if (rc_) return rc_; }
-            if (accum) { MPU_DISPATCH_K(n_classes, (map_view_fixup_kernel<KK, true><<<dim3(64), dim3(256), 0, st>>>(a, f.list, f.count, f.cap, nxt))); }
-            else       { MPU_DISPATCH_K(n_classes, (map_view_fixup_kernel<KK, false><<<dim3(64), dim3(256), 0, st>>>(a, f.list, f.count, f.cap, nxt))); }
-            if (sched_log_on()) sched_note("map_view fast accum=%d K=%d", accum ? 1 : 0, n_classes);
-            const int rc_ = launch_ok();
-            guard.done = rc_ == MPU_OK;
-            return rc_;
-        }
-        // (unreachable in practice: the scratch sequence number advanced without a launch; the guard zeroes the counters)
+        return run_with_fixup(st,
+            [&](unsigned* list, unsigned* count, unsigned cap) -> int {
+                f.list = list; f.count = count; f.cap = cap;
+                const dim3 g(f.walk.nblk8 * 8u), b(256);
+                if (accum) { MPU_DISPATCH_K(n_classes, (map_view_fast_kernel<KK, true><<<g, b, 0, st>>>(f))); }
+                else       { MPU_DISPATCH_K(n_classes, (map_view_fast_kernel<KK, false><<<g, b, 0, st>>>(f))); }
+                return MPU_OK;
+            },
+            [&](const unsigned* list, const unsigned* count, unsigned cap, unsigned* nxt) -> int {
+                if (accum) { MPU_DISPATCH_K(n_classes, (map_view_fixup_kernel<KK, true><<<dim3(64), dim3(256), 0, st>>>(a, list, count, cap, nxt))); }
+                else       { MPU_DISPATCH_K(n_classes, (map_view_fixup_kernel<KK, false><<<dim3(64), dim3(256), 0, st>>>(a, list, count, cap, nxt))); }
+                if (sched_log_on()) sched_note("map_view fast accum=%d K=%d", accum ? 1 : 0, n_classes);
+                return MPU_OK;
+            });
     }
     if (sched_log_on()) sched_note("map_view generic accum=%d K=%d", accum ? 1 : 0, n_classes);
     if (accum) { MPU_DISPATCH_K(n_classes, (map_view_kernel<KK, true><<<dim3(brick_grid(a.grid)), dim3(256), 0, st>>>(a))); }
     else       { MPU_DISPATCH_K(n_classes, (map_view_kernel<KK, false><<<dim3(brick_grid(a.grid)), dim3(256), 0, st>>>(a))); }
     return launch_ok();
 }
+
+// Argument checks and kernel arguments of the back-mapping entry points, nearest and linear (who: the entry point's name
+// for the message). accum: z += Wv * x over the planes [p_lo, p_hi); else the plain map of all planes (Wv, p_lo, p_hi and
+// owns_oob are not read). check_dims is false for mpu_map_accumulate_view alone, which has never checked dim / planes.
+#define MPU_REQUIRE_WHO(cond, what) do { if (!(cond)) return mpu::fail(MPU_EINVAL, "%s: " what, who); } while (0)
+static int make_map_args(const char* who, const mpu_voxel_grid* grid, const mpu_view_pred* view, bool accum, bool check_dims,
+                         const float* d_Wv, int p_lo, int p_hi, int owns_oob, float* d_out, MapArgs& a) {
+    MPU_REQUIRE_WHO(grid && view && d_out && (!accum || d_Wv) && view->d_pred && view->d_g && view->d_offsets, "null argument");
+    if (check_dims) MPU_REQUIRE_WHO(view->dim >= 2 && view->n_planes >= 2, "view needs dim>=2, planes>=2");
+    if (accum) MPU_REQUIRE_WHO(0 <= p_lo && p_lo < p_hi && p_hi <= view->n_planes, "bad plane range");
+    to_grid(*grid, a.grid); to_view(*view, a.view);
+    a.Wv = accum ? d_Wv : nullptr;
+    a.p_lo = accum ? p_lo : 0; a.p_hi = accum ? p_hi : view->n_planes; a.owns_oob = accum ? owns_oob : 1;
+    a.out = d_out;
+    return MPU_OK;
+}
+static int make_fuse_args(const char* who, const mpu_voxel_grid* grid, const mpu_view_pred* views, int n_views,
+                          const float* d_W, const float* d_b, int sum_fusion, float* d_probs, uint8_t* d_labels, FuseArgs& a) {
+    MPU_REQUIRE_WHO(grid && views, "null argument");
+    MPU_REQUIRE_WHO(n_views >= 1 && n_views <= MAX_VIEWS, "n_views must be in 1..16");
+    MPU_REQUIRE_WHO(sum_fusion || (d_W && d_b), "W and b required unless sum_fusion");
+    MPU_REQUIRE_WHO(d_probs || d_labels, "no output requested");
+    to_grid(*grid, a.grid);
+    for (int v = 0; v < n_views; ++v) {
+        MPU_REQUIRE_WHO(views[v].d_pred && views[v].d_g && views[v].d_offsets, "null view field");
+        MPU_REQUIRE_WHO(views[v].dim >= 2 && views[v].n_planes >= 2, "view needs dim>=2, planes>=2");
+        to_view(views[v], a.views[v]);
+    }
+    a.V = n_views; a.W = d_W; a.b = d_b; a.sum_fusion = sum_fusion; a.probs = d_probs; a.labels = d_labels;
+    return MPU_OK;
+}
+#undef MPU_REQUIRE_WHO
 
 extern "C" {
 
@@ -1415,25 +1456,25 @@ int mpu_sample_view_planes_sc(const float* d_vol, const uint8_t* d_labels, const
     if (fast) {
         const dim3 g((unsigned)((a.dim + 31) / 32), (unsigned)((a.dim + 7) / 8), (unsigned)a.P), b(256);
         hipStream_t st = (hipStream_t)stream;
-        unsigned *cnt = nullptr, *nxt = nullptr, *lst = nullptr;
-        { const int rc_ = fuse_scratch(st, &cnt, &nxt, &lst); if (rc_) return rc_; }
-        FuseCounterGuard guard{st, lst};
+        return run_with_fixup(st,
+            [&](unsigned* lst, unsigned* cnt, unsigned cap) -> int {
 #define MPU_SAMPLE_FAST3(KIND_, C_, LAB_) \
-        if (gensc) sample_fast_kernel<KIND_, C_, LAB_, SampleArgsSc><<<g, b, lds, st>>>(a, lst, cnt, FUSE_LIST_CAP); \
-        else sample_fast_kernel<KIND_, C_, LAB_, SampleArgs><<<g, b, 0, st>>>(a0, lst, cnt, FUSE_LIST_CAP);
+                if (gensc) sample_fast_kernel<KIND_, C_, LAB_, SampleArgsSc><<<g, b, lds, st>>>(a, lst, cnt, cap); \
+                else sample_fast_kernel<KIND_, C_, LAB_, SampleArgs><<<g, b, 0, st>>>(a0, lst, cnt, cap);
 #define MPU_SAMPLE_FAST(KIND_) \
-        if (a.C == 1) { if (a.out_lab) { MPU_SAMPLE_FAST3(KIND_, 1, true) } else { MPU_SAMPLE_FAST3(KIND_, 1, false) } } \
-        else          { if (a.out_lab) { MPU_SAMPLE_FAST3(KIND_, 2, true) } else { MPU_SAMPLE_FAST3(KIND_, 2, false) } }
-        if (a.ax.kind == 1) { MPU_SAMPLE_FAST(1) } else { MPU_SAMPLE_FAST(2) }
+                if (a.C == 1) { if (a.out_lab) { MPU_SAMPLE_FAST3(KIND_, 1, true) } else { MPU_SAMPLE_FAST3(KIND_, 1, false) } } \
+                else          { if (a.out_lab) { MPU_SAMPLE_FAST3(KIND_, 2, true) } else { MPU_SAMPLE_FAST3(KIND_, 2, false) } }
+                if (a.ax.kind == 1) { MPU_SAMPLE_FAST(1) } else { MPU_SAMPLE_FAST(2) }
 #undef MPU_SAMPLE_FAST
 #undef MPU_SAMPLE_FAST3
-        { const int rc_ = launch_ok(); if (rc_) return rc_; }
-        if (gensc) sample_fixup_kernel<SampleArgsSc><<<dim3(64), dim3(256), lds, st>>>(a, lst, cnt, FUSE_LIST_CAP, nxt);
-        else sample_fixup_kernel<SampleArgs><<<dim3(64), dim3(256), 0, st>>>(a0, lst, cnt, FUSE_LIST_CAP, nxt);
-        if (sched_log_on()) sched_note("sample fast kind=%d C=%d labels=%d", a.ax.kind, a.C, a.out_lab ? 1 : 0);
-        const int rc_ = launch_ok();
-        guard.done = rc_ == MPU_OK;
-        return rc_;
+                return MPU_OK;
+            },
+            [&](const unsigned* lst, const unsigned* cnt, unsigned cap, unsigned* nxt) -> int {
+                if (gensc) sample_fixup_kernel<SampleArgsSc><<<dim3(64), dim3(256), lds, st>>>(a, lst, cnt, cap, nxt);
+                else sample_fixup_kernel<SampleArgs><<<dim3(64), dim3(256), 0, st>>>(a0, lst, cnt, cap, nxt);
+                if (sched_log_on()) sched_note("sample fast kind=%d C=%d labels=%d", a.ax.kind, a.C, a.out_lab ? 1 : 0);
+                return MPU_OK;
+            });
     }
     if (sched_log_on()) sched_note("sample generic kinds=%d%d%d C=%d labels=%d", a.ax.kind, a.ay.kind, a.az.kind, a.C, a.out_lab ? 1 : 0);
     const long tpd = (a.dim + 15) / 16;
@@ -1464,11 +1505,8 @@ int mpu_sample_view_planes(const float* d_vol, const uint8_t* d_labels, const in
 int mpu_map_view_nearest(const mpu_voxel_grid* grid, const mpu_view_pred* view, int32_t n_classes,
                          float* d_mapped, void* stream) {
     { const int rc_ = sync_fast_switch(); if (rc_) return rc_; }
-    MPU_REQUIRE(grid && view && d_mapped && view->d_pred && view->d_g && view->d_offsets,
-                "mpu_map_view_nearest: null argument");
-    MPU_REQUIRE(view->dim >= 2 && view->n_planes >= 2, "mpu_map_view_nearest: view needs dim>=2, planes>=2");
-    MapArgs a; to_grid(*grid, a.grid); to_view(*view, a.view);
-    a.Wv = nullptr; a.p_lo = 0; a.p_hi = view->n_planes; a.owns_oob = 1; a.out = d_mapped;
+    MapArgs a;
+    { const int rc_ = make_map_args("mpu_map_view_nearest", grid, view, false, true, nullptr, 0, 0, 1, d_mapped, a); if (rc_) return rc_; }
     return launch_map_view(a, n_classes, false, (hipStream_t)stream);
 }
 
@@ -1476,11 +1514,8 @@ int mpu_map_accumulate_view(const mpu_voxel_grid* grid, const mpu_view_pred* vie
                             const float* d_Wv, int32_t p_lo, int32_t p_hi, int32_t owns_oob,
                             float* d_z, void* stream) {
     { const int rc_ = sync_fast_switch(); if (rc_) return rc_; }
-    MPU_REQUIRE(grid && view && d_z && d_Wv && view->d_pred && view->d_g && view->d_offsets,
-                "mpu_map_accumulate_view: null argument");
-    MPU_REQUIRE(0 <= p_lo && p_lo < p_hi && p_hi <= view->n_planes, "mpu_map_accumulate_view: bad plane range");
-    MapArgs a; to_grid(*grid, a.grid); to_view(*view, a.view);
-    a.Wv = d_Wv; a.p_lo = p_lo; a.p_hi = p_hi; a.owns_oob = owns_oob; a.out = d_z;
+    MapArgs a;
+    { const int rc_ = make_map_args("mpu_map_accumulate_view", grid, view, true, false, d_Wv, p_lo, p_hi, owns_oob, d_z, a); if (rc_) return rc_; }
     return launch_map_view(a, n_classes, true, (hipStream_t)stream);
 }
 
@@ -1488,55 +1523,32 @@ int mpu_map_fuse_views(const mpu_voxel_grid* grid, const mpu_view_pred* views, i
                        int32_t n_classes, const float* d_W, const float* d_b, int32_t sum_fusion,
                        float* d_probs, uint8_t* d_labels, void* stream) {
     { const int rc_ = sync_fast_switch(); if (rc_) return rc_; }
-    MPU_REQUIRE(grid && views, "mpu_map_fuse_views: null argument");
-    MPU_REQUIRE(n_views >= 1 && n_views <= MAX_VIEWS, "mpu_map_fuse_views: n_views must be in 1..16");
-    MPU_REQUIRE(sum_fusion || (d_W && d_b), "mpu_map_fuse_views: W and b required unless sum_fusion");
-    MPU_REQUIRE(d_probs || d_labels, "mpu_map_fuse_views: no output requested");
-    FuseArgs a; to_grid(*grid, a.grid);
-    for (int v = 0; v < n_views; ++v) {
-        MPU_REQUIRE(views[v].d_pred && views[v].d_g && views[v].d_offsets, "mpu_map_fuse_views: null view field");
-        MPU_REQUIRE(views[v].dim >= 2 && views[v].n_planes >= 2, "mpu_map_fuse_views: view needs dim>=2, planes>=2");
-        to_view(views[v], a.views[v]);
-    }
-    a.V = n_views; a.W = d_W; a.b = d_b; a.sum_fusion = sum_fusion; a.probs = d_probs; a.labels = d_labels;
+    FuseArgs a;
+    { const int rc_ = make_fuse_args("mpu_map_fuse_views", grid, views, n_views, d_W, d_b, sum_fusion, d_probs, d_labels, a); if (rc_) return rc_; }
     // straight-line kernel on composed affine maps + exact fix-up of the flagged voxels, when every view is eligible
-    bool fast = fast_path_host() && n_classes >= 1 && n_classes <= 16 && (long)a.grid.X * a.grid.Y * a.grid.Z < (1L << 32);
     FuseFastArgs f;
+    bool fast = fast_grid(a.grid, n_classes) && brick_walk(a.grid.X, a.grid.Y, a.grid.Z, true, f.walk);
     for (int v = 0; fast && v < n_views; ++v) fast = compose_view(a.grid, a.views[v], n_classes, f.v[v]);
     if (fast) {
         hipStream_t st = (hipStream_t)stream;
-        unsigned* nxt = nullptr;
-        { const int rc_ = fuse_scratch(st, &f.count, &nxt, &f.list); if (rc_) return rc_; }
-        FuseCounterGuard guard{st, f.list};
-        constexpr int cfg = 2;                                   // brick / lane layout (0 and 1 measured slower: DESIGN section 4.6)
         f.V = n_views; f.X = a.grid.X; f.Y = a.grid.Y; f.Z = a.grid.Z;
         f.W = d_W; f.b = d_b; f.sum_fusion = sum_fusion; f.probs = d_probs; f.labels = d_labels;
-        f.cap = FUSE_LIST_CAP;
-        long nblk = cfg ? (long)cdiv(f.X, 8) * cdiv(f.Y, 8) * cdiv(f.Z, 16) : (long)cdiv(f.X, 4) * cdiv(f.Y, 4) * cdiv(f.Z, 64);    // bricks
-        constexpr int morton = 2;                                // brick order: z slowest inside an XCD's run (1 = z fastest, 3 = interleaved: section 4.6)
-        f.morton = 0; f.px2 = f.py2 = 0;
-        if (morton) {
-            const int nxb = cdiv(f.X, cfg ? 8 : 4), nyb = cdiv(f.Y, cfg ? 8 : 4), nzb = cdiv(f.Z, cfg ? 16 : 64);
-            while ((1 << f.px2) < nxb) ++f.px2;
-            while ((1 << f.py2) < nyb) ++f.py2;
-            const long padded = (1L << f.px2) * (1L << f.py2) * nzb;
-            if (padded < (1L << 31)) { f.morton = (morton >= 2 && padded % (8L * nzb) == 0) ? morton : 1; nblk = padded; }
-        }
-        f.nblk8 = (unsigned)((nblk + 7) / 8);
-        const dim3 g(f.nblk8 * 8u), b(256);
-        const bool fx_on = env(ENV_FUSE_FX) != 0;                // 0: the fp64 index arithmetic of round 2 (A/B, equality test)
-        bool fx = fx_on && cfg == 2;
+        bool fx = env(ENV_FUSE_FX) != 0;                         // 0: the fp64 index arithmetic of round 2 (A/B, equality test)
         for (int v = 0; fx && v < n_views; ++v) fx = fx_eligible(f.v[v]);
-        if (fx)            { MPU_DISPATCH_K(n_classes, (map_fuse_fast_kernel<KK, 2, true><<<g, b, 0, st>>>(f))); }
-        else if (cfg == 2) { MPU_DISPATCH_K(n_classes, (map_fuse_fast_kernel<KK, 2><<<g, b, 0, st>>>(f))); }
-        else if (cfg == 1) { MPU_DISPATCH_K(n_classes, (map_fuse_fast_kernel<KK, 1><<<g, b, 0, st>>>(f))); }
-        else               { MPU_DISPATCH_K(n_classes, (map_fuse_fast_kernel<KK, 0><<<g, b, 0, st>>>(f))); }
-        { const int rc_ = launch_ok(); if (rc_) return rc_; }
-        MPU_DISPATCH_K(n_classes, (map_fuse_fixup_kernel<KK><<<dim3(256), dim3(512), 0, st>>>(a, f.list, f.count, f.cap, nxt)));
-        if (sched_log_on()) sched_note("map_fuse fast views=%d K=%d brick=%d fx=%d", n_views, n_classes, cfg, fx ? 1 : 0);
-        const int rc_ = launch_ok();
-        guard.done = rc_ == MPU_OK;
-        return rc_;
+        return run_with_fixup(st,
+            [&](unsigned* list, unsigned* count, unsigned cap) -> int {
+                f.list = list; f.count = count; f.cap = cap;
+                const dim3 g(f.walk.nblk8 * 8u), b(256);
+                if (fx) { MPU_DISPATCH_K(n_classes, (map_fuse_fast_kernel<KK, true><<<g, b, 0, st>>>(f))); }
+                else    { MPU_DISPATCH_K(n_classes, (map_fuse_fast_kernel<KK, false><<<g, b, 0, st>>>(f))); }
+                return MPU_OK;
+            },
+            [&](const unsigned* list, const unsigned* count, unsigned cap, unsigned* nxt) -> int {
+                MPU_DISPATCH_K(n_classes, (map_fuse_fixup_kernel<KK><<<dim3(256), dim3(512), 0, st>>>(a, list, count, cap, nxt)));
+                // (brick=2: the one lane layout there is; the log line is as it was when there were three)
+                if (sched_log_on()) sched_note("map_fuse fast views=%d K=%d brick=%d fx=%d", n_views, n_classes, 2, fx ? 1 : 0);
+                return MPU_OK;
+            });
     }
     if (sched_log_on()) sched_note("map_fuse generic views=%d K=%d", n_views, n_classes);
     MPU_DISPATCH_K(n_classes, (map_fuse_kernel<KK><<<dim3(fuse_grid(a.grid)), dim3(256), 0, (hipStream_t)stream>>>(a)));
@@ -1548,11 +1560,8 @@ int mpu_map_fuse_views(const mpu_voxel_grid* grid, const mpu_view_pred* views, i
 int mpu_map_view_linear(const mpu_voxel_grid* grid, const mpu_view_pred* view, int32_t n_classes,
                         float* d_mapped, void* stream) {
     { const int rc_ = sync_fast_switch(); if (rc_) return rc_; }
-    MPU_REQUIRE(grid && view && d_mapped && view->d_pred && view->d_g && view->d_offsets,
-                "mpu_map_view_linear: null argument");
-    MPU_REQUIRE(view->dim >= 2 && view->n_planes >= 2, "mpu_map_view_linear: view needs dim>=2, planes>=2");
-    MapArgs a; to_grid(*grid, a.grid); to_view(*view, a.view);
-    a.Wv = nullptr; a.p_lo = 0; a.p_hi = view->n_planes; a.owns_oob = 1; a.out = d_mapped;
+    MapArgs a;
+    { const int rc_ = make_map_args("mpu_map_view_linear", grid, view, false, true, nullptr, 0, 0, 1, d_mapped, a); if (rc_) return rc_; }
     if (sched_log_on()) sched_note("map_view linear accum=0 K=%d", n_classes);
     MPU_DISPATCH_K(n_classes, (map_view_linear_kernel<KK, false><<<dim3(brick_grid(a.grid)), dim3(256), 0, (hipStream_t)stream>>>(a)));
     return launch_ok();
@@ -1562,12 +1571,8 @@ int mpu_map_accumulate_view_linear(const mpu_voxel_grid* grid, const mpu_view_pr
                                    const float* d_Wv, int32_t p_lo, int32_t p_hi, int32_t owns_oob,
                                    float* d_z, void* stream) {
     { const int rc_ = sync_fast_switch(); if (rc_) return rc_; }
-    MPU_REQUIRE(grid && view && d_z && d_Wv && view->d_pred && view->d_g && view->d_offsets,
-                "mpu_map_accumulate_view_linear: null argument");
-    MPU_REQUIRE(view->dim >= 2 && view->n_planes >= 2, "mpu_map_accumulate_view_linear: view needs dim>=2, planes>=2");
-    MPU_REQUIRE(0 <= p_lo && p_lo < p_hi && p_hi <= view->n_planes, "mpu_map_accumulate_view_linear: bad plane range");
-    MapArgs a; to_grid(*grid, a.grid); to_view(*view, a.view);
-    a.Wv = d_Wv; a.p_lo = p_lo; a.p_hi = p_hi; a.owns_oob = owns_oob; a.out = d_z;
+    MapArgs a;
+    { const int rc_ = make_map_args("mpu_map_accumulate_view_linear", grid, view, true, true, d_Wv, p_lo, p_hi, owns_oob, d_z, a); if (rc_) return rc_; }
     if (sched_log_on()) sched_note("map_view linear accum=1 K=%d", n_classes);
     MPU_DISPATCH_K(n_classes, (map_view_linear_kernel<KK, true><<<dim3(brick_grid(a.grid)), dim3(256), 0, (hipStream_t)stream>>>(a)));
     return launch_ok();
@@ -1577,17 +1582,8 @@ int mpu_map_fuse_views_linear(const mpu_voxel_grid* grid, const mpu_view_pred* v
                               int32_t n_classes, const float* d_W, const float* d_b, int32_t sum_fusion,
                               float* d_probs, uint8_t* d_labels, void* stream) {
     { const int rc_ = sync_fast_switch(); if (rc_) return rc_; }
-    MPU_REQUIRE(grid && views, "mpu_map_fuse_views_linear: null argument");
-    MPU_REQUIRE(n_views >= 1 && n_views <= MAX_VIEWS, "mpu_map_fuse_views_linear: n_views must be in 1..16");
-    MPU_REQUIRE(sum_fusion || (d_W && d_b), "mpu_map_fuse_views_linear: W and b required unless sum_fusion");
-    MPU_REQUIRE(d_probs || d_labels, "mpu_map_fuse_views_linear: no output requested");
-    FuseArgs a; to_grid(*grid, a.grid);
-    for (int v = 0; v < n_views; ++v) {
-        MPU_REQUIRE(views[v].d_pred && views[v].d_g && views[v].d_offsets, "mpu_map_fuse_views_linear: null view field");
-        MPU_REQUIRE(views[v].dim >= 2 && views[v].n_planes >= 2, "mpu_map_fuse_views_linear: view needs dim>=2, planes>=2");
-        to_view(views[v], a.views[v]);
-    }
-    a.V = n_views; a.W = d_W; a.b = d_b; a.sum_fusion = sum_fusion; a.probs = d_probs; a.labels = d_labels;
+    FuseArgs a;
+    { const int rc_ = make_fuse_args("mpu_map_fuse_views_linear", grid, views, n_views, d_W, d_b, sum_fusion, d_probs, d_labels, a); if (rc_) return rc_; }
     if (sched_log_on()) sched_note("map_fuse linear views=%d K=%d", n_views, n_classes);
     MPU_DISPATCH_K(n_classes, (map_fuse_linear_kernel<KK><<<dim3(brick_grid(a.grid)), dim3(256), 0, (hipStream_t)stream>>>(a)));
     return launch_ok();

@@ -327,6 +327,70 @@ def test_fast_paths_equal_exact_search_at_scale(aff):
         assert torch.equal(a, b_)
 
 
+def test_fused_fixed_point_screen_equals_fp64_screen_subprocess(tmp_path):
+    """map_fuse_fast_kernel screens a lane's index coordinates in 32-bit fixed point (FX); MPU_FUSE_FX=0 (read once per
+    process, hence fresh interpreters, one after the other) selects the kernel's fp64 screen, which is also what a view
+    that is not FX-eligible runs. Probabilities and labels must be IDENTICAL on the "odd" case of
+    test_fast_paths_equal_exact_search_at_scale (50x47x61, K = 5, five views, Z % 4 != 0: unpacked stores) and on a
+    64x56x68, K = 3 rotated volume fused to labels only (the packed 32-bit label store); the schedule log must show
+    fx=1 in the default process and fx=0 in the other."""
+    import os, subprocess, sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    script = r'''
+import sys, numpy as np, torch
+sys.path.insert(0, %r)
+from multiplanarunet_amd import _lib
+from multiplanarunet_amd.interpolation import Volume, ViewGeometry, map_and_fuse
+sys.path.insert(0, %r)
+from test_gpu_geometry import _schedule_log
+lib = _lib.load()
+views = np.array([[0, 0, 1], [1, 0, 0], [0, 1, 0], [0.3, 0.5, 0.8], [-0.6, 0.64, 0.48]], float)
+th = np.deg2rad(25.0)
+R = np.array([[np.cos(th), -np.sin(th), 0], [np.sin(th), np.cos(th), 0], [0, 0, 1]])
+A_odd = np.eye(4); A_odd[:3, :3] = np.diag([1.7, 1.9, 1.1])
+A_rot = np.eye(4); A_rot[:3, :3] = R.dot(np.diag([1.0, 0.8, 1.5])); A_rot[:3, 3] = [3.0, -2.0, 5.0]
+out, log = {}, []
+for name, A, shape, K, dim, want_probs in (("odd", A_odd, (50, 47, 61), 5, 96, True), ("packed", A_rot, (64, 56, 68), 3, 64, False)):
+    rng = np.random.RandomState(3)
+    vol = Volume(rng.randn(*shape, 1).astype(np.float32), None, A)
+    W = torch.tensor(rng.uniform(.5, 1.5, (len(views), K)).astype(np.float32))
+    b = torch.tensor(rng.uniform(-.1, .1, (K,)).astype(np.float32))
+    preds = []
+    for vi, v in enumerate(views):
+        g = ViewGeometry(v, dim, float(dim), "same+20")
+        pr = torch.tensor(np.random.RandomState(10 + vi).rand(g.n_planes, dim, dim, K).astype(np.float32), device="cuda")
+        preds.append((pr, (g.real_axis, g.real_axis, g.offsets), g.inv_basis))
+    (probs, labels), lines = _schedule_log(lib, lambda: map_and_fuse(vol, preds, W, b, want_probs=want_probs))
+    torch.cuda.synchronize()
+    log += [name + ": " + l for l in lines]
+    out[name + "_labels"] = labels.cpu().numpy()
+    if want_probs:
+        out[name + "_probs"] = probs.cpu().numpy()
+np.savez(sys.argv[1], log=np.array(log), **out)
+''' % (os.path.dirname(here), here)
+    res = {}
+    for fx in ("1", "0"):
+        path = str(tmp_path / ("fx%s.npz" % fx))
+        env = dict(os.environ)
+        env.pop("MPU_FUSE_FX", None)
+        if fx == "0":
+            env["MPU_FUSE_FX"] = "0"
+        r = subprocess.run([sys.executable, "-c", script, path], env=env, capture_output=True, text=True,
+                           cwd=os.path.dirname(here), timeout=120)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        res[fx] = np.load(path)
+        log = [str(l) for l in res[fx]["log"]]
+        for name in ("odd", "packed"):
+            fused = [l for l in log if l.startswith(name + ": map_fuse ")]
+            assert len(fused) == 1 and fused[0].startswith(name + ": map_fuse fast") and fused[0].endswith("fx=" + fx), log
+    keys = ("odd_probs", "odd_labels", "packed_labels")
+    assert sorted(k for k in res["1"].files if k != "log") == sorted(keys)
+    for k in keys:
+        assert res["1"][k].shape == res["0"][k].shape and res["1"][k].size > 0
+        assert np.array_equal(res["1"][k], res["0"][k]), (k, int((res["1"][k] != res["0"][k]).sum()))
+    assert len(np.unique(res["1"]["packed_labels"])) == 3 and len(np.unique(res["1"]["odd_labels"])) == 5
+
+
 def test_cell_division_is_ieee():
     """The straight-line sampler divides by a cell width through a Newton-refined reciprocal of the axis step
     (csrc/geometry.hip cell_div); it must give the IEEE quotient the reference's NumPy division gives. 2^28

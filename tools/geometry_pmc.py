@@ -20,10 +20,10 @@ out = {"note": __doc__.strip().split("\n", 2)[2], "kernels": {}}
 for name, (v, k, t) in fetch.items():
     if not any(s in name for s in ("map_fuse", "map_view", "sample_f", "sample_view")):
         continue
-    mt = re.search(r"(map_fuse_fast_kernel|map_fuse_fixup_kernel|map_view_fast_kernel|map_view_fixup_kernel|sample_fast_kernel|sample_fixup_kernel|map_fuse_kernel|sample_view_planes_kernel)ILi(\d+)E?L?[ib]?(\d*)", name)
+    mt = re.search(r"map_fuse_fast_kernelILi(\d+)E", name)
     short = name.replace("_ZN3mpu", "")[:70]
-    if mt and mt.group(1) == "map_fuse_fast_kernel":
-        short = "map_fuse_fast_kernel<%s,%s>" % (mt.group(2), mt.group(3) or "2")
+    if mt:          # <K,2>: the key bench.py and the earlier profiles use (2 = the one brick layout; not the FX flag)
+        short = "map_fuse_fast_kernel<%s,2>" % mt.group(1)
     wv = write.get(name, (0.0, k, 0))[0]
     out["kernels"][short] = {"launches": k, "avg_us_profiled": round(t / k / 1e3, 1), "fetch_KB_raw_per_launch": round(v / k, 1),
                              "write_KB_per_launch": round(wv / k, 1), "hbm_bytes_per_launch": int((2 * v + wv) * 1024 / k)}
