@@ -307,7 +307,9 @@ int mpu_unet_prepare_inference(const mpu_unet* m, const float* d_params, const f
  *   the moving statistics in d_bn_state; activations stay in d_workspace for
  *   mpu_unet_backward. */
 /* d_out may be NULL in training mode: the probabilities then stay in the workspace only, at byte offset
- * mpu_unet_workspace_probs_offset(m, batch) (f32 [B,H,W,n_classes]; valid until the next forward on that workspace). */
+ * mpu_unet_workspace_probs_offset(m, batch) (f32 [B,H,W,n_classes]; valid until the next forward on that workspace). On a handle
+ * created with softmax == 0 the region holds the LOGITS (what d_out would have received): the backward pass of
+ * MPU_LOSS_SPARSE_CE_LOGITS reads them there. */
 int64_t mpu_unet_workspace_probs_offset(const mpu_unet* m, int32_t batch);
 /* Byte offset (inside the workspace of `batch`) of ONE float: the mean over the B*H*W pixels of the weighted per-pixel loss of the
  * last backward pass (= mean of the d_loss tensor mpu_unet_backward fills; written by the pass whether d_loss is NULL or not;
@@ -327,7 +329,7 @@ int mpu_unet_forward(const mpu_unet* m, int32_t batch, const float* d_x, const f
  * Must follow mpu_unet_forward(training=1) on the same workspace -- ONE backward pass per training forward: the forward's first
  * launch zeroes the fixed-point BatchNorm accumulators of both passes (round 6, bf16 / bf16x3), a second backward pass on the same
  * forward would add to the first one's sums. The handle remembers which form of the head the last training forward ran (with a
- * 64-channel last block and a softmax head it leaves NO post-BatchNorm tensor of that block in the workspace; the backward pass
+ * 64-channel last block and a head that trains it leaves NO post-BatchNorm tensor of that block in the workspace; the backward pass
  * then recomputes it): forward and backward of one step run on the same handle, not interleaved with another step's. */
 int mpu_unet_backward(const mpu_unet* m, int32_t batch, const uint8_t* d_y,
                       const float* d_sample_weight, const float* d_params, const void* d_packed,
@@ -345,9 +347,17 @@ int mpu_unet_backward(const mpu_unet* m, int32_t batch, const uint8_t* d_y,
  *   MPU_LOSS_DICE / MPU_LOSS_JACCARD : smooth >= 0                                   loss_functions.py:80-112 / :33-77
  *   MPU_LOSS_GENERALIZED_DICE        : type_weight (mpu_gdl_weight)                  :207-266
  *   MPU_LOSS_FOCAL                   : gamma, class_weights[n_class_weights] (0 or n_classes entries)   :166-204
- *   MPU_LOSS_EXP_LOG                 : gamma_dice, gamma_cross, weight_dice, weight_cross               :115-163 */
+ *   MPU_LOSS_EXP_LOG                 : gamma_dice, gamma_cross, weight_dice, weight_cross               :115-163
+ * MPU_LOSS_SPARSE_CE_LOGITS is tf.keras.losses.SparseCategoricalCrossentropy(reduction=NONE, from_logits=True) on a handle created
+ * with softmax == 0 (`build.out_activation: linear` + `fit.loss_kwargs: {from_logits: true}`): TF 2.3 goes straight to
+ * sparse_softmax_cross_entropy_with_logits, without the probability clip of MPU_LOSS_SPARSE_CE. Per pixel, with z the K logits:
+ * L = logsumexp_k(z_k) - z_y (the maximum subtracted first), d_loss f32 [B,H*W] = w_b * L as for MPU_LOSS_SPARSE_CE, the logged mean
+ * over the B*H*W pixels, gradient of the sum dz_k = w_b * (softmax(z)_k - [k == y]) with no clip mask. It takes no field but `kind`,
+ * changes no workspace size or offset, and is the only loss with which a softmax == 0 handle trains: mpu_unet_backward /
+ * _backward_events / _backward_adam accept such a handle if and only if it is attached. MPU_LOSS_SPARSE_CE on such a handle detaches
+ * it again. The output of the forward pass stays the logits. */
 typedef enum { MPU_LOSS_SPARSE_CE = 0, MPU_LOSS_DICE = 1, MPU_LOSS_JACCARD = 2, MPU_LOSS_GENERALIZED_DICE = 3,
-               MPU_LOSS_FOCAL = 4, MPU_LOSS_EXP_LOG = 5 } mpu_loss_kind;
+               MPU_LOSS_FOCAL = 4, MPU_LOSS_EXP_LOG = 5, MPU_LOSS_SPARSE_CE_LOGITS = 6 } mpu_loss_kind;
 typedef enum { MPU_GDL_SQUARE = 0, MPU_GDL_SIMPLE = 1, MPU_GDL_UNIFORM = 2 } mpu_gdl_weight;
 typedef struct {
     int32_t kind;              /* mpu_loss_kind                                        */
@@ -359,7 +369,8 @@ typedef struct {
     float   class_weights[8];
 } mpu_loss_config;
 /* MPU_EINVAL + mpu_last_error() on an unknown kind or type_weight, a negative smooth, a class-weight count that is neither 0 nor
- * n_classes, or a handle created with softmax == 0. MPU_EUNSUPPORTED on a handle with more than 8 classes unless cfg is the
+ * n_classes, one of the five per-image kinds on a handle created with softmax == 0, or MPU_LOSS_SPARSE_CE_LOGITS on a handle created
+ * with softmax == 1 (it would apply the softmax twice). MPU_EUNSUPPORTED on a handle with more than 8 classes unless cfg is the
  * default (MPU_LOSS_SPARSE_CE, no class weights). */
 int mpu_unet_set_loss(mpu_unet* m, const mpu_loss_config* cfg);
 
@@ -614,6 +625,13 @@ int mpu_train_metrics_update(const float* d_pred, const uint8_t* d_y, int64_t n,
 int64_t mpu_eval_loss_scratch_bytes(int32_t B, int64_t ppi, int32_t n_classes);
 int mpu_eval_loss(const mpu_loss_config* cfg, const float* d_pred, const uint8_t* d_y, const float* d_sw, int32_t B, int64_t ppi,
                   int32_t n_classes, void* d_scratch, float* d_loss, double* d_acc, void* stream);
+/* MPU_LOSS_SPARSE_CE_LOGITS of one batch: mpu_eval_loss reads probabilities and keeps refusing kind 6; this entry reads d_logits f32
+ * [B, ppi, n_classes], the output of a handle created with softmax == 0. L_b = the mean over the image's pixels of
+ * logsumexp_k(z_k) - z_y, formed in f64 from the f32 logits with the maximum subtracted. Everything else -- d_y, d_sw, d_loss, d_acc,
+ * the ranges, the scratch size (mpu_eval_loss_scratch_bytes), the chunking and the fixed summation order, the skip of labels
+ * >= n_classes, the error codes -- is mpu_eval_loss's. */
+int mpu_eval_loss_logits(const float* d_logits, const uint8_t* d_y, const float* d_sw, int32_t B, int64_t ppi, int32_t n_classes,
+                         void* d_scratch, float* d_loss, double* d_acc, void* stream);
 
 /* Measurement aid (bench.py roofline leg; no reference counterpart): when
  * enabled, every MFMA convolution launch is bracketed by HIP events recorded on

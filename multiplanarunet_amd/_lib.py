@@ -21,6 +21,7 @@ ABI_VERSION = 2                         # mpu_abi_version() this binding was wri
 # mpu_loss_kind / mpu_gdl_weight
 (MPU_LOSS_SPARSE_CE, MPU_LOSS_DICE, MPU_LOSS_JACCARD, MPU_LOSS_GENERALIZED_DICE, MPU_LOSS_FOCAL,
  MPU_LOSS_EXP_LOG) = range(6)
+MPU_LOSS_SPARSE_CE_LOGITS = 6           # mpu_unet_set_loss on a handle with softmax == 0 only; evaluated by mpu_eval_loss_logits
 MPU_GDL_SQUARE, MPU_GDL_SIMPLE, MPU_GDL_UNIFORM = 0, 1, 2
 # mpu_optimizer_kind / mpu_optimizer_flag
 MPU_OPT_ADAM, MPU_OPT_SGD, MPU_OPT_RMSPROP, MPU_OPT_ADAMAX = range(4)
@@ -171,6 +172,7 @@ _SIGS = {
     "mpu_train_metrics_update": (C.c_int, [c_p, c_p, i64, i32, c_p, c_p]),
     "mpu_eval_loss_scratch_bytes": (i64, [i32, i64, i32]),
     "mpu_eval_loss": (C.c_int, [C.POINTER(LossConfig), c_p, c_p, c_p, i32, i64, i32, c_p, c_p, c_p, c_p]),
+    "mpu_eval_loss_logits": (C.c_int, [c_p, c_p, c_p, i32, i64, i32, c_p, c_p, c_p, c_p]),
     "mpu_geometry_set_fast_path": (C.c_int, [i32]),
     "mpu_geometry_check_cell_division": (C.c_int, [C.POINTER(Axis), i64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "mpu_probe_mfma_bf16": (C.c_int, [i32, i32, c_p, C.POINTER(f64), c_p]),

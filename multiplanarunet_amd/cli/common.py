@@ -43,6 +43,21 @@ def load_hparams(project_dir):
     return hp
 
 
+def validate_output_loss(hp):
+    """build.out_activation against fit.loss / fit.loss_kwargs, before `mp train` creates anything: a linear output trains only
+    with the cross-entropy from logits (bin/train.py:130 names that configuration), and from_logits on a softmax output is
+    refused with UNet.compile's own error."""
+    from ..unet import resolve_ce_kwargs
+    fit, act = hp["fit"], hp["build"].get("out_activation", "softmax")
+    loss = fit["loss"][0] if isinstance(fit["loss"], (list, tuple)) and len(fit["loss"]) == 1 else fit["loss"]
+    if not (isinstance(loss, str) and "sparsecategoricalcrossentropy" in loss.lower().replace("_", "")):
+        return
+    from_logits = resolve_ce_kwargs(fit.get("loss_kwargs"), act)
+    if act == "linear" and not from_logits:
+        raise ValueError("build.out_activation: linear trains only with the cross-entropy from logits: add "
+                         "fit.loss_kwargs: {from_logits: true} to train_hparams.yaml (or build a softmax output)")
+
+
 def load_dataset(cfg, project_dir, hp, device, synthetic=0, seed=0, need_labels=True):
     """List of Volume objects for one of train_data / val_data / test_data (or synthetic toy volumes)."""
     fit = hp["fit"]

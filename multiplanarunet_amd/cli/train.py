@@ -11,7 +11,8 @@ import torch
 
 from .common import (validate_project_dir, load_hparams, load_dataset, load_or_create_views,
                      fill_build_from_data, save_audited_hparams, set_bias_weights_on_all_outputs,
-                     init_callback_objects, remove_validation_callbacks, DEFAULT_CALLBACKS, note_inert_flags)
+                     init_callback_objects, remove_validation_callbacks, DEFAULT_CALLBACKS, note_inert_flags,
+                     validate_output_loss)
 
 
 def get_argparser():
@@ -112,6 +113,7 @@ def run(args):
     hp = load_hparams(project_dir)
     if hp["build"].get("n_classes"):                       # (an audited YAML; one that leaves it to the data is checked below)
         require_trainable(hp["build"]["n_classes"], "mp train")
+    validate_output_loss(hp)                               # a linear output needs fit.loss_kwargs.from_logits, a softmax one refuses it
     note_inert_flags(args, [("no_images", "no sample images are written during training"), ("debug", "the TF debugger has no counterpart"),
                             ("max_loaded_images", "volumes stay resident in HBM: there is no image queue"),
                             ("num_access", "volumes stay resident in HBM: there is no image queue")], log)

@@ -46,6 +46,38 @@ __global__ __launch_bounds__(256) void eval_ce_stats_kernel(const float* __restr
     if (threadIdx.x == 0) part[(long)b * gridDim.x + chunk] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
+// The cross-entropy from logits (MPU_LOSS_SPARSE_CE_LOGITS; the per-pixel value of head_loss_grad<HL_CE_LOGITS>, unet_ops.hip):
+// logsumexp_k z_k - z_y in f64 from the f32 logits, the maximum subtracted. Same chunks, same order, same skip as above.
+template <int K>
+__global__ __launch_bounds__(256) void eval_ce_logits_stats_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ y, long ppi,
+                                                                  double* __restrict__ part) {
+    __shared__ double red[4];
+    const int b = blockIdx.y, chunk = blockIdx.x;
+    const long base = (long)b * ppi;
+    double s = 0.0;
+    for (int i = 0; i < CE_PPT; ++i) {
+        const long m = (long)chunk * CE_CHUNK + (long)i * 256 + threadIdx.x;
+        if (m >= ppi) break;
+        const int yy = y[base + m];
+        if (yy >= K) continue;                                   // a label outside the classes: in no sum, and it indexes nothing
+        float z[K];
+        float mx, zy;
+#pragma unroll
+        for (int k = 0; k < K; ++k) z[k] = logits[(base + m) * K + k];
+        mx = z[0]; zy = z[0];
+#pragma unroll
+        for (int k = 1; k < K; ++k) { mx = fmaxf(mx, z[k]); if (k == yy) zy = z[k]; }
+        double S = 0.0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) S += exp((double)z[k] - (double)mx);
+        s += log(S) - ((double)zy - (double)mx);
+    }
+    for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(long)b * gridDim.x + chunk] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 // one workgroup; scratch (doubles): part [B][nchunk] | wl [B]
 __global__ __launch_bounds__(256) void eval_ce_finalize_kernel(const float* __restrict__ sw, int B, int nchunk, double inv_ppi,
                                                               double* __restrict__ scratch, float* __restrict__ d_loss,
@@ -68,11 +100,12 @@ __global__ __launch_bounds__(256) void eval_ce_finalize_kernel(const float* __re
 }
 
 int launch_eval_ce(const float* probs, const uint8_t* y, const float* sw, int B, long ppi, int K, double* scratch, float* d_loss,
-                   double* acc, hipStream_t st) {
+                   double* acc, hipStream_t st, bool logits = false) {
     const int nchunk = (int)((ppi + CE_CHUNK - 1) / CE_CHUNK);
     const dim3 grid((unsigned)nchunk, (unsigned)B);
     switch (K) {
-#define MPU_CE_CASE(KK) case KK: eval_ce_stats_kernel<KK><<<grid, 256, 0, st>>>(probs, y, ppi, scratch); break;
+#define MPU_CE_CASE(KK) case KK: if (logits) eval_ce_logits_stats_kernel<KK><<<grid, 256, 0, st>>>(probs, y, ppi, scratch); \
+                                 else eval_ce_stats_kernel<KK><<<grid, 256, 0, st>>>(probs, y, ppi, scratch); break;
         MPU_CE_CASE(1) MPU_CE_CASE(2) MPU_CE_CASE(3) MPU_CE_CASE(4) MPU_CE_CASE(5) MPU_CE_CASE(6) MPU_CE_CASE(7) MPU_CE_CASE(8)
 #undef MPU_CE_CASE
         default: return fail(MPU_EUNSUPPORTED, "%s", "mpu_eval_loss: 1..8 classes");
@@ -100,6 +133,7 @@ extern "C" int64_t mpu_eval_loss_scratch_bytes(int32_t B, int64_t ppi, int32_t n
 extern "C" int mpu_eval_loss(const mpu_loss_config* cfg, const float* d_pred, const uint8_t* d_y, const float* d_sw, int32_t B,
                              int64_t ppi, int32_t n_classes, void* d_scratch, float* d_loss, double* d_acc, void* stream) {
     MPU_REQUIRE(cfg && d_pred && d_y && d_scratch, "mpu_eval_loss: null argument");
+    MPU_REQUIRE(cfg->kind != MPU_LOSS_SPARSE_CE_LOGITS, "mpu_eval_loss: reads probabilities; the cross-entropy from logits is mpu_eval_loss_logits");
     MPU_REQUIRE(cfg->kind >= MPU_LOSS_SPARSE_CE && cfg->kind <= MPU_LOSS_EXP_LOG, "mpu_eval_loss: unknown loss kind");
     MPU_REQUIRE(((uintptr_t)d_scratch & 7) == 0 && ((uintptr_t)d_acc & 7) == 0, "mpu_eval_loss: d_scratch and d_acc must be 8-byte aligned");
     if (!eval_shape_ok(B, (long)ppi, n_classes))
@@ -113,4 +147,13 @@ extern "C" int mpu_eval_loss(const mpu_loss_config* cfg, const float* d_pred, co
         return launch_eval_ce(d_pred, d_y, d_sw, B, (long)ppi, n_classes, (double*)d_scratch, d_loss, d_acc, st);
     return launch_head_loss_coeffs(*cfg, d_pred, d_y, d_sw, B, (long)ppi, n_classes, (double*)d_scratch, nullptr, d_loss, nullptr, st,
                                    d_acc);
+}
+
+extern "C" int mpu_eval_loss_logits(const float* d_logits, const uint8_t* d_y, const float* d_sw, int32_t B, int64_t ppi,
+                                    int32_t n_classes, void* d_scratch, float* d_loss, double* d_acc, void* stream) {
+    MPU_REQUIRE(d_logits && d_y && d_scratch, "mpu_eval_loss_logits: null argument");
+    MPU_REQUIRE(((uintptr_t)d_scratch & 7) == 0 && ((uintptr_t)d_acc & 7) == 0, "mpu_eval_loss_logits: d_scratch and d_acc must be 8-byte aligned");
+    if (!eval_shape_ok(B, (long)ppi, n_classes))
+        return fail(MPU_EUNSUPPORTED, "%s", "mpu_eval_loss_logits: need 1 <= B <= 65535, 1 <= ppi <= 2^40, 1 <= n_classes <= 8");
+    return launch_eval_ce(d_logits, d_y, d_sw, B, (long)ppi, n_classes, (double*)d_scratch, d_loss, d_acc, (hipStream_t)stream, true);
 }

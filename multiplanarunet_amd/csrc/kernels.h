@@ -309,7 +309,10 @@ int launch_head_combine(const float* partial, long M, int K, const float* bh, in
 enum { HL_CE = 0,         // Keras sparse CE: no table, per-pixel loss out of the head pass
        HL_REGION = 1,     // Dice / Jaccard / generalized Dice: a, c only, no clip
        HL_FOCAL = 2,      // f only: (cw_y / ppi) * (gamma (1-q)^(gamma-1) log q - (1-q)^gamma / q)
-       HL_EXPLOG = 3 };   // a, c on the clipped sums + f = -(weight_cross gamma_cross / ppi) (-log q)^(gamma_cross-1) / q
+       HL_EXPLOG = 3,     // a, c on the clipped sums + f = -(weight_cross gamma_cross / ppi) (-log q)^(gamma_cross-1) / q
+       HL_CE_LOGITS = 4 };// sparse CE from logits (MPU_LOSS_SPARSE_CE_LOGITS): `probs` holds logits; no table, no clip, per-pixel loss as HL_CE
+// the forms whose per-pixel loss and mean come out of the head pass itself (the others: launch_head_loss_coeffs)
+constexpr bool head_loss_per_pixel(int form) { return form == HL_CE || form == HL_CE_LOGITS; }
 struct HeadLoss { int kind; const float* coef /* [B][K][2] = a, c */; float inv_ppi, gamma, wcross; float cw[8]; };
 // x^e for x > 0 (1 - q and -log q of a probability clipped to [1e-7, 1 - 1e-7]). The statistics pass forms it in f64; the head
 // kernels (register budget: f64 exp / log spill there) as expf(e logf(x)) with the product's rounding error carried along --
@@ -320,8 +323,9 @@ __device__ __forceinline__ float head_pow(float x, float e) {
     const float r = expf(t);
     return fmaf(r, lo, r);
 }
+inline bool loss_is_per_image(int loss_kind) { return loss_kind >= MPU_LOSS_DICE && loss_kind <= MPU_LOSS_EXP_LOG; }
 inline int head_loss_form(int loss_kind) {
-    return loss_kind == MPU_LOSS_SPARSE_CE ? HL_CE : loss_kind == MPU_LOSS_FOCAL ? HL_FOCAL : loss_kind == MPU_LOSS_EXP_LOG ? HL_EXPLOG : HL_REGION;
+    return loss_kind == MPU_LOSS_SPARSE_CE ? HL_CE : loss_kind == MPU_LOSS_SPARSE_CE_LOGITS ? HL_CE_LOGITS : loss_kind == MPU_LOSS_FOCAL ? HL_FOCAL : loss_kind == MPU_LOSS_EXP_LOG ? HL_EXPLOG : HL_REGION;
 }
 // Statistics pass + coefficient step of such a loss, two launches: per image and class I = sum [y=k] p, P = sum p, R = sum [y=k]
 // (exp-log: on the clipped p) and the image's sum of the per-pixel term (focal, exp-log), in fixed-order f64 partials whose

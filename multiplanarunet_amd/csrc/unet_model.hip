@@ -229,7 +229,7 @@ Plan make_plan(const mpu_unet* m, int B) {
     }
     P.coeffs = take(3L * m->cmax * 4);
     P.stats = take(m->n_stats * 4);
-    if (m->loss.kind != MPU_LOSS_SPARSE_CE) {       // (at the end: every other offset is the cross-entropy plan's)
+    if (loss_is_per_image(m->loss.kind)) {          // (at the end: every other offset is the cross-entropy plan's)
         P.loss_scratch = take(head_loss_scratch_doubles(B, (long)m->cfg.H * m->cfg.W, m->cfg.n_classes) * 8);
         P.loss_coef = take((long)B * m->cfg.n_classes * 2 * 4);
     }
@@ -462,10 +462,11 @@ int conv_wgrad(Run& r, size_t ci_) {
 }
 
 // Round 6: the training step's head as the three head_bn_* passes (unet_ops.hip): bf16 or bf16x3 (accumulator mode), a 64-channel last block
-// feeding a softmax head, no launch tap (the replay tests check the unfused kernels launch by launch)
+// feeding a softmax head -- or a linear one that trains (MPU_LOSS_SPARSE_CE_LOGITS attached) --, no launch tap (the replay tests check
+// the unfused kernels launch by launch)
 bool head_train_fused_wanted(const Run& r) {
     const mpu_unet* m = r.m;
-    return env(ENV_HEAD_TRAIN_FUSED) != 0 && r.acc_mode && !m->tap && m->cfg.softmax &&
+    return env(ENV_HEAD_TRAIN_FUSED) != 0 && r.acc_mode && !m->tap && (m->cfg.softmax || m->loss.kind == MPU_LOSS_SPARSE_CE_LOGITS) &&
            m->F[0] == 64 && head_train_fused_shape_ok(m->cfg.dtype, m->head_C, m->cfg.n_classes);
 }
 
@@ -650,7 +651,9 @@ int run_backward(Run& r, const uint8_t* d_y, const float* d_sw, float* d_loss, c
     // then the same head kernels in that loss's form, which produce neither
     HeadLoss hlv{}; const HeadLoss* hl = nullptr;
     float* loss_mean = (float*)r.at(P.loss_mean);
-    if (m->loss.kind != MPU_LOSS_SPARSE_CE) {
+    if (m->loss.kind == MPU_LOSS_SPARSE_CE_LOGITS) {            // per-pixel loss and mean out of the head pass, as the default's
+        hlv.kind = HL_CE_LOGITS; hl = &hlv;
+    } else if (m->loss.kind != MPU_LOSS_SPARSE_CE) {
         const long ppi = (long)m->cfg.H * m->cfg.W;
         hlv.kind = head_loss_form(m->loss.kind); hlv.coef = (const float*)r.at(P.loss_coef); hlv.inv_ppi = (float)(1.0 / (double)ppi);
         hlv.gamma = m->loss.kind == MPU_LOSS_FOCAL ? m->loss.gamma : m->loss.gamma_cross; hlv.wcross = m->loss.weight_cross;
@@ -890,6 +893,8 @@ int require_trainable(const mpu_unet* m) {
         return fail(MPU_EUNSUPPORTED, "%s", "U-Net training and evaluation support 1..8 classes; 9..16 are inference-only");
     return MPU_OK;
 }
+// A handle created with softmax == 0 trains with the cross-entropy from logits alone (mpu_unet_set_loss).
+bool trains(const mpu_unet* m) { return m->cfg.softmax || m->loss.kind == MPU_LOSS_SPARSE_CE_LOGITS; }
 
 }  // namespace
 
@@ -957,8 +962,12 @@ void mpu_unet_destroy(mpu_unet* m) {
 
 int mpu_unet_set_loss(mpu_unet* m, const mpu_loss_config* cfg) {
     MPU_REQUIRE(m && cfg, "mpu_unet_set_loss: null argument");
-    MPU_REQUIRE(m->cfg.softmax, "mpu_unet_set_loss: the losses are defined on probabilities (out_activation='softmax')");
-    MPU_REQUIRE(cfg->kind >= MPU_LOSS_SPARSE_CE && cfg->kind <= MPU_LOSS_EXP_LOG, "mpu_unet_set_loss: unknown loss kind");
+    if (cfg->kind == MPU_LOSS_SPARSE_CE_LOGITS)
+        MPU_REQUIRE(!m->cfg.softmax, "mpu_unet_set_loss: the cross-entropy from logits needs a handle created with softmax == 0 "
+                                     "(out_activation='linear'): on probabilities it would apply the softmax twice");
+    else if (cfg->kind != MPU_LOSS_SPARSE_CE || cfg->n_class_weights != 0)     // (plain cross-entropy on a linear handle: detaches the above)
+        MPU_REQUIRE(m->cfg.softmax, "mpu_unet_set_loss: the losses are defined on probabilities (out_activation='softmax')");
+    MPU_REQUIRE(cfg->kind >= MPU_LOSS_SPARSE_CE && cfg->kind <= MPU_LOSS_SPARSE_CE_LOGITS, "mpu_unet_set_loss: unknown loss kind");
     if (cfg->kind == MPU_LOSS_DICE || cfg->kind == MPU_LOSS_JACCARD)
         MPU_REQUIRE(cfg->smooth >= 0.f, "mpu_unet_set_loss: smooth must not be negative");      // (a NaN fails this too)
     if (cfg->kind == MPU_LOSS_GENERALIZED_DICE)
@@ -1053,7 +1062,7 @@ int mpu_unet_backward(const mpu_unet* m, int32_t batch, const uint8_t* d_y, cons
                       const float* d_params, const void* d_packed, float* d_bn_state, void* d_workspace,
                       float* d_grads, float* d_loss, void* stream) {
     MPU_REQUIRE(d_y && d_sample_weight && d_grads, "mpu_unet_backward: null argument");
-    MPU_REQUIRE(m && m->cfg.softmax, "mpu_unet_backward: training needs out_activation='softmax'");
+    MPU_REQUIRE(m && trains(m), "mpu_unet_backward: training needs out_activation='softmax'");
     RC(require_trainable(m));
     Run r;
     RC(make_run(r, m, batch, d_params, d_packed, d_bn_state, d_grads, d_workspace, stream));
@@ -1065,7 +1074,7 @@ int mpu_unet_backward_adam(const mpu_unet* m, int32_t batch, const uint8_t* d_y,
                            float* d_loss, float* d_m, float* d_v, int64_t t, int64_t* d_step, double lr, double beta1,
                            double beta2, double eps, void* stream) {
     MPU_REQUIRE(d_y && d_sample_weight && d_grads && d_m && d_v, "mpu_unet_backward_adam: null argument");
-    MPU_REQUIRE(m && m->cfg.softmax, "mpu_unet_backward_adam: training needs out_activation='softmax'");
+    MPU_REQUIRE(m && trains(m), "mpu_unet_backward_adam: training needs out_activation='softmax'");
     RC(require_trainable(m));
     MPU_REQUIRE(d_step || t >= 1, "mpu_unet_backward_adam: need a device step counter or a 1-based step number");
     Run r;
@@ -1105,7 +1114,7 @@ int mpu_unet_backward_events(const mpu_unet* m, int32_t batch, const uint8_t* d_
                              float* d_grads, float* d_loss, void* const* ready_events, int32_t n_events,
                              void* stream) {
     MPU_REQUIRE(d_y && d_sample_weight && d_grads, "mpu_unet_backward_events: null argument");
-    MPU_REQUIRE(m && m->cfg.softmax, "mpu_unet_backward_events: training needs out_activation='softmax'");
+    MPU_REQUIRE(m && trains(m), "mpu_unet_backward_events: training needs out_activation='softmax'");
     RC(require_trainable(m));
     Run r;
     RC(make_run(r, m, batch, d_params, d_packed, d_bn_state, d_grads, d_workspace, stream));

@@ -1188,6 +1188,7 @@ __global__ __launch_bounds__(256) void head_forward_kernel(const T* __restrict__
         case HL_REGION: { constexpr int LL = HL_REGION; BODY } break;       \
         case HL_FOCAL: { constexpr int LL = HL_FOCAL; BODY } break;         \
         case HL_EXPLOG: { constexpr int LL = HL_EXPLOG; BODY } break;       \
+        case HL_CE_LOGITS: { constexpr int LL = HL_CE_LOGITS; BODY } break; \
         default: return fail(MPU_EINVAL, "%s", "head: unknown loss form");  \
     }
 
@@ -1337,7 +1338,7 @@ int launch_head_combine(const float* partial, long M, int K, const float* bh, in
 
 // Loss gradient at the logits of one pixel, shared by head_backward_kernel and the two head_bn_* backward passes (which both
 // recompute it: same function, same inputs, same bits). LK = HL_CE: the Keras sparse CE on clipped probabilities, *lv = the weighted
-// per-pixel loss. Every other kind (kernels.h HeadLoss; mpunet/evaluate/loss_functions.py) is a per-image loss whose value comes out
+// per-pixel loss; HL_CE_LOGITS: the same loss from logits, no clip (below). Every other kind (kernels.h HeadLoss; mpunet/evaluate/loss_functions.py) is a per-image loss whose value comes out
 // of launch_head_loss_coeffs:  g_k = w_b * (a_bk + [y = k] * (c_bk + f(q_y))) * pass_k,  a, c from hl.coef[b][k][2], pass_k the clip
 // mask of focal / exp-log (loss_functions.py:130-131,179-180: clip_by_value(p, 1e-7, 1 - 1e-7)), *lv = 0. logf / expf only where the
 // loss has a per-pixel term (x^e is head_pow, kernels.h, not the device library's powf). No FMA contraction in the new kinds: the
@@ -1368,6 +1369,29 @@ __device__ __forceinline__ void head_loss_grad(const HeadLoss& hl, const float* 
 #pragma unroll
         for (int k = 0; k < K; ++k) dzv[k] = p[k] * (g[k] - dot);
         if (lv) *lv = (-logf(qy) + logf(S)) * wt;
+    } else if constexpr (LK == HL_CE_LOGITS) {
+        // TF's sparse_softmax_cross_entropy_with_logits (Keras from_logits=True: no clip, no mask). `probs` holds the K logits z of
+        // the pixel (a head with softmax = 0 stores them there):  L = w (log sum_k e^(z_k - max z) - (z_y - max z)),
+        // dz_k = w (e^(z_k - max z) / sum - [k = y]). |z| near 100 stays finite: the exponents are <= 0. K = 1: L = 0, dz = 0.
+#pragma clang fp contract(off)
+        const float wt = sw[mm / ppi];
+        float mx = probs[mm * K];
+        p[0] = mx;
+#pragma unroll
+        for (int k = 1; k < K; ++k) { p[k] = probs[mm * K + k]; mx = fmaxf(mx, p[k]); }
+        float S = 0.f, So = 0.f, dy = 0.f;                       // So: the sum without the label's term; dy = z_y - max z
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const float d = p[k] - mx;
+            if (k == yy) dy = d;
+            g[k] = expf(d);
+            S += g[k];
+            So += k == yy ? 0.f : g[k];
+        }
+        const float inv = 1.f / S;                               // softmax_y - 1 = -So / S: no cancellation on a confident pixel
+#pragma unroll
+        for (int k = 0; k < K; ++k) dzv[k] = ((k == yy ? -So : g[k]) * inv) * wt;
+        if (lv) *lv = (logf(S) - dy) * wt;
     } else {
 #pragma clang fp contract(off)
         const long b = mm / ppi;
@@ -1460,7 +1484,7 @@ __global__ __launch_bounds__(256, (K <= 3 ? 4 : 2)) void head_backward_kernel(co
             head_loss_grad<LK, K>(hl, probs, y, sw, mm, ppi, dzv, &lv);
 #pragma unroll
             for (int k = 0; k < K; ++k) ab[k] += dzv[k];
-            if constexpr (LK == HL_CE) {                         // (the per-image losses: value and mean from launch_head_loss_coeffs)
+            if constexpr (head_loss_per_pixel(LK)) {             // (the per-image losses: value and mean from launch_head_loss_coeffs)
                 lsum += lv;
                 if (loss) loss[mm] = lv;
             }
@@ -1726,7 +1750,7 @@ __global__ __launch_bounds__(256, (K <= 4 ? 4 : 2)) void head_bn_backward_kernel
             head_loss_grad<LK, K>(hl, probs, y, sw, mm, ppi, dzv, &lv);
 #pragma unroll
             for (int k = 0; k < K; ++k) ab[k] += dzv[k];
-            if constexpr (LK == HL_CE) {
+            if constexpr (head_loss_per_pixel(LK)) {
                 lsum += lv;
                 if (loss) loss[mm] = lv;
             }

@@ -27,6 +27,25 @@ _CUSTOM_LOSSES = {
 }
 _CUSTOM_LOSSES["SparseExpLogDice"] = _CUSTOM_LOSSES["SparseExponentialLogarithmicLoss"]          # :270
 _GDL_WEIGHTS = {"square": _lib.MPU_GDL_SQUARE, "simple": _lib.MPU_GDL_SIMPLE, "uniform": _lib.MPU_GDL_UNIFORM}
+_CE = "SparseCategoricalCrossentropy"
+
+
+def resolve_ce_kwargs(loss_kwargs, out_activation):
+    """from_logits of tf.keras.losses.SparseCategoricalCrossentropy(reduction=NONE, **loss_kwargs) (mpunet/train/trainer.py:82) on a
+    model with the given out_activation. `name` is dropped, `reduction` and unknown keys raise TypeError as the constructor call
+    would; from_logits=True on a softmax output raises ValueError (the loss would apply a second softmax to probabilities)."""
+    kw = dict(loss_kwargs or {})
+    if "reduction" in kw:                # trainer.py:82 passes it itself
+        raise TypeError("%s() got multiple values for keyword argument 'reduction'" % _CE)
+    kw.pop("name", None)
+    from_logits = bool(kw.pop("from_logits", False))
+    for k in kw:
+        raise TypeError("%s() got an unexpected keyword argument %r" % (_CE, k))
+    if from_logits and out_activation != "linear":
+        raise ValueError("%s(from_logits=True) on out_activation=%r would apply the softmax twice: build the model with "
+                         "out_activation=\"linear\" (build.out_activation: linear), or drop from_logits"
+                         % (_CE, out_activation))
+    return from_logits
 
 # tf.keras.optimizers (TF 2.3), as mpunet/train/utils.py:100-111 resolves `fit.optimizer`: class name -> (mpu_optimizer_kind,
 # constructor keywords with their defaults). Adam's lr and epsilon are the project YAML's (train_hparams.yaml:125-126), which
@@ -236,6 +255,7 @@ class UNet:
         self._grad_hook = None         # e.g. an all-reduce over RCCL (multiplanarunet_amd.distributed)
         self.loss_name = "SparseCategoricalCrossentropy"
         self._per_image_loss = False   # compile() with a loss of mpunet/evaluate/loss_functions.py: one value per image
+        self.from_logits = False       # compile(loss_kwargs={"from_logits": True}) on a linear model: the cross-entropy reads logits
         self._init_weights(seed)
 
         # receptive field of the contracting path (unet.py:104-109, utils/conv_arithmetics.py:57)
@@ -551,6 +571,10 @@ class UNet:
         SparseJaccardDistanceLoss, SparseGeneralizedDiceLoss, SparseFocalLoss, SparseExponentialLogarithmicLoss
         (alias SparseExpLogDice) -- with `loss_kwargs` as their constructors take them (trainer.py:82). Those five give ONE
         loss value per image (reduction=NONE over the flattened output): forward_backward / train_step return [B, 1].
+        SparseCategoricalCrossentropy takes `loss_kwargs` too (resolve_ce_kwargs): {"from_logits": True} on a model built with
+        out_activation="linear" is TF's sparse_softmax_cross_entropy_with_logits -- logsumexp(z) - z_y per pixel, no probability
+        clip, gradient softmax(z) - onehot(y) -- and is what trains and evaluates such a model (`self.from_logits`); its output
+        stays the logits. The five per-image losses need out_activation="softmax".
 
         `optimizer`: Adam, SGD, RMSprop or Adamax by their tf.keras.optimizers names, `optimizer_kwargs` as their constructors
         take them (an unknown key: TypeError; anything else Keras has: NotImplementedError). A key that is omitted takes the
@@ -589,7 +613,10 @@ class UNet:
                 self._require_trainable("compile(loss=%r)" % lname)
                 self._set_loss(lname, dict(loss_kwargs or {}))
             elif "sparsecategoricalcrossentropy" in lname.lower().replace("_", ""):
-                self._set_loss(None, {})
+                from_logits = resolve_ce_kwargs(loss_kwargs, self.out_activation)
+                if from_logits:
+                    self._require_trainable("compile(loss=%r)" % lname)
+                self._set_loss(None, {}, from_logits=from_logits)
             else:
                 raise NotImplementedError("loss %r is not supported: SparseCategoricalCrossentropy or one of %s"
                                           % (lname, ", ".join(sorted(_CUSTOM_LOSSES))))
@@ -668,14 +695,15 @@ class UNet:
     def _slot_ptrs(self):
         return (C.c_void_p * 3)(*[s.data_ptr() for s in self._slots] + [None] * (3 - len(self._slots)))
 
-    def _set_loss(self, lname, kw):
+    def _set_loss(self, lname, kw, from_logits=False):
         """Validate `kw` against the constructor of loss_functions.<lname> and attach the loss to the library handle
-        (mpu_unet_set_loss). lname None: back to the sparse cross-entropy."""
+        (mpu_unet_set_loss). lname None: back to the sparse cross-entropy -- on probabilities (a softmax model; on a linear one what
+        this class has always done there: it predicts, it does not train), or with from_logits on the logits of a linear model."""
         cfg = _lib.LossConfig()
         if lname is None:
-            if not self._per_image_loss:   # nothing attached: the handle is as mpu_unet_create made it
-                return
-            cfg.kind = _lib.MPU_LOSS_SPARSE_CE
+            if not self._per_image_loss and not self.from_logits and not from_logits:
+                return                     # nothing attached: the handle is as mpu_unet_create made it
+            cfg.kind = _lib.MPU_LOSS_SPARSE_CE_LOGITS if from_logits else _lib.MPU_LOSS_SPARSE_CE
         else:
             kind, defaults, var_kw = _CUSTOM_LOSSES[lname]
             if self.out_activation != "softmax":
@@ -712,6 +740,7 @@ class UNet:
         self._loss_cfg = cfg
         self.loss_name = lname or "SparseCategoricalCrossentropy"
         self._per_image_loss = lname is not None
+        self.from_logits = bool(from_logits) and lname is None
         self._ws = None                    # the workspace plan of a handle with a per-image loss is larger
         self._ws_batch = 0
 
@@ -1000,8 +1029,12 @@ class UNet:
             if self._eval_ws is None or self._eval_ws.numel() < need:
                 self._eval_ws = torch.empty(need, dtype=torch.uint8, device=p.device)
             self._eval_ws_shape = (B, ppi)
-        _lib.call("mpu_eval_loss", C.byref(self._loss_cfg), _lib.ptr(p), _lib.ptr(y), _lib.ptr(sw), B, ppi, K,
-                  _lib.ptr(self._eval_ws), _lib.ptr(loss_out), _lib.ptr(acc), _lib.stream_ptr())
+        if self.from_logits:               # `probs` holds the linear model's logits
+            _lib.call("mpu_eval_loss_logits", _lib.ptr(p), _lib.ptr(y), _lib.ptr(sw), B, ppi, K,
+                      _lib.ptr(self._eval_ws), _lib.ptr(loss_out), _lib.ptr(acc), _lib.stream_ptr())
+        else:
+            _lib.call("mpu_eval_loss", C.byref(self._loss_cfg), _lib.ptr(p), _lib.ptr(y), _lib.ptr(sw), B, ppi, K,
+                      _lib.ptr(self._eval_ws), _lib.ptr(loss_out), _lib.ptr(acc), _lib.stream_ptr())
         if metrics_state is not None and self._metric_names:
             _lib.call("mpu_train_metrics_update", _lib.ptr(p), _lib.ptr(y), B * ppi, K, _lib.ptr(metrics_state),
                       _lib.stream_ptr())
