@@ -145,6 +145,25 @@ int mpu_volume_order_stats(const float* d_vol, int64_t n_vox, int32_t n_channels
 int mpu_volume_moments(const float* d_vol, int64_t n_vox, int32_t n_channels, const double* mean,
                        void* d_workspace, int64_t workspace_bytes, double* out, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * NIfTI-1 payload -> resident volume (csrc/volume_decode.hip): the order and type conversion nifti.read_nifti does with NumPy
+ * on the host. d_payload: the file's bytes behind vox_offset as they lie there (Fortran order: x fastest, then y, z and the
+ * fourth dimension), aligned to the element width. datatype: the NIfTI code (2 u8, 4 i16, 8 i32, 16 f32, 64 f64, 256 i8,
+ * 512 u16, 768 u32, 1024 i64, 1280 u64; others MPU_EUNSUPPORTED). byteswap != 0: the file has the other endianness.
+ * shape = (X, Y, Z, C), every entry in [1, 32767]; a 3-D file gives C = 1. scaled != 0 applies `f64(stored) * slope + inter`
+ * (two rounded f64 operations); WHETHER a file's scl_slope / scl_inter ask for it is the caller's decision (nifti.py).
+ *   MPU_DECODE_IMAGE   d_out f32 [X,Y,Z,C] (C order). Not scaled: stored type -> f32 in one conversion (i64 / u64 not through
+ *                      f64; f32 bit for bit). Scaled: the f64 result rounded to f32, nearest even.
+ *   MPU_DECODE_LABELS  d_out u8 [X,Y,Z,C]: the f64 value (scaled or not) truncated toward zero. *d_bad_count (device u64, zeroed
+ *                      by the call) counts the voxels that are non-finite or whose truncation leaves [0, 256): NumPy's
+ *                      astype(uint8) is platform-defined there; they are written as 0.
+ * Asynchronous on `stream`; 64-bit indices throughout.
+ * ------------------------------------------------------------------------ */
+typedef enum { MPU_DECODE_IMAGE = 0, MPU_DECODE_LABELS = 1 } mpu_decode_kind;
+int mpu_volume_decode(const void* d_payload, int32_t datatype, int32_t byteswap, const int64_t shape[4],
+                      int32_t scaled, double slope, double inter, int32_t kind, void* d_out,
+                      uint64_t* d_bad_count, void* stream);
+
 /* One view's prediction volume as seen by the back-mapping
  * (mpunet/utils/fusion/fuse_and_predict.py:92-137). */
 typedef struct {

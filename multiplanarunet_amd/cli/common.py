@@ -3,8 +3,7 @@ import os
 import numpy as np
 import yaml
 
-from ..data import (list_volume_files, load_volume_file, load_label_file, as_volume, make_toy_volume, random_views,
-                    audit_dim_and_span)
+from ..data import (list_volume_files, load_label_file, as_volume, make_toy_volume, random_views, audit_dim_and_span)
 from ..nifti import volume_identifier
 
 DEFAULT_HPARAMS = {
@@ -67,23 +66,107 @@ def load_dataset(cfg, project_dir, hp, device, synthetic=0, seed=0, need_labels=
             img, lab, aff = make_toy_volume(64, seed + i)
             vols.append(as_volume(img, lab, aff, fit.get("bg_value"), fit.get("scaler"), device, "toy_%d" % (seed + i)))
         return vols
+    for path, lp in list_dataset_entries(cfg, project_dir):
+        vols.append(load_entry(path, lp, hp, device, need_labels))
+    return vols
+
+
+def list_dataset_entries(cfg, project_dir):
+    """[(image path, label path or None), ...] of one of train_data / val_data / test_data: the files only, nothing is read."""
     base = cfg.get("base_dir")
     if not base:
-        return vols
+        return []
     if not os.path.isabs(base):
         base = os.path.join(project_dir, base)
+    out = []
     for path in list_volume_files(base, cfg.get("img_subdir", "images")):
-        img, lab, aff = load_volume_file(path)
-        if lab is None:
-            lp = os.path.join(base, cfg.get("label_subdir", "labels"), os.path.basename(path))
-            if os.path.exists(lp):
-                lab = load_label_file(lp)
-        if lab is None and need_labels:
-            raise ValueError("no labels for %s" % path)
-        ident = volume_identifier(path)
-        vols.append(as_volume(img, lab, aff, fit.get("bg_value"), fit.get("scaler"), device, ident))
-        vols[-1].source_path = path                    # (`mp predict` writes <id>_PRED.nii.gz for NIfTI inputs)
-    return vols
+        lp = os.path.join(base, cfg.get("label_subdir", "labels"), os.path.basename(path))
+        out.append((path, lp if os.path.exists(lp) else None))
+    return out
+
+
+def check_has_labels(payload, need_labels):
+    if payload.labels is None and need_labels:
+        raise ValueError("no labels for %s" % payload.path)
+    return payload
+
+
+def load_entry(path, label_path, hp, device, need_labels=True):
+    """One resident Volume of a dataset entry (data.load_volume_to_device: NIfTI files are decoded on the device)."""
+    import torch
+    from ..data import read_volume_host, adopt_payload
+    fit = hp["fit"]
+    payload = check_has_labels(read_volume_host(path, label_path, raw_nifti=torch.device(device).type == "cuda"), need_labels)
+    return adopt_payload(payload, device, fit.get("bg_value"), fit.get("scaler"), volume_identifier(path))
+
+
+def dataset_entries(cfg, project_dir, hp, device, synthetic=0, seed=0, need_labels=True):
+    """The set load_dataset would load, as volume_queue.VolumeEntry objects: nothing is read yet. An entry's loader does file
+    work only (a loader thread may run it); its adopter makes the resident Volume on the calling thread's stream."""
+    import torch
+    from ..volume_queue import VolumeEntry
+    from ..data import read_volume_host, adopt_payload, HostPayload
+    fit = hp["fit"]
+    raw = torch.device(device).type == "cuda"
+
+    def adopt(e, payload):
+        return adopt_payload(payload, device, fit.get("bg_value"), fit.get("scaler"), e.identifier)
+
+    if synthetic:
+        def toy(i):
+            def load(e):
+                img, lab, aff = make_toy_volume(64, seed + i)
+                return HostPayload(None, None, ("host", img), ("host", lab), aff)
+            return load
+        return [VolumeEntry(None, None, "toy_%d" % (seed + i), toy(i), adopt) for i in range(synthetic)]
+
+    def load(e):
+        return check_has_labels(read_volume_host(e.path, e.label_path, raw_nifti=raw), need_labels)
+    return [VolumeEntry(p, lp, volume_identifier(p), load, adopt) for p, lp in list_dataset_entries(cfg, project_dir)]
+
+
+def fill_build_from_entries(hp, entries, max_label_files=50):
+    """fill_build_from_data without resident volumes: shape, affine and channel count come from the NIfTI HEADERS; an entry
+    without one (.npz, a generated volume, a NIfTI file of a rank the header audit does not take) is loaded on the host, looked
+    at and dropped, one at a time. build.n_classes, when the YAML leaves it open, is audited from at most 50 label files read
+    one at a time (auditor._audit_classes; here the largest label + 1, the rule of fill_build_from_data)."""
+    from types import SimpleNamespace
+    from ..nifti import read_nifti_header
+
+    def host_payload(e):
+        e.load_host()
+        p, e.payload = e.payload, None
+        return p
+
+    infos = []
+    for e in entries:
+        shape = aff = None
+        if e.path and str(e.path).endswith((".nii", ".nii.gz")):
+            h, aff = read_nifti_header(e.path)
+            shape = tuple(h["shape"]) if len(h["shape"]) in (3, 4) else None
+        if shape is None:
+            p = host_payload(e)
+            shape, aff = tuple(p.image[1].shape), p.affine
+        shape4 = tuple(int(s) for s in shape) + (1,) * (4 - len(shape))
+        infos.append(SimpleNamespace(affine=np.asarray(aff, np.float64), image=np.broadcast_to(np.float32(0), shape4),
+                                     n_channels=shape4[3], labels=None))
+    n_classes = None
+    if not hp["build"].get("n_classes"):
+        labelled = [e for e in entries if e.label_path or not e.path or str(e.path).endswith(".npz")]
+        pick = np.random.RandomState(0).choice(len(labelled), min(int(max_label_files), len(labelled)), replace=False) \
+            if labelled else []
+        top = []
+        for i in sorted(int(k) for k in pick):
+            e = labelled[i]
+            if e.label_path:
+                lab = load_label_file(e.label_path)
+            else:
+                p = host_payload(e)
+                lab = None if p.labels is None else p.labels[1]
+            if lab is not None:
+                top.append(int(np.asarray(lab).max()))
+        n_classes = max(top) + 1 if top else None
+    return fill_build_from_data(hp, infos, n_classes=n_classes)
 
 
 def load_or_create_views(project_dir, n_views, seed=None):
@@ -262,7 +345,19 @@ def set_bias_weights_on_all_outputs(model, volumes, hparams, logger=None):
     if layer is None:
         raise ValueError("model has no output layer with an activation")
     counts = hparams.get("class_counts")
-    if counts is None:
+    if counts is None and hasattr(volumes, "max_loaded"):
+        # a limitation queue: one count per image currently in the queue (utils.py:222-231) -- max_loaded draws from its FIFO,
+        # which visit every preloaded volume once; the preload is the same on every rank (the queue's shared seed)
+        (logger or print)("OBS: Estimating class counts from %d images" % volumes.max_loaded)
+        counts = np.zeros(int(model.n_classes), dtype=np.int64)
+        for _ in range(volumes.max_loaded):
+            with volumes.get_random_image() as vol:
+                c = class_counts_from_volumes([vol], model.n_classes)
+            if c.size > counts.size:
+                counts = np.concatenate([counts, np.zeros(c.size - counts.size, np.int64)])
+            counts[:c.size] += c
+    elif counts is None:
+        volumes = getattr(volumes, "volumes", volumes)          # (an eager queue: its list)
         (logger or print)("OBS: Estimating class counts from %d images" % len(volumes))
         counts = class_counts_from_volumes(volumes, model.n_classes)
     return set_bias_weights(layer, counts, logger)

@@ -9,7 +9,7 @@ from argparse import ArgumentParser
 import numpy as np
 import torch
 
-from .common import (validate_project_dir, load_hparams, load_dataset, require_audited_hparams,
+from .common import (validate_project_dir, load_hparams, load_dataset, dataset_entries, require_audited_hparams,
                      fusion_weights_path, note_inert_flags)
 
 
@@ -56,7 +56,7 @@ def run(args):
     from ..fusion_model import FusionModel
     from ..predict import multi_view_predict
     from ..interpolation import dice_all
-    from ..data import load_volume_file, load_label_file, as_volume
+    from ..data import load_volume_to_device
     from ..nifti import volume_identifier
     from ..formats import save_nifti
     project_dir = os.path.abspath(args.project_dir)
@@ -70,15 +70,17 @@ def run(args):
     log = (lambda *a, **k: print(*a, flush=True)) if rank == 0 else (lambda *a, **k: None)
     hp = load_hparams(project_dir)
     fit, build = hp["fit"], hp["build"]
+    lazy = False
     if args.f:
-        img, lab, aff = load_volume_file(args.f)
-        if args.l:
-            lab = load_label_file(args.l)
-        vols = [as_volume(img, lab, aff, fit.get("bg_value"), fit.get("scaler"), device, volume_identifier(args.f))]
-        vols[0].source_path = args.f
+        vols = [load_volume_to_device(args.f, args.l, device, fit.get("bg_value"), fit.get("scaler"),
+                                      volume_identifier(args.f), label_wins=True)]
     else:
         key = "val_data" if args.on_val else args.dataset.replace("_data", "") + "_data"
-        vols = load_dataset(hp[key], project_dir, hp, device, args.synthetic, seed=5000, need_labels=False)
+        if args.synthetic:
+            vols = load_dataset(hp[key], project_dir, hp, device, args.synthetic, seed=5000, need_labels=False)
+        else:                                             # files: nothing is read yet (bin/predict.py:394, a lazy queue)
+            vols = dataset_entries(hp[key], project_dir, hp, device, need_labels=False)
+            lazy = True
     if not vols:
         raise OSError("no volumes to predict on")
     require_audited_hparams(hp, "mp predict")             # geometry of the training session, never re-audited here
@@ -104,17 +106,32 @@ def run(args):
     if rank == 0:
         os.makedirs(nii, exist_ok=True)
     results, per_view = {}, {}
-    for v in vols:
-        src = str(getattr(v, "source_path", "") or "")
+
+    def plan(item):
+        """(write a NIfTI file?, output folder, output file) of a volume or a dataset entry."""
+        src = str(getattr(item, "source_path", None) or getattr(item, "path", None) or "")
         as_nii = args.out_format == "nii" or (args.out_format == "auto" and src.endswith((".nii", ".nii.gz")))
         # bin/predict.py:90-117: with --save_input_files the prediction goes into a sub-folder <identifier>/ of nii_files,
         # next to <identifier>_IMAGE and <identifier>_LABELS
-        out_base = os.path.join(nii, v.identifier) if args.save_input_files else nii
-        dst = os.path.join(out_base, "%s_PRED.%s" % (v.identifier, "nii.gz" if as_nii else "npz"))
+        out_base = os.path.join(nii, item.identifier) if args.save_input_files else nii
+        return as_nii, out_base, os.path.join(out_base, "%s_PRED.%s" % (item.identifier, "nii.gz" if as_nii else "npz"))
+
+    # what there is to do is settled from the names alone, so that a volume whose output exists is never read; an output that
+    # exists without --overwrite / --continue stops the run where the loop reaches it, as before
+    todo, conflict = [], None
+    for item in vols:
+        dst = plan(item)[2]
         if os.path.exists(dst) and args.continue_:
             continue
         if os.path.exists(dst) and not args.overwrite:
-            raise OSError("%s exists (use --overwrite or --continue)" % dst)
+            conflict = dst
+            break
+        todo.append(item)
+    if lazy:                                              # at most the current and the next volume are loaded
+        from ..volume_queue import LazyQueue, Dataset
+        todo = LazyQueue(Dataset(todo, key), logger=log)
+    for v in todo:
+        as_nii, out_base, dst = plan(v)
         if world > 1:
             res = D.multi_view_predict_sharded(model, v, views, build["dim"], fit["real_space_span"], fm,
                                                sum_fusion=args.sum_fusion, batch_size=None, want_probs=args.no_argmax,
@@ -156,6 +173,8 @@ def run(args):
                 d = dice_all(v.labels, labels, n_classes=build["n_classes"], ignore_zero=True)
                 results[v.identifier] = d
                 log("%s: dices %s mean %.4f" % (v.identifier, np.round(d, 4), float(np.nanmean(d))))
+    if conflict is not None:
+        raise OSError("%s exists (use --overwrite or --continue)" % conflict)
     if rank == 0 and results:
         os.makedirs(os.path.join(out_dir, "csv"), exist_ok=True)
         with open(os.path.join(out_dir, "csv", "results.csv"), "w") as f:

@@ -9,8 +9,8 @@ from argparse import ArgumentParser
 import numpy as np
 import torch
 
-from .common import (validate_project_dir, load_hparams, load_dataset, load_or_create_views,
-                     fill_build_from_data, save_audited_hparams, set_bias_weights_on_all_outputs,
+from .common import (validate_project_dir, load_hparams, load_dataset, load_or_create_views, dataset_entries,
+                     fill_build_from_data, fill_build_from_entries, save_audited_hparams, set_bias_weights_on_all_outputs,
                      init_callback_objects, remove_validation_callbacks, DEFAULT_CALLBACKS, note_inert_flags,
                      validate_output_loss)
 
@@ -114,19 +114,36 @@ def run(args):
     if hp["build"].get("n_classes"):                       # (an audited YAML; one that leaves it to the data is checked below)
         require_trainable(hp["build"]["n_classes"], "mp train")
     validate_output_loss(hp)                               # a linear output needs fit.loss_kwargs.from_logits, a softmax one refuses it
-    note_inert_flags(args, [("no_images", "no sample images are written during training"), ("debug", "the TF debugger has no counterpart"),
-                            ("max_loaded_images", "volumes stay resident in HBM: there is no image queue"),
-                            ("num_access", "volumes stay resident in HBM: there is no image queue")], log)
-    train = load_dataset(hp["train_data"], project_dir, hp, device, args.synthetic, seed=0)
-    val = [] if args.no_val else load_dataset(hp["val_data"], project_dir, hp, device,
-                                              max(1, args.synthetic // 4) if args.synthetic else 0, seed=1000)
-    if not train:
-        raise OSError("no training volumes (set train_data.base_dir to a folder with images/*.npz, or --synthetic N)")
-    fill_build_from_data(hp, train)                        # audit the FULL training set (before --just_one)
-    require_trainable(hp["build"]["n_classes"], "mp train")    # 9..16 classes predict and fuse, they do not train: every rank, up front
-    train_all = list(train)
-    if args.just_one:
-        train, val = train[:1], val[:1]
+    note_inert_flags(args, [("no_images", "no sample images are written during training"), ("debug", "the TF debugger has no counterpart")], log)
+    no_data = "no training volumes (set train_data.base_dir to a folder with images/*.npz, or --synthetic N)"
+    n_val_syn = max(1, args.synthetic // 4) if args.synthetic else 0
+    if args.max_loaded_images is None:                     # every volume resident before the first step, as without queues
+        train = load_dataset(hp["train_data"], project_dir, hp, device, args.synthetic, seed=0)
+        val = [] if args.no_val else load_dataset(hp["val_data"], project_dir, hp, device, n_val_syn, seed=1000)
+        if not train:
+            raise OSError(no_data)
+        fill_build_from_data(hp, train)                    # audit the FULL training set (before --just_one)
+        require_trainable(hp["build"]["n_classes"], "mp train")    # 9..16 classes predict and fuse, they do not train: every rank, up front
+        train_all = list(train)
+        if args.just_one:
+            train, val = train[:1], val[:1]
+    else:
+        # --max_loaded_images / --num_access (bin/train.py:232-247): at most that many volumes of each set are loaded at a time
+        # (volume_queue.LimitationQueue). The audit reads headers, not volumes; a value that covers a whole set gives the eager
+        # queue for it, with the reference's warning.
+        from ..volume_queue import get_data_queues
+        tr_e = dataset_entries(hp["train_data"], project_dir, hp, device, args.synthetic, seed=0)
+        va_e = [] if args.no_val else dataset_entries(hp["val_data"], project_dir, hp, device, n_val_syn, seed=1000)
+        if not tr_e:
+            raise OSError(no_data)
+        fill_build_from_entries(hp, tr_e)                  # audit the FULL training set (before --just_one)
+        require_trainable(hp["build"]["n_classes"], "mp train")
+        if args.just_one:
+            tr_e, va_e = tr_e[:1], va_e[:1]
+        # initial order: a seed all ranks share (the replicas count the same volumes for the output bias); replacements: per rank
+        train, val = get_data_queues(tr_e, va_e, "limitation", "limitation" if va_e else None, args.max_loaded_images,
+                                     args.num_access, log, seed=0, rank_seed=1000 + rank)
+        train_all = train
     fit, build = hp["fit"], hp["build"]
     if world > 1:
         torch.distributed.barrier()                        # every rank has passed the checks and read the YAML
@@ -172,7 +189,7 @@ def run(args):
     mk = lambda vols, noise, seed, augs: TrainSampler(vols, views, build["dim"], fit["real_space_span"], per_rank,
                                                       build["n_classes"], noise_sd=noise,
                                                       fg_batch_fraction=fit["fg_batch_fraction"], seed=seed,
-                                                      augmenters=augs)
+                                                      augmenters=augs, n_channels=build["n_channels"], device=device)
     augs = build_augmenters(fit.get("augmenters"), seed=1000 + rank)     # YAML fit.augmenters (Elastic2D)
     if augs:
         log("Augmenters:", ", ".join(str(a) for a in augs))
@@ -223,6 +240,9 @@ def run(args):
     except KeyboardInterrupt:
         log("Interrupted: saving weights")
     finally:
+        pool = getattr(train, "loading_pool", None) or getattr(val, "loading_pool", None)
+        if pool is not None:                               # the limitation queues' loader threads
+            pool.close()
         if rank == 0:
             model.save_weights(last)
             log("Saved", last)

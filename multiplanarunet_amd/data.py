@@ -42,6 +42,110 @@ def load_label_file(path):
         return z["labels"] if "labels" in z.files else z[z.files[0]]
 
 
+def _is_nifti(path):
+    return str(path).endswith((".nii", ".nii.gz"))
+
+
+class HostPayload:
+    """One volume as a loader thread leaves it: FILE WORK ONLY (read, gunzip, header parse), pageable host memory, no call into
+    HIP or torch's device API (volume_queue.py: the threading rule). `image` is ("raw", header, payload bytes) for a NIfTI file
+    of rank 3 or 4 -- decoded on the device by adopt_payload -- or ("host", f32 [X,Y,Z,C]) for everything that keeps the host
+    path (.npz, other ranks); `labels` is None or one of the same two forms."""
+    __slots__ = ("path", "label_path", "image", "labels", "affine")
+
+    def __init__(self, path, label_path, image, labels, affine):
+        self.path, self.label_path, self.image, self.labels, self.affine = path, label_path, image, labels, affine
+
+
+def read_volume_host(path, label_path=None, raw_nifti=True, label_wins=False):
+    """HostPayload of an image file and, unless the image file carries labels itself (.npz; label_wins: even then), of `label_path`.
+    raw_nifti=False decodes NIfTI files on the host too (formats.load_nifti / load_nifti_labels: today's path)."""
+    from .nifti import read_nifti_payload
+    image = labels = affine = None
+    if raw_nifti and _is_nifti(path):
+        h, affine, buf = read_nifti_payload(path)
+        if len(h["shape"]) in (3, 4):
+            image = ("raw", h, buf)
+    if image is None:                                         # .npz, a NIfTI file of another rank (today's errors), the host path
+        img, lab, affine = load_volume_file(path)
+        image = ("host", img)
+        labels = None if lab is None else ("host", lab)
+    if label_path and (labels is None or label_wins):
+        labels = read_labels_host(label_path, raw_nifti)
+    return HostPayload(path, label_path, image, labels, affine)
+
+
+def read_labels_host(label_path, raw_nifti=True):
+    """The `labels` member of a HostPayload for a label file."""
+    from .nifti import read_nifti_payload
+    if raw_nifti and _is_nifti(label_path):
+        h, _, buf = read_nifti_payload(label_path)
+        s = h["shape"]
+        if len(s) == 3 or (len(s) == 4 and s[3] == 1):        # (load_nifti_labels drops a trailing singleton axis)
+            return ("raw", h, buf)
+    return ("host", load_label_file(label_path))
+
+
+def decode_nifti_payload(header, payload, device, labels=False, path=""):
+    """One host-to-device copy of the payload bytes and mpu_volume_decode (csrc/volume_decode.hip) on the current stream:
+    f32 [X,Y,Z,C] with the bits of formats.load_nifti, or (labels=True) u8 [X,Y,Z] with the bits of formats.load_nifti_labels.
+    A label value NumPy's astype(uint8) is platform-defined for (non-finite, or outside [0, 256) after truncation) is a
+    ValueError naming the file."""
+    import ctypes as C
+    import sys
+    from . import _lib
+    from .nifti import scaling_of
+    shape = tuple(int(s) for s in header["shape"])
+    if len(shape) not in (3, 4) or (labels and len(shape) == 4 and shape[3] != 1):
+        raise ValueError("%s: the device decode takes NIfTI data of rank 3 or 4 (labels: one channel), got shape %r" % (path, shape))
+    shape4 = shape + (1,) * (4 - len(shape))
+    swap = (header["endian"] == ">") == (sys.byteorder == "little")
+    scaled, slope, inter = scaling_of(header)
+    dev = torch.device(device)
+    raw = torch.frombuffer(payload, dtype=torch.uint8).to(dev)
+    if labels:
+        out = torch.empty(shape4[:3], dtype=torch.uint8, device=dev)
+        bad = torch.empty(1, dtype=torch.int64, device=dev)
+    else:
+        out = torch.empty(shape4, dtype=torch.float32, device=dev)
+        bad = None
+    _lib.call("mpu_volume_decode", _lib.ptr(raw), int(header["datatype"]), int(swap), (C.c_int64 * 4)(*shape4), int(scaled),
+              float(slope), float(inter), _lib.MPU_DECODE_LABELS if labels else _lib.MPU_DECODE_IMAGE, _lib.ptr(out),
+              _lib.ptr(bad), _lib.stream_ptr())
+    if labels:
+        n_bad = int(bad.item())
+        if n_bad:
+            raise ValueError("%s: %d label voxels are non-finite or outside [0, 256) after truncation: they cannot be stored "
+                             "as uint8 class indices" % (path, n_bad))
+    return out
+
+
+def adopt_payload(payload, device, bg_value="1pct", scaler="RobustScaler", identifier=None, fit_on="device"):
+    """HostPayload -> Volume, on the CALLING thread's current stream: upload, decode, then as_volume's background value and
+    scaler fit on the resident tensor."""
+    kind = payload.image[0]
+    img = decode_nifti_payload(payload.image[1], payload.image[2], device, False, payload.path) if kind == "raw" \
+        else payload.image[1]
+    lab = payload.labels
+    if lab is not None:
+        lab = decode_nifti_payload(lab[1], lab[2], device, True, payload.label_path) if lab[0] == "raw" else lab[1]
+    if identifier is None:
+        from .nifti import volume_identifier
+        identifier = volume_identifier(payload.path)
+    vol = as_volume(img, lab, payload.affine, bg_value, scaler, device, identifier, fit_on=fit_on)
+    vol.source_path = payload.path                    # (`mp predict` writes <id>_PRED.nii.gz for NIfTI inputs)
+    return vol
+
+
+def load_volume_to_device(path, label_path=None, device="cuda", bg_value="1pct", scaler="RobustScaler", identifier=None,
+                          fit_on="device", label_wins=False):
+    """File(s) -> resident Volume. A NIfTI file of rank 3 or 4 goes up as it lies in the file and is put into C order and f32
+    (labels: u8) by mpu_volume_decode -- the same bits as the host conversion, without its two NumPy passes. .npz files, NIfTI
+    files of another rank, a CPU `device` and fit_on="host" keep the host path and its errors."""
+    on_device = torch.device(device).type == "cuda" and fit_on == "device"
+    return adopt_payload(read_volume_host(path, label_path, on_device, label_wins), device, bg_value, scaler, identifier, fit_on)
+
+
 def list_volume_files(base_dir, img_subdir="images"):
     d = os.path.join(base_dir, img_subdir)
     if not os.path.isdir(d):
@@ -99,6 +203,17 @@ def as_volume(image, labels, affine, bg_value="1pct", scaler="RobustScaler", dev
     bg_dev, sc = scalers.prepare_device(img_dev, pct, scaler or None)
     return Volume(img_dev, labels, affine, bg_value=bg if pct is None else bg_dev, scaler=sc, device=device,
                   identifier=identifier)
+
+
+def _volume_tensors(vol):
+    """Every device tensor a sampling call of `vol` reads."""
+    ts = [vol.image, vol._bg] + list(vol._axes_dev)
+    if vol.labels is not None:
+        ts.append(vol.labels)
+    if vol._scaler is not None:
+        for _, held in vol._scaler._dev.values():
+            ts += [t for t in held.values() if t is not None]
+    return ts
 
 
 def random_views(n, min_angle_deg=60.0, seed=None):
@@ -204,8 +319,18 @@ class TrainSampler:
 
     def __init__(self, volumes, views, dim, real_space_span, batch_size, n_classes, noise_sd=0.1,
                  fg_batch_fraction=0.5, force_all_fg="auto", sample_weights=None, seed=None, max_tries=10,
-                 augmenters=None):
-        self.volumes = list(volumes)
+                 augmenters=None, n_channels=None, device=None):
+        # `volumes`: a list of resident Volumes, a volume_queue.EagerQueue (its list), or a volume_queue.LimitationQueue: then
+        # every slot of a batch takes its volume from the queue's FIFO (n_channels and device cannot be read off a volume that
+        # is not loaded yet: pass them)
+        self.queue = volumes if hasattr(volumes, "loaded_queue") else None
+        self.volumes = [] if self.queue is not None else list(getattr(volumes, "volumes", volumes))
+        if self.queue is not None and (n_channels is None or device is None):
+            raise ValueError("TrainSampler over a limitation queue needs n_channels and device")
+        if self.queue is None and self.volumes:
+            n_channels, device = self.volumes[0].n_channels, self.volumes[0].device
+        self.n_channels = None if n_channels is None else int(n_channels)
+        self.device = None if device is None else torch.device(device)
         self.views = np.asarray(views, float)
         self.dim, self.span = int(dim), real_space_span
         self.batch_size, self.n_classes = int(batch_size), int(n_classes)
@@ -223,11 +348,44 @@ class TrainSampler:
             self._fg_mask |= 1 << int(c)
         self._views_l = [tuple(float(a) for a in v) for v in self.views]
 
-    def _vc(self, vi):
-        c = self._cache.get(vi)
+    def _vc(self, vol):
+        """The volume's _VolCache; keyed by the VOLUME (a list index names different volumes over time under a queue)."""
+        if isinstance(vol, (int, np.integer)):
+            vol = self.volumes[vol]
+        c = self._cache.get(vol)
         if c is None:
-            c = self._cache[vi] = _VolCache(self.volumes[vi], self.dim, self.span)
+            c = self._cache[vol] = _VolCache(vol, self.dim, self.span)
         return c
+
+    def _take_from_queue(self, B):
+        """The batch's volumes from the limitation queue's FIFO, one get / release per slot as get_random_image does it
+        (isotrophic_live_view_sequence_2d.py:150-160), BEFORE the first cut: an arrival is adopted here -- upload, decode,
+        scaler fit on this thread's current stream (volume_queue.py: the threading rule). An entry that reaches its access
+        limit is only marked; __call__ retires it (unload, replacement load) once the batch's cuts are issued, because a
+        rejected candidate is cut again from the same volume. Should every loaded entry expire inside one batch (max_loaded far
+        below the batch size), the remaining slots reuse the expired ones in turn rather than wait for loads that are not
+        requested before the batch is done."""
+        q, cur = self.queue, torch.cuda.current_stream()
+        vols, retiring = [], []
+        for slot in range(B):
+            if retiring and q.loaded_queue.empty() and q.n_loading == 0:
+                vols.append(retiring[slot % len(retiring)].volume)
+                continue
+            entry, n = q.get()
+            fresh = entry.volume is None
+            vol = entry.adopt()
+            if fresh:
+                vol._alloc_stream, vol._marked_streams = cur, set()
+            elif getattr(vol, "_alloc_stream", None) != cur:                       # (adopted elsewhere, e.g. by the bias count)
+                marked = vol.__dict__.setdefault("_marked_streams", set())
+                if cur not in marked:
+                    for t in _volume_tensors(vol) + [self._vc(vol).bg_scaled]:  # read here, allocated on another stream
+                        t.record_stream(cur)
+                    marked.add(cur)
+            if q.release(entry, n, defer_unload=True):
+                retiring.append(entry)
+            vols.append(vol)
+        return vols, retiring
 
     def _issue_cut(self, vi, X, Y, slot, off_dev, stats):
         """Enqueue one candidate plane of volume vi into X[slot], Y[slot] and its statistics into stats[slot] (class mask,
@@ -270,9 +428,9 @@ class TrainSampler:
         deciding a slot on a candidate drawn before the earlier slots were settled changes nothing statistically. With no
         rejection the random stream is consumed in the same order as the one-candidate-at-a-time form."""
         B, d = self.batch_size, self.dim
-        vol0 = self.volumes[0]
-        dev = vol0.device
-        X = torch.empty((B, d, d, vol0.n_channels), dtype=torch.float32, device=dev)
+        dev = self.device
+        qvols, retiring = self._take_from_queue(B) if self.queue is not None else (None, ())
+        X = torch.empty((B, d, d, self.n_channels), dtype=torch.float32, device=dev)
         Y = torch.empty((B, d, d), dtype=torch.uint8, device=dev)
         off_dev = torch.empty(B, dtype=torch.float64, device=dev)
         stats = torch.empty((B, 2), dtype=torch.int32, device=dev)
@@ -302,8 +460,8 @@ class TrainSampler:
             todo = []
             for slot in range(first, B):
                 if not fresh[slot]:
-                    if vis[slot] is None:
-                        vis[slot] = self.rng.randint(0, len(self.volumes))
+                    if vis[slot] is None:                     # (a list or an eager queue: the random stream as without queues)
+                        vis[slot] = qvols[slot] if qvols is not None else self.volumes[self.rng.randint(0, len(self.volumes))]
                     tries[slot] += 1
                     view = self._views_l[self.rng.randint(0, nviews)]
                     off = self.rng.uniform(-half, half)
@@ -312,8 +470,8 @@ class TrainSampler:
                     todo.append((slot, vis[slot], plane_basis_fast(view, noise)))
                     fresh[slot] = True
             off_dev.copy_(off_host, non_blocking=True)
-            for slot, vi, basis in todo:
-                vol, vc = self.volumes[vi], self._vc(vi)
+            for slot, vol, basis in todo:
+                vc = self._vc(vol)
                 g = vc.geom
                 g.basis[:] = basis
                 p = vc.ptrs
@@ -347,8 +505,16 @@ class TrainSampler:
                     first += 1
                 else:
                     break
-        ws = [self.sample_weights[vi] for vi in vis]
-        bgs = [list(self.volumes[vi].bg_value) for vi in vis]
+        if qvols is None:
+            index_of = {v: i for i, v in enumerate(self.volumes)}
+            ws = [self.sample_weights[index_of[v]] for v in vis]
+        else:
+            ws = [1.0] * B
+        bgs = [list(v.bg_value) for v in vis]
+        for entry in retiring:                                # the cuts are issued (and judged): unload, request the replacement
+            self._cache.pop(entry.volume, None)
+            self.queue.retire(entry)
+        self.last_identifiers = [v.identifier for v in vis]   # (diagnostic: which volumes this batch was cut from)
         x, y = X, Y
         w = torch.tensor(ws, dtype=torch.float32, device=dev)
         for aug in self.augmenters:

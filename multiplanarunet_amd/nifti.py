@@ -169,6 +169,45 @@ def read_nifti(path, dtype=np.float32, scaled=True):
     return data, best_affine(h), h
 
 
+def read_nifti_header(path):
+    """(header, affine) from the first 348 bytes: shape, datatype and geometry of a volume without reading its data."""
+    with _open(path, "rb") as f:
+        h = _parse_header(f.read(348))
+    return h, best_affine(h)
+
+
+def read_nifti_payload(path):
+    """(header, affine 4x4 f64, payload bytes): what read_nifti reads, with its validation and its errors, and NO NumPy work on
+    the payload -- the bytes behind vox_offset as they lie in the file (Fortran order, the file's endianness), for
+    data.load_volume_to_device, which hands them to mpu_volume_decode."""
+    with _open(path, "rb") as f:
+        raw = f.read(348)
+        h = _parse_header(raw)
+        off = int(h["vox_offset"])
+        if off < 352:
+            off = 352
+        f.read(off - 348)                                         # extension flag + extensions
+        nbytes = int(np.prod(h["shape"], dtype=np.int64)) * np.dtype(_DTYPES[h["datatype"]]).itemsize
+        buf = bytearray(nbytes)                                   # (writable: torch wraps it for the upload without a copy)
+        view, got = memoryview(buf), 0
+        while got < nbytes:
+            n = f.readinto(view[got:])
+            if not n:
+                break
+            got += n
+    if got != nbytes:
+        raise NiftiError("%s: truncated data (%d of %d bytes)" % (path, got, nbytes))
+    return h, best_affine(h), buf
+
+
+def scaling_of(h):
+    """(scaled, slope, inter) of a header: whether read_nifti's scaled branch runs -- its condition, restated once for the
+    device decode -- and the two f64 constants it uses (a non-finite scl_inter counts as 0)."""
+    slope, inter = float(h["scl_slope"]), float(h["scl_inter"])
+    scaled = bool(np.isfinite(slope) and slope != 0.0 and not (slope == 1.0 and (inter == 0.0 or not np.isfinite(inter))))
+    return scaled, slope, (inter if np.isfinite(inter) else 0.0)
+
+
 def _qform_params(affine):
     """(quaternion b, c, d, qfac, voxel sizes) of an affine, as set_qform derives them: zooms = column lengths, a
     left-handed rotation part flips the third axis (qfac = -1), the nearest orthogonal matrix (polar part) gives the

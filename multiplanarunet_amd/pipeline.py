@@ -95,7 +95,7 @@ class TrainPipeline:
         if dev.type != "cuda":
             raise RuntimeError("TrainPipeline drives the HIP path: it needs a GPU device")
         B, d = sampler.batch_size, sampler.dim
-        C = int(sampler.volumes[0].n_channels)
+        C = int(sampler.n_channels)                     # (under a limitation queue no volume may be resident yet)
         self.gx = torch.zeros((B, d, d, C), dtype=torch.float32, device=dev)      # the graph's input tensors
         self.gy = torch.zeros((B, d * d, 1), dtype=torch.uint8, device=dev)
         self.gw = torch.ones(B, dtype=torch.float32, device=dev)
