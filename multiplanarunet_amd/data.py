@@ -309,12 +309,73 @@ class _VolCache:
                      _lib.ptr(vol._axes_dev[2]), _lib.ptr(vol._bg), vol._sc]
 
 
+class SliceRule:
+    """
+    The accept / reject rule of one training batch, host ints only: `_get_valid_slice_from`
+    (isotrophic_live_view_sequence_2d.py:119-161) with `validate_lab_vec`, `validate_lab` and `is_valid_im`
+    (isotrophic_live_view_sequence.py:91-128), as the reference EXECUTES it (tests/golden/sampler_rule_golden.json is
+    recorded from the reference class). Two pieces of state:
+
+    * `has_fg`: accepted slices with foreground so far; lives for the batch.
+    * the "classes seen" mask of ONE slot. `validate_lab_vec` returns a new array and `_get_valid_slice_from` rebinds only
+      its local name, so the vector `__getitem__` passes in is all zero for every slot: the mask starts at 0 per slot,
+      accumulates over that slot's tries only, and keeps the classes of a candidate that passed the vector check even when the
+      fraction or the all-background check then rejects it.
+
+    A slot's verdicts depend on earlier slots only through `has_fg` and the slot index, so slots must be judged in order,
+    each to its acceptance, but a slot's candidates may have been drawn at any time.
+    """
+
+    def __init__(self, batch_size, n_classes, fg_batch_fraction=0.5, force_all_fg="auto", max_tries=10):
+        self.batch_size, self.max_tries = int(batch_size), int(max_tries)
+        self.fg_classes = list(range(1, int(n_classes))) or [1]
+        self.fg_mask = 0
+        for c in self.fg_classes:
+            self.fg_mask |= 1 << c
+        self.n_fg_slices = int(np.ceil(batch_size * fg_batch_fraction))
+        if isinstance(force_all_fg, str) and force_all_fg.lower() == "auto":
+            self.force_all_fg = self.batch_size > len(self.fg_classes)
+        else:
+            self.force_all_fg = bool(force_all_fg)
+        self.reset()
+
+    def reset(self):
+        """A new batch."""
+        self.has_fg = 0
+        self._slot, self._acc = -1, 0
+
+    def judge(self, slot, n_try, mask, nonbg):
+        """Candidate number n_try (1-based) of `slot`: mask = bit l set for every label l < 32 in the plane, nonbg = the image
+        plane is not all background. True: accepted (the slot is done), False: rejected (the slot needs another candidate)."""
+        if slot != self._slot:
+            self._slot, self._acc = slot, 0
+        left = self.batch_size - slot
+        present = mask & self.fg_mask
+        last = n_try >= self.max_tries
+        if self.force_all_fg and not last:
+            new = self._acc | present
+            missing = len(self.fg_classes) - bin(new).count("1")
+            if not (missing == 0 or missing < left):
+                return False
+            self._acc = new                                   # kept even if the candidate is rejected below
+        if present:
+            ok, inc = True, 1
+        elif (self.n_fg_slices - self.has_fg) < left:
+            ok, inc = True, 0
+        else:
+            ok, inc = False, 0
+        if (ok or last) and (last or nonbg):
+            self.has_fg += inc
+            return True
+        return False
+
+
 class TrainSampler:
     """
     Random-plane batch sampler (training half of IsotrophicLiveViewSequence2D). Every plane is cut by the HIP
     sampling kernel straight into the batch tensors; the accept / reject statistics of a candidate (classes
     present, not-all-background) come back in one 8-byte read (mpu_plane_stats), which is the only host
-    synchronisation per candidate.
+    synchronisation per round of candidates. SliceRule decides.
     """
 
     def __init__(self, volumes, views, dim, real_space_span, batch_size, n_classes, noise_sd=0.1,
@@ -335,18 +396,16 @@ class TrainSampler:
         self.dim, self.span = int(dim), real_space_span
         self.batch_size, self.n_classes = int(batch_size), int(n_classes)
         self.noise_sd = float(noise_sd)
-        self.fg_classes = np.arange(1, n_classes) if n_classes > 1 else np.array([1])
-        self.n_fg_slices = int(np.ceil(batch_size * fg_batch_fraction))
-        self.force_all_fg = (batch_size > len(self.fg_classes)) if force_all_fg == "auto" else bool(force_all_fg)
+        self.rule = SliceRule(batch_size, n_classes, fg_batch_fraction, force_all_fg, max_tries)
         self.sample_weights = sample_weights or [1.0] * len(self.volumes)
         self.rng = np.random.RandomState(seed)
-        self.max_tries = max_tries
         self.augmenters = list(augmenters or [])      # applied after scaling (isotrophic_live_view_sequence_2d.py:203-208)
         self._cache = {}
-        self._fg_mask = 0
-        for c in self.fg_classes:
-            self._fg_mask |= 1 << int(c)
         self._views_l = [tuple(float(a) for a in v) for v in self.views]
+
+    @property
+    def max_tries(self):
+        return self.rule.max_tries
 
     def _vc(self, vol):
         """The volume's _VolCache; keyed by the VOLUME (a list index names different volumes over time under a queue)."""
@@ -423,10 +482,12 @@ class TrainSampler:
         """One batch. Round 5: the candidates of ALL undecided slots are cut before the host reads their statistics -- one
         read (one stream synchronisation) per ROUND instead of one per candidate: a batch whose first candidates are all
         accepted costs a single round trip, which is what lets the sampler run on a side stream beside a train step without
-        queueing behind its kernels 2 x B times (pipeline.TrainPipeline). The accept / reject rule and its sequential state
-        (foreground balance, classes seen) are the reference's, applied slot by slot in order; candidates are i.i.d. draws, so
-        deciding a slot on a candidate drawn before the earlier slots were settled changes nothing statistically. With no
-        rejection the random stream is consumed in the same order as the one-candidate-at-a-time form."""
+        queueing behind its kernels 2 x B times (pipeline.TrainPipeline). SliceRule alone decides, slot by slot in order: the
+        foreground count runs over the batch, the classes-seen mask over the tries of one slot (which is what the reference
+        executes, see SliceRule). Candidates are i.i.d. draws and a slot's verdicts depend on earlier slots only through the
+        foreground count and the slot index, so deciding a slot on a candidate drawn before the earlier slots were settled
+        changes nothing statistically. With no rejection the random stream is consumed in the same order as the
+        one-candidate-at-a-time form. Diagnostics of the last batch: `rounds`, `last_identifiers`, `last_trace`."""
         B, d = self.batch_size, self.dim
         dev = self.device
         qvols, retiring = self._take_from_queue(B) if self.queue is not None else (None, ())
@@ -434,8 +495,9 @@ class TrainSampler:
         Y = torch.empty((B, d, d), dtype=torch.uint8, device=dev)
         off_dev = torch.empty(B, dtype=torch.float64, device=dev)
         stats = torch.empty((B, 2), dtype=torch.int32, device=dev)
-        has_fg, fg_vec = 0, 0                                 # fg_vec: bit mask of the fg classes seen so far
-        nfg = len(self.fg_classes)
+        rule = self.rule
+        rule.reset()
+        trace = self.last_trace = [[] for _ in range(B)]      # (diagnostic: per slot the judged candidates, (mask, nonbg))
         vis = [None] * B
         tries = [0] * B
         fresh = [False] * B                                   # slot holds a candidate not yet judged
@@ -482,29 +544,12 @@ class TrainSampler:
             self.rounds += 1
             while first < B:                                  # judge in slot order until a candidate is rejected
                 slot = first
-                m, nonbg = st[slot][0], bool(st[slot][1])
+                m, nonbg = st[slot][0] & 0xFFFFFFFF, bool(st[slot][1])   # (i32 read of a u32 mask: label 31 is the sign bit)
                 fresh[slot] = False
-                present = m & self._fg_mask
-                last = tries[slot] >= self.max_tries
-                fg_try = fg_vec
-                if self.force_all_fg and not last:
-                    new = fg_vec | present
-                    missing = nfg - bin(new).count("1")
-                    if not (missing == 0 or missing < (B - slot)):
-                        break                                 # rejected: this slot gets a new candidate next round
-                    fg_try = new
-                if present:
-                    ok, inc = True, 1
-                elif (self.n_fg_slices - has_fg) < (B - slot):
-                    ok, inc = True, 0
-                else:
-                    ok, inc = False, 0
-                if (ok or last) and (last or nonbg):
-                    has_fg += inc
-                    fg_vec = fg_try
-                    first += 1
-                else:
-                    break
+                trace[slot].append((m, nonbg))
+                if not rule.judge(slot, tries[slot], m, nonbg):
+                    break                                     # this slot gets a new candidate next round
+                first += 1
         if qvols is None:
             index_of = {v: i for i, v in enumerate(self.volumes)}
             ws = [self.sample_weights[index_of[v]] for v in vis]

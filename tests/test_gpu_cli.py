@@ -17,8 +17,11 @@ def test_mp_train_then_predict_synthetic(tmp_path):
         "  optimizer: Adam\n  optimizer_kwargs: {lr: 1.0e-3, decay: 0.0, beta_1: 0.9, beta_2: 0.999, epsilon: 1.0e-8}\n"
         "  loss: SparseCategoricalCrossentropy\n  fg_batch_fraction: 0.5\n  bg_value: 1pct\n  scaler: RobustScaler\n"
         "  augmenters: [{cls_name: Elastic2D, kwargs: {alpha: [0, 100], sigma: [6, 9], apply_prob: 0.333}}]\n")
+    # 6 epochs of 40 steps. The run is deterministic, and at half that length it sits on the steep part of the learning curve,
+    # where the batch stream decides the outcome: measured mean Dice 0.914 with the sampler's earlier accept / reject rule and
+    # 0.495 with the reference's (data.SliceRule); at 30 steps per epoch the latter gives 0.941, at 40 steps 0.943 (earlier rule 0.874)
     mp.entry_func(["train", "--project_dir", str(proj), "--synthetic", "4", "--epochs", "6",
-                   "--train_images_per_epoch", "160", "--val_images_per_epoch", "32"])
+                   "--train_images_per_epoch", "320", "--val_images_per_epoch", "32"])
     assert (proj / "model" / "model_weights.npz").exists() and (proj / "views.npz").exists()
     assert any(f.startswith("@epoch") for f in os.listdir(proj / "model"))
     from multiplanarunet_amd import hdf5, formats

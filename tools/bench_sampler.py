@@ -14,6 +14,10 @@ for augs in (None, [{"cls_name": "Elastic2D", "kwargs": {"alpha": [0, 450], "sig
     for _ in range(3): s()
     torch.cuda.synchronize(); t0 = time.perf_counter()
     n = 20
-    for _ in range(n): x, y, w = s()
+    rounds = cands = 0
+    for _ in range(n):
+        x, y, w = s()
+        rounds += s.rounds; cands += sum(len(c) for c in s.last_trace)
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
-    print("augmenters=%s: %.1f ms / batch of 16 -> %.0f slices/s" % (bool(augs), dt / n * 1e3, 16 * n / dt))
+    print("augmenters=%s: %.1f ms / batch of 16 -> %.0f slices/s; %.2f candidates, %.2f rounds (host reads) per batch"
+          % (bool(augs), dt / n * 1e3, 16 * n / dt, cands / n, rounds / n))
