@@ -554,7 +554,9 @@ int mpu_unet_optimizer_pack(const mpu_unet* m, const mpu_optimizer_config* cfg, 
 
 /* Single-layer entry points (unit tests / layer-wise integration). Channels
  * must be multiples of 8. d_w is the fp32 Keras HWIO kernel; d_w_dgrad may be
- * NULL; sizes: fwd taps*Cin*Cout elements, dgrad 9*Cin*Cout elements.
+ * NULL; sizes: fwd taps*Cin*Cout elements, dgrad 9*Cin*Cout elements (every
+ * element of both is written, except that the 1x1 mode writes only the first
+ * Cin*Cout elements of d_w_dgrad and leaves the other 8*Cin*Cout untouched).
  * mpu_conv2d_igemm computes out[m][n] = act(sum_k in[m@tap][k] w[tap][n][k] + bias[n])
  * (* (mask[m][n] > 0) when d_mask is given) over the channel-concatenation of
  * in0 and in1. */

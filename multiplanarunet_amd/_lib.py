@@ -281,6 +281,17 @@ def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def owned(t, shape, dtype, device, what):
+    """The caller-owned output or scratch tensor `t` after a shape / dtype check, or a fresh torch.empty when t is None."""
+    import torch
+    shape = tuple(int(s) for s in shape) if isinstance(shape, (tuple, list, torch.Size)) else (int(shape),)
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError("%s: expected a contiguous %s tensor of shape %s, got %s %s" % (what, dtype, shape, t.dtype, tuple(t.shape)))
+    return t
+
+
 def stream_ptr():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -19,10 +19,13 @@ def gaussian_kernel1d(sigma, truncate=4.0):
     return phi / phi.sum(), radius
 
 
-def elastic_transform_2d(image, labels, alpha, sigma, bg_val=0.0, noise=None, generator=None):
+def elastic_transform_2d(image, labels, alpha, sigma, bg_val=0.0, noise=None, generator=None, workspace=None, out=None,
+                         out_labels=None):
     """
     elastic_deformation.py:6-69 on device tensors: image [H,W(,C)] f32, labels [H,W] u8 or None ->
     (image', labels'). noise: optional [2,H,W] f64 uniform fields (default: torch.rand on the device).
+    workspace (mpu_elastic_workspace_doubles(H, W) f64), out [H,W,C] f32, out_labels [H,W] u8: caller-owned device tensors
+    (default: allocated here).
     """
     squeeze = image.ndim == 2
     img = (image[..., None] if squeeze else image).contiguous().float()
@@ -35,12 +38,15 @@ def elastic_transform_2d(image, labels, alpha, sigma, bg_val=0.0, noise=None, ge
     noise = torch.as_tensor(noise).to(device=dev, dtype=torch.float64).contiguous()
     w, radius = gaussian_kernel1d(sigma)
     wt = torch.tensor(w, dtype=torch.float64, device=dev)
-    ws = torch.empty(int(_lib.load().mpu_elastic_workspace_doubles(H, W)), dtype=torch.float64, device=dev)
-    out = torch.empty_like(img)
+    n_ws = int(_lib.load().mpu_elastic_workspace_doubles(H, W))
+    ws = torch.empty(n_ws, dtype=torch.float64, device=dev) if workspace is None else workspace
+    if ws.dtype != torch.float64 or ws.numel() < n_ws or not ws.is_contiguous():
+        raise ValueError("workspace: expected %d contiguous f64" % n_ws)
+    out = _lib.owned(out, img.shape, torch.float32, dev, "out")
     lab = lab_out = None
     if labels is not None:
         lab = labels.to(device=dev, dtype=torch.uint8).contiguous()
-        lab_out = torch.empty_like(lab)
+        lab_out = _lib.owned(out_labels, lab.shape, torch.uint8, dev, "out_labels")
     _lib.call("mpu_elastic_transform_2d", _lib.ptr(img), _lib.ptr(lab), H, W, C, _lib.ptr(noise), _lib.ptr(wt), radius,
               float(alpha), _lib.ptr(bgt), _lib.ptr(ws), _lib.ptr(out), _lib.ptr(lab_out), _lib.stream_ptr())
     return (out[..., 0] if squeeze else out), lab_out

@@ -86,11 +86,12 @@ def read_labels_host(label_path, raw_nifti=True):
     return ("host", load_label_file(label_path))
 
 
-def decode_nifti_payload(header, payload, device, labels=False, path=""):
+def decode_nifti_payload(header, payload, device, labels=False, path="", out=None, bad=None):
     """One host-to-device copy of the payload bytes and mpu_volume_decode (csrc/volume_decode.hip) on the current stream:
     f32 [X,Y,Z,C] with the bits of formats.load_nifti, or (labels=True) u8 [X,Y,Z] with the bits of formats.load_nifti_labels.
     A label value NumPy's astype(uint8) is platform-defined for (non-finite, or outside [0, 256) after truncation) is a
-    ValueError naming the file."""
+    ValueError naming the file. out / bad (labels: the int64 [1] counter of such values): caller-owned device tensors
+    (default: allocated here)."""
     import ctypes as C
     import sys
     from . import _lib
@@ -104,10 +105,10 @@ def decode_nifti_payload(header, payload, device, labels=False, path=""):
     dev = torch.device(device)
     raw = torch.frombuffer(payload, dtype=torch.uint8).to(dev)
     if labels:
-        out = torch.empty(shape4[:3], dtype=torch.uint8, device=dev)
-        bad = torch.empty(1, dtype=torch.int64, device=dev)
+        out = _lib.owned(out, shape4[:3], torch.uint8, dev, "out")
+        bad = _lib.owned(bad, 1, torch.int64, dev, "bad")
     else:
-        out = torch.empty(shape4, dtype=torch.float32, device=dev)
+        out = _lib.owned(out, shape4, torch.float32, dev, "out")
         bad = None
     _lib.call("mpu_volume_decode", _lib.ptr(raw), int(header["datatype"]), int(swap), (C.c_int64 * 4)(*shape4), int(scaled),
               float(slope), float(inter), _lib.MPU_DECODE_LABELS if labels else _lib.MPU_DECODE_IMAGE, _lib.ptr(out),

@@ -207,14 +207,14 @@ class Volume:
 # --------------------------------------------------------------------------- #
 # sampling
 # --------------------------------------------------------------------------- #
-def sample_view(volume, geom, want_labels=True, out=None):
-    """Planes of one view, model order: X f32 [P,dim,dim,C], y u8 [P,dim,dim] or None."""
+def sample_view(volume, geom, want_labels=True, out=None, out_labels=None):
+    """Planes of one view, model order: X f32 [P,dim,dim,C], y u8 [P,dim,dim] or None (out / out_labels: caller-owned)."""
     P, d, Cn = geom.n_planes, geom.dim, volume.n_channels
     dev = volume.device
     X = out if out is not None else torch.empty((P, d, d, Cn), dtype=torch.float32, device=dev)
     y = None
     if want_labels and volume.labels is not None:
-        y = torch.empty((P, d, d), dtype=torch.uint8, device=dev)
+        y = _lib.owned(out_labels, (P, d, d), torch.uint8, dev, "out_labels")
     offs = geom.device_axes(dev)[1] if hasattr(geom, "device_axes") else torch.tensor(geom.offsets, device=dev)
     shape = (C.c_int32 * 4)(*[int(v) for v in volume.image.shape])
     gs = geom.struct(volume.rot_mat, volume.axes)
@@ -299,7 +299,7 @@ def _map_entry(method, nearest, linear):
     raise NotImplementedError("map method %r: 'nearest' and 'linear' are on the path (fuse_and_predict.py:92-137)" % (method,))
 
 
-def map_real_space_pred(pred, grid, inv_basis, volume, method="nearest"):
+def map_real_space_pred(pred, grid, inv_basis, volume, method="nearest", out=None):
     """
     pred in the reference layout [dim,dim,P,K] (torch, device) on axes
     grid=(g,g,offsets) -> mapped f32 [X,Y,Z,K]; OOB voxels -> [1,0,..,0].
@@ -307,13 +307,14 @@ def map_real_space_pred(pred, grid, inv_basis, volume, method="nearest"):
     method="linear" (fuse_and_predict.py:130-134, the other half of the reference's signature): the K probability
     maps are interpolated by the same RegularGridInterpolator -- per axis _find_indices, per class an fp64 sum over
     the eight corners in itertools.product order of pred * ((1*wx)*wy)*wz, rounded once to f32 -- bit for bit.
+    out: caller-owned f32 [X,Y,Z,K] (default: allocated here).
     """
     entry = _map_entry(method, "mpu_map_view_nearest", "mpu_map_view_linear")
     pm = pred.permute(2, 0, 1, 3)
     h = _ViewPredHolder(pm, grid, inv_basis, volume.device)
     K = int(pm.shape[-1])
     X, Y, Z = (int(v) for v in volume.image.shape[:3])
-    mapped = torch.empty((X, Y, Z, K), dtype=torch.float32, device=volume.device)
+    mapped = _lib.owned(out, (X, Y, Z, K), torch.float32, volume.device, "out")
     vg = volume.voxel_grid()
     _lib.call(entry, C.byref(vg), C.byref(h.struct), K, _lib.ptr(mapped),
               _lib.stream_ptr())
@@ -321,12 +322,12 @@ def map_real_space_pred(pred, grid, inv_basis, volume, method="nearest"):
 
 
 def map_and_fuse(volume, view_preds, W=None, b=None, sum_fusion=False,
-                 want_probs=True, want_labels=True, method="nearest"):
+                 want_probs=True, want_labels=True, method="nearest", out_probs=None, out_labels=None):
     """
     Fused _multi_view_predict_on + merge_multi_view_preds. view_preds: list of
     (pred [P,dim,dim,K] device f32, grid=(g,g,offsets), inv_basis[, ViewGeometry.device_axes]). Returns
     (merged f32 [X,Y,Z,K] or None, merged_map u8 [X,Y,Z] or None). method: how a voxel reads a view's prediction
-    ("nearest" / "linear", as map_real_space_pred); the fusion arithmetic is the same.
+    ("nearest" / "linear", as map_real_space_pred); the fusion arithmetic is the same. out_probs / out_labels: caller-owned.
     """
     entry = _map_entry(method, "mpu_map_fuse_views", "mpu_map_fuse_views_linear")
     dev = volume.device
@@ -335,8 +336,8 @@ def map_and_fuse(volume, view_preds, W=None, b=None, sum_fusion=False,
     K = int(holders[0].pred.shape[-1])
     arr = (_lib.ViewPred * V)(*[h.struct for h in holders])
     X, Y, Z = (int(v) for v in volume.image.shape[:3])
-    probs = torch.empty((X, Y, Z, K), dtype=torch.float32, device=dev) if want_probs else None
-    labels = torch.empty((X, Y, Z), dtype=torch.uint8, device=dev) if want_labels else None
+    probs = _lib.owned(out_probs, (X, Y, Z, K), torch.float32, dev, "out_probs") if want_probs else None
+    labels = _lib.owned(out_labels, (X, Y, Z), torch.uint8, dev, "out_labels") if want_labels else None
     Wd = bd = None
     if not sum_fusion:
         Wd = torch.as_tensor(W, dtype=torch.float32).to(dev).reshape(V, K).contiguous()
@@ -374,11 +375,11 @@ def map_accumulate(volume, pred_chunk, grid, inv_basis, Wv, p_lo, p_hi, owns_oob
     return z
 
 
-def fusion_finalize(z, b=None, sum_fusion=False, want_probs=True):
+def fusion_finalize(z, b=None, sum_fusion=False, want_probs=True, out_probs=None, out_labels=None):
     K = int(z.shape[-1])
     n = z.numel() // K
-    probs = torch.empty_like(z) if want_probs else None
-    labels = torch.empty(z.shape[:-1], dtype=torch.uint8, device=z.device)
+    probs = _lib.owned(out_probs, z.shape, torch.float32, z.device, "out_probs") if want_probs else None
+    labels = _lib.owned(out_labels, z.shape[:-1], torch.uint8, z.device, "out_labels")
     bd = None if sum_fusion else torch.as_tensor(b, dtype=torch.float32).to(z.device).reshape(K).contiguous()
     _lib.call("mpu_fusion_finalize", _lib.ptr(z), n, K, _lib.ptr(bd), 1 if sum_fusion else 0,
               _lib.ptr(probs), _lib.ptr(labels), _lib.stream_ptr())

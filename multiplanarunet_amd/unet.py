@@ -766,13 +766,14 @@ class UNet:
         n = _lib.load().mpu_unet_grad_ready_points(self._h, buf, 32)
         return [int(buf[i]) for i in range(n)]
 
-    def forward_backward(self, x, y, sample_weight=None, want_loss=True, ready_events=None, adam=None):
+    def forward_backward(self, x, y, sample_weight=None, want_loss=True, ready_events=None, adam=None, loss_out=None):
         """Train-mode forward + backward; fills self.grads (sum-gradient). Returns (probs, loss[B,H*W] or None); with a per-image
         loss (compile) the loss is [B,1]: sample_weight[b] * L_b.
         ready_events: optional list (one entry per grad_ready_points(), None = skip) of torch.cuda.Event recorded
         on the current stream when that part of the gradient buffer is final (data-parallel overlap).
         adam: (t, step_dev) -- ALSO apply the optimizer inside the same library call (mpu_unet_backward_adam: the
-        update of the deep levels' parameters runs beside the weight gradients of the high-resolution levels)."""
+        update of the deep levels' parameters runs beside the weight gradients of the high-resolution levels).
+        loss_out: caller-owned f32 device tensor for the loss (default: allocated here)."""
         self._require_trainable("forward_backward")
         X = self._as_input(x)
         B = X.shape[0]
@@ -788,8 +789,9 @@ class UNet:
                                  else sample_weight).to(device=self.device, dtype=torch.float32).contiguous()
         probs = self._forward(X, training=True)
         self._update_metrics(probs, y)
-        loss = torch.empty((B, 1 if self._per_image_loss else y.shape[1]), dtype=torch.float32,
-                           device=self.device) if want_loss else None
+        loss = None
+        if want_loss:
+            loss = _lib.owned(loss_out, (B, 1 if self._per_image_loss else y.shape[1]), torch.float32, self.device, "loss_out")
         if adam is not None:
             if ready_events is not None:
                 raise ValueError("forward_backward: adam= and ready_events= exclude each other")
@@ -950,17 +952,18 @@ class UNet:
                              tuple(self._slots), self.params, self.grads, self.packed, self.bn_state, self._metrics_state)
         return replay
 
-    def train_step(self, x, y, sample_weight=None, want_loss=True):
-        """One Model.fit inner step. Returns the per-pixel loss [B,H*W] (device) or None."""
+    def train_step(self, x, y, sample_weight=None, want_loss=True, loss_out=None):
+        """One Model.fit inner step. Returns the per-pixel loss [B,H*W] (device) or None (loss_out: as
+        forward_backward)."""
         self._require_trainable("train_step")
         hook = self._grad_hook
         if hook is None and not self.l2_reg and self._plain_adam():     # single GPU, no l2 term: backward + optimizer as one library call
             self._ensure_slots()
             self.iterations += 1
-            _, loss = self.forward_backward(x, y, sample_weight, want_loss, adam=(self.iterations, None))
+            _, loss = self.forward_backward(x, y, sample_weight, want_loss, adam=(self.iterations, None), loss_out=loss_out)
             return loss
         events = getattr(hook, "ready_events", None)
-        _, loss = self.forward_backward(x, y, sample_weight, want_loss, ready_events=events)
+        _, loss = self.forward_backward(x, y, sample_weight, want_loss, ready_events=events, loss_out=loss_out)
         if hook is not None:
             hook(self.grads)                     # data-parallel: SUM of replica gradients
         self._add_l2(want_loss)                  # once, after the replica sum (Keras scales it 1/replicas per replica)

@@ -39,6 +39,13 @@ def tol(dtype, ref):
     return (1e-5, 1e-5 * s) if dtype == torch.float32 else (1.2e-2, 1.2e-2 * s)
 
 
+def wgrad_tol(dtype, ref):
+    """(rtol, atol) of a weight gradient: bf16 operands give exact products, accumulated in f32."""
+    if dtype == torch.bfloat16:
+        return 2e-3, 2e-3 * float(ref.abs().max())
+    return tol(dtype, ref)
+
+
 def rnd(t, dtype):
     """round to the storage dtype, return f64"""
     return t.to(dtype).to(torch.float64)
@@ -319,9 +326,7 @@ def _run_case(case, dtype, workspace=False, x3=False, report=None):
     # weight gradient
     dW = ops.conv2d_wgrad(mode, x0, dzd, x1=x1)
     ref = dw_ref.reshape(k * k, Cin, Cout)
-    rt, at = tol(dtype, ref)
-    if dtype == torch.bfloat16:
-        rt, at = 2e-3, 2e-3 * float(ref.abs().max())      # f32 accumulate of exact bf16 products
+    rt, at = wgrad_tol(dtype, ref)
     np.testing.assert_allclose(dW.cpu().double().numpy(), ref.numpy(), rtol=rt, atol=at)
 
 
@@ -384,7 +389,7 @@ def test_shape_sweep_against_fp64_reference(case, dtype):
     _run_case(case, dtype)
 
 
-@pytest.mark.parametrize("case", [
+FIRST_LAYER_CASES = [
     # B, H,   W,   Cout, image channels
     (16, 128, 128, 64, 1),        # BASELINE configs[1] first layer: dedicated HBM-bound kernel, 1024 strips
     (3, 20, 50, 64, 2),           # two image channels, ragged row passes (50 = 32 + 18)
@@ -392,28 +397,43 @@ def test_shape_sweep_against_fp64_reference(case, dtype):
     (5, 9, 7, 8, 2),              # one channel group: 256 pixel lanes, rows shorter than a pass
     (2, 12, 40, 24, 1),           # 3 channel groups (not a power of two): general path, same entry point
     (2, 16, 16, 64, 3),           # three image channels: general path
-])
-def test_first_layer_weight_gradient(case):
-    """mpu_conv2d_wgrad_first_layer (wgrad_c8.hip) vs an f64 evaluation of dW[t][ci][co] = sum x[px+t][ci] dz[px][co]
-    and db = sum dz on the same bf16-rounded operands; padding channels of dW must be exactly zero."""
-    from multiplanarunet_amd import ops
+]
+
+
+def first_layer_inputs(case):
+    """(x [B,H,W,8] bf16, dz bf16, fp64 dW [9,8,Cout], fp64 db) of a first-layer case: dW[t][ci][co] = sum x[px+t][ci] dz[px][co]
+    and db = sum dz on the same bf16-rounded operands."""
     B, H, W, Cout, CI = case
     g = torch.Generator().manual_seed(B * 1000 + H * 10 + CI)
     x = torch.zeros(B, H, W, 8)
     x[..., :CI] = torch.randn(B, H, W, CI, generator=g)
     x = x.bfloat16()
     dz = torch.randn(B, H, W, Cout, generator=g).bfloat16()
-    dW, db = ops.conv2d_wgrad_first_layer(x.cuda(), CI, dz.cuda())
     xd, zd = x.double(), dz.double()
     xp = F.pad(xd.permute(0, 3, 1, 2), (1, 1, 1, 1)).permute(0, 2, 3, 1)        # [B, H+2, W+2, 8]
     ref = torch.stack([torch.einsum("bhwi,bhwo->io", xp[:, ky:ky + H, kx:kx + W], zd)
                        for ky in range(3) for kx in range(3)])                   # [9, 8, Cout]
+    return x, dz, ref, zd.sum((0, 1, 2))
+
+
+def check_first_layer(dW, db, ref, rb, CI):
+    """The bounds of the first-layer weight and bias gradient; padding channels of dW must be exactly zero."""
     dWc = dW.cpu().double()
     assert torch.count_nonzero(dWc[:, CI:]) == 0
-    s = float(ref.abs().max())
-    assert float((dWc - ref).abs().max()) <= 2e-3 * s
-    rb = zd.sum((0, 1, 2))
+    assert float((dWc - ref).abs().max()) <= 2e-3 * float(ref.abs().max())
     assert float((db.cpu().double() - rb).abs().max()) <= 2e-3 * float(rb.abs().max()) + 1e-3
+
+
+@pytest.mark.parametrize("case", FIRST_LAYER_CASES)
+def test_first_layer_weight_gradient(case):
+    """mpu_conv2d_wgrad_first_layer (wgrad_c8.hip) vs an f64 evaluation of dW[t][ci][co] = sum x[px+t][ci] dz[px][co]
+    and db = sum dz on the same bf16-rounded operands; padding channels of dW must be exactly zero."""
+    from multiplanarunet_amd import ops
+    B, H, W, Cout, CI = case
+    x, dz, ref, rb = first_layer_inputs(case)
+    dW, db = ops.conv2d_wgrad_first_layer(x.cuda(), CI, dz.cuda())
+    check_first_layer(dW, db, ref, rb, CI)
+    s = float(ref.abs().max())
     # the general-purpose entry point agrees (it has no channel-count hint and runs the MFMA kernels)
     dWg = ops.conv2d_wgrad(CONV3, x.cuda(), dz.cuda()).cpu().double()
     assert float((dWg - ref).abs().max()) <= 2e-3 * s
