@@ -164,6 +164,23 @@ int mpu_volume_decode(const void* d_payload, int32_t datatype, int32_t byteswap,
                       int32_t scaled, double slope, double inter, int32_t kind, void* d_out,
                       uint64_t* d_bad_count, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * Resident volume -> NIfTI-1 payload (csrc/volume_encode.hip): the inverse of mpu_volume_decode, and the
+ * np.asfortranarray(data).tobytes(order="F") of nifti.write_nifti (nib.save(...), mpunet/bin/predict.py:90-117) done on the
+ * device. d_in: [X,Y,Z,C] in C order, aligned to its element width. shape = (X, Y, Z, C), every entry in [1, 32767].
+ * d_payload: the bytes as they lie behind vox_offset of a little-endian file (x fastest, then y, z and the fourth dimension):
+ *   d_payload[((c * Z + z) * Y + y) * X + x] = convert(d_in[((x * Y + y) * Z + z) * C + c])
+ * Pairs (every other one is MPU_EUNSUPPORTED):
+ *   MPU_ENCODE_F32 -> datatype 16   bit for bit (NaN payloads included); d_payload aligned to 4 bytes; d_bad_count may be NULL
+ *   MPU_ENCODE_U8 / _I32 / _I64 -> datatype 2   class indices; d_payload needs no alignment. A value outside [0, 256) is
+ *                                   written as 0 and counted, once per element, in *d_bad_count (device u64, zeroed by the call).
+ * Asynchronous on `stream`; 64-bit indices throughout; only the payload's X*Y*Z*C elements are written; the only atomic is the
+ * counter's; two calls give the same bytes. A call that returns an error has written nothing, the counter included.
+ * ------------------------------------------------------------------------ */
+typedef enum { MPU_ENCODE_F32 = 0, MPU_ENCODE_U8 = 1, MPU_ENCODE_I32 = 2, MPU_ENCODE_I64 = 3 } mpu_encode_source;
+int mpu_volume_encode(const void* d_in, int32_t source, const int64_t shape[4], int32_t datatype, void* d_payload,
+                      uint64_t* d_bad_count, void* stream);
+
 /* One view's prediction volume as seen by the back-mapping
  * (mpunet/utils/fusion/fuse_and_predict.py:92-137). */
 typedef struct {

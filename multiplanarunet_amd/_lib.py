@@ -94,6 +94,7 @@ class OptimizerConfig(C.Structure):    # mpu_optimizer_config
 
 # mpu_scaler_kind
 MPU_DECODE_IMAGE, MPU_DECODE_LABELS = 0, 1      # mpu_decode_kind
+MPU_ENCODE_F32, MPU_ENCODE_U8, MPU_ENCODE_I32, MPU_ENCODE_I64 = range(4)      # mpu_encode_source
 MPU_SCALER_NONE, MPU_SCALER_SUB_DIV, MPU_SCALER_MUL_ADD, MPU_SCALER_DIV, MPU_SCALER_QUANTILE = range(5)
 
 
@@ -201,6 +202,7 @@ _SIGS = {
     "mpu_volume_order_stats": (C.c_int, [c_p, i64, i32, i32, C.POINTER(i64), i32, c_p, i64, C.POINTER(f32), C.POINTER(i64), c_p]),
     "mpu_volume_moments": (C.c_int, [c_p, i64, i32, C.POINTER(f64), c_p, i64, C.POINTER(f64), c_p]),
     "mpu_volume_decode": (C.c_int, [c_p, i32, i32, C.POINTER(i64), i32, f64, f64, i32, c_p, c_p, c_p]),
+    "mpu_volume_encode": (C.c_int, [c_p, i32, C.POINTER(i64), i32, c_p, c_p, c_p]),
     "mpu_unet_backward_adam": (C.c_int, [c_p, i32] + [c_p] * 10 + [i64, c_p, f64, f64, f64, f64, c_p]),
     "mpu_optimizer_num_slots": (C.c_int, [C.POINTER(OptimizerConfig)]),
     "mpu_optimizer_step": (C.c_int, [C.POINTER(OptimizerConfig), c_p, c_p, C.POINTER(c_p), i64, i64, c_p, c_p]),

@@ -3,6 +3,9 @@
 loop, back-mapping and fusion run in multiplanarunet_amd.predict (distributed: plane-sharded).
 Outputs <out_dir>/nii_files/<id>_PRED.nii.gz for NIfTI inputs (mpunet/bin/predict.py:90-117; native writer, nifti.py) and
 <id>_PRED.npz (labels + affine) for .npz / synthetic volumes; --out_format forces one of them.
+Rank 0 writes through ONE prediction_writer.PredictionWriter: the compute thread makes a NIfTI file's payload bytes on the device
+(mpu_volume_encode) and fetches them with one copy; gzip, the write and the rename onto the final name run on the writer's thread
+while the next volume is predicted. The writer is closed before run() returns or raises: every file is complete by then.
 """
 import os
 from argparse import ArgumentParser
@@ -50,15 +53,32 @@ def best_model_path(model_dir):
     return get_best_model(model_dir)
 
 
+def plan_todo(items, dst_of, continue_, overwrite):
+    """(items to predict, first conflicting output or None). What there is to do is settled from the FINAL output names alone, so
+    that a volume whose output exists is never read; an output that exists without --overwrite / --continue stops the run where
+    the loop reaches it. A temporary file a killed run left behind (prediction_writer.temp_path) is no output: its volume is
+    predicted again and the file is overwritten."""
+    todo, conflict = [], None
+    for item in items:
+        dst = dst_of(item)
+        if os.path.exists(dst) and continue_:
+            continue
+        if os.path.exists(dst) and not overwrite:
+            conflict = dst
+            break
+        todo.append(item)
+    return todo, conflict
+
+
 def run(args):
     from .. import distributed as D
     from ..unet import UNet
     from ..fusion_model import FusionModel
     from ..predict import multi_view_predict
     from ..interpolation import dice_all
-    from ..data import load_volume_to_device
+    from ..data import load_volume_to_device, encoded_payload_to_host
     from ..nifti import volume_identifier
-    from ..formats import save_nifti
+    from ..prediction_writer import PredictionWriter
     project_dir = os.path.abspath(args.project_dir)
     validate_project_dir(project_dir)
     for req in ("views.npz", "model"):
@@ -116,63 +136,70 @@ def run(args):
         out_base = os.path.join(nii, item.identifier) if args.save_input_files else nii
         return as_nii, out_base, os.path.join(out_base, "%s_PRED.%s" % (item.identifier, "nii.gz" if as_nii else "npz"))
 
-    # what there is to do is settled from the names alone, so that a volume whose output exists is never read; an output that
-    # exists without --overwrite / --continue stops the run where the loop reaches it, as before
-    todo, conflict = [], None
-    for item in vols:
-        dst = plan(item)[2]
-        if os.path.exists(dst) and args.continue_:
-            continue
-        if os.path.exists(dst) and not args.overwrite:
-            conflict = dst
-            break
-        todo.append(item)
+    todo, conflict = plan_todo(vols, lambda item: plan(item)[2], args.continue_, args.overwrite)
     if lazy:                                              # at most the current and the next volume are loaded
         from ..volume_queue import LazyQueue, Dataset
         todo = LazyQueue(Dataset(todo, key), logger=log)
-    for v in todo:
-        as_nii, out_base, dst = plan(v)
-        if world > 1:
-            res = D.multi_view_predict_sharded(model, v, views, build["dim"], fit["real_space_span"], fm,
-                                               sum_fusion=args.sum_fusion, batch_size=None, want_probs=args.no_argmax,
-                                               map_method=args.map_method)
-            probs, labels = res if args.no_argmax else (None, res)
-        else:
-            pve = None
-            if v.labels is not None and not args.no_eval:     # bin/predict.py:334-346: per-view Dice inside the loop
-                rows = per_view.setdefault(v.identifier, {})
-                pve = dict(eval_prob=args.eval_prob, n_classes=build["n_classes"], log=log,
-                           report=lambda i, view, vd, md, mean, rows=rows: rows.__setitem__(i, (view, vd, md, float(mean))))
-            probs, labels = multi_view_predict(model, v, views, build["dim"], fit["real_space_span"], fm,
-                                               sum_fusion=args.sum_fusion, batch_size=None,
-                                               want_probs=args.no_argmax, per_view_eval=pve, map_method=args.map_method)
-        if rank == 0 and args.save_input_files:
-            sub = out_base                                # the volume as it was read: unscaled image, label map
-            os.makedirs(sub, exist_ok=True)
-            raw = v.image.cpu().numpy()                   # (the volume as read: the scaler is applied by the sampling kernel)
-            raw = raw[..., 0] if raw.shape[-1] == 1 else raw
-            lab_h = None if v.labels is None else v.labels.cpu().numpy().astype(np.uint8)
-            if as_nii:
-                save_nifti(os.path.join(sub, "%s_IMAGE.nii.gz" % v.identifier), raw, v.affine)
-                if lab_h is not None:
-                    save_nifti(os.path.join(sub, "%s_LABELS.nii.gz" % v.identifier), lab_h, v.affine)
+    writer = PredictionWriter() if rank == 0 else None
+
+    def put_nifti(path, t, affine):
+        """Compute thread: encode on the device, one copy to the host, then the job for the writer's thread."""
+        shape, dtype, payload = encoded_payload_to_host(t, path)
+        writer.submit_nifti(path, shape, dtype, affine, payload)
+
+    try:
+        for v in todo:
+            as_nii, out_base, dst = plan(v)
+            if world > 1:
+                res = D.multi_view_predict_sharded(model, v, views, build["dim"], fit["real_space_span"], fm,
+                                                   sum_fusion=args.sum_fusion, batch_size=None, want_probs=args.no_argmax,
+                                                   map_method=args.map_method)
+                probs, labels = res if args.no_argmax else (None, res)
             else:
-                np.savez_compressed(os.path.join(sub, "%s_IMAGE.npz" % v.identifier), image=raw, affine=v.affine)
-                if lab_h is not None:
-                    np.savez_compressed(os.path.join(sub, "%s_LABELS.npz" % v.identifier), labels=lab_h, affine=v.affine)
-        if rank == 0:
-            if as_nii:                                # the label map, or with --no_argmax the fused [X,Y,Z,K] probabilities
-                pred = probs.cpu().numpy() if (args.no_argmax and probs is not None) else labels.cpu().numpy().astype(np.uint8)
-                save_nifti(dst, pred, v.affine)
-            else:
-                out = {"labels": labels.cpu().numpy(), "affine": v.affine}
-                if args.no_argmax and probs is not None:
-                    out["probs"] = probs.cpu().numpy()
-                np.savez_compressed(dst, **out)
-            if v.labels is not None and not args.no_eval:
-                d = dice_all(v.labels, labels, n_classes=build["n_classes"], ignore_zero=True)
-                results[v.identifier] = d
-                log("%s: dices %s mean %.4f" % (v.identifier, np.round(d, 4), float(np.nanmean(d))))
+                pve = None
+                if v.labels is not None and not args.no_eval:     # bin/predict.py:334-346: per-view Dice inside the loop
+                    rows = per_view.setdefault(v.identifier, {})
+                    pve = dict(eval_prob=args.eval_prob, n_classes=build["n_classes"], log=log,
+                               report=lambda i, view, vd, md, mean, rows=rows: rows.__setitem__(i, (view, vd, md, float(mean))))
+                probs, labels = multi_view_predict(model, v, views, build["dim"], fit["real_space_span"], fm,
+                                                   sum_fusion=args.sum_fusion, batch_size=None,
+                                                   want_probs=args.no_argmax, per_view_eval=pve, map_method=args.map_method)
+            if rank == 0 and args.save_input_files:
+                sub = out_base                            # the volume as it was read: unscaled image, label map
+                os.makedirs(sub, exist_ok=True)
+                raw = v.image                             # (the volume as read: the scaler is applied by the sampling kernel)
+                raw = raw.reshape(raw.shape[:3]) if raw.shape[-1] == 1 else raw
+                if as_nii:
+                    put_nifti(os.path.join(sub, "%s_IMAGE.nii.gz" % v.identifier), raw, v.affine)
+                    if v.labels is not None:
+                        put_nifti(os.path.join(sub, "%s_LABELS.nii.gz" % v.identifier), v.labels, v.affine)
+                else:
+                    writer.submit_npz(os.path.join(sub, "%s_IMAGE.npz" % v.identifier),
+                                      {"image": raw.cpu().numpy(), "affine": v.affine})
+                    if v.labels is not None:
+                        writer.submit_npz(os.path.join(sub, "%s_LABELS.npz" % v.identifier),
+                                          {"labels": v.labels.cpu().numpy().astype(np.uint8), "affine": v.affine})
+            if rank == 0:
+                if as_nii:                            # the label map, or with --no_argmax the fused [X,Y,Z,K] probabilities
+                    put_nifti(dst, probs if (args.no_argmax and probs is not None) else labels, v.affine)
+                else:
+                    out = {"labels": labels.cpu().numpy(), "affine": v.affine}
+                    if args.no_argmax and probs is not None:
+                        out["probs"] = probs.cpu().numpy()
+                    writer.submit_npz(dst, out)
+                if v.labels is not None and not args.no_eval:
+                    d = dice_all(v.labels, labels, n_classes=build["n_classes"], ignore_zero=True)
+                    results[v.identifier] = d
+                    log("%s: dices %s mean %.4f" % (v.identifier, np.round(d, 4), float(np.nanmean(d))))
+    except BaseException:
+        if writer is not None:                            # (this error wins; what was queued is still written, completely)
+            try:
+                writer.close()
+            except OSError:
+                pass
+        raise
+    if writer is not None:
+        writer.close()                                    # every file is complete from here on; a write failure is raised here
     if conflict is not None:
         raise OSError("%s exists (use --overwrite or --continue)" % conflict)
     if rank == 0 and results:

@@ -11,13 +11,18 @@ train_fusion.py:336): the IMAGES of a round are dealt over the ranks -- each ran
 (the expensive part: V U-Net passes per image) and keeps their points -- and FusionModel.fit runs data parallel: per step one
 SUM all-reduce of V*K + K + 2 doubles, per epoch one of the 3K validation counts. Every rank holds the same FusionLayer
 weights at all times; rank 0 alone writes the weights file.
+
+File sets are walked ONE IMAGE AT A TIME (train_fusion.py:12-14,156: "To keep memory load down ..."): the rounds are planned on
+common.dataset_entries (identifiers only, nothing read), and a rank walks its share of a round through a volume_queue.LazyQueue
+-- read ahead one payload on a loader thread, adopt, collect the image's points over all views, unload. At most one volume is
+resident and one further host payload is held next to the round's points. --synthetic volumes stay resident.
 """
 import os
 from argparse import ArgumentParser
 import numpy as np
 import torch
 
-from .common import (validate_project_dir, load_hparams, load_dataset, require_audited_hparams,
+from .common import (validate_project_dir, load_hparams, load_dataset, dataset_entries, require_audited_hparams,
                      fusion_weights_path)
 from .predict import best_model_path
 
@@ -59,14 +64,11 @@ def predict_and_map(model, sampler, volume, view, batch_size, n_planes="same+20"
 
 def collect_points(model, sampler, volumes, views, n_classes, batch_size, log, eval_prob=1.0, rng=None,
                    map_method="nearest"):
-    """points [sum voxels, V, K] f32 and targets [sum voxels] u8, both resident on the GPU."""
+    """points [sum voxels, V, K] f32 and targets [sum voxels] u8, both resident on the GPU. `volumes`: any iterable of volumes --
+    a list, or a volume_queue.LazyQueue, which loads each volume when the loop reaches it and unloads it when the loop moves on."""
     from ..interpolation import dice_all
     rng = rng or np.random
     xs, ys = [], []
-    if not volumes:                                        # a rank without an image in this round (fewer images than ranks)
-        dev = model.device
-        return (torch.empty((0, len(views), n_classes), dtype=torch.float32, device=dev),
-                torch.empty((0,), dtype=torch.uint8, device=dev))
     for vol in volumes:
         n = int(np.prod(vol.image.shape[:3]))
         pts = torch.empty((n, len(views), n_classes), dtype=torch.float32, device=vol.image.device)
@@ -78,6 +80,11 @@ def collect_points(model, sampler, volumes, views, n_classes, batch_size, log, e
                 log("  %s view %s: mapped dice %s" % (vol.identifier, np.round(view, 3), np.round(d, 4)))
         xs.append(pts)
         ys.append(vol.labels.reshape(-1).to(torch.uint8))
+        del vol                                            # (before a lazy queue adopts the next one: one volume resident)
+    if not xs:                                             # a rank without an image in this round (fewer images than ranks)
+        dev = model.device
+        return (torch.empty((0, len(views), n_classes), dtype=torch.float32, device=dev),
+                torch.empty((0,), dtype=torch.uint8, device=dev))
     return torch.cat(xs), torch.cat(ys)
 
 
@@ -108,9 +115,14 @@ def run(args):
     if os.path.exists(fpath) and not (args.overwrite or args.continue_training):
         raise OSError("Fusion weights already exist at '%s' (use --overwrite or --continue_training)" % fpath)
     # validation images first; training images are added when there are fewer than 15 (train_fusion.py:283-312)
-    images = load_dataset(hp["val_data"], project_dir, hp, device, args.synthetic, seed=7000)
-    if not args.synthetic and len(images) < 15:
-        extra = load_dataset(hp["train_data"], project_dir, hp, device, 0, seed=0)
+    # file sets: entries (identifiers; nothing is read before the round that needs it); synthetic volumes: resident, as before
+    lazy = not args.synthetic
+    if lazy:
+        images = dataset_entries(hp["val_data"], project_dir, hp, device)
+    else:
+        images = load_dataset(hp["val_data"], project_dir, hp, device, args.synthetic, seed=7000)
+    if lazy and len(images) < 15:
+        extra = dataset_entries(hp["train_data"], project_dir, hp, device)
         if extra:
             need = 15 - len(images)
             idx = rng.choice(np.arange(len(extra)), need, replace=need > len(extra))
@@ -144,6 +156,9 @@ def run(args):
     for r, ids_r in enumerate(rounds):
         log("Set %d/%d: %s" % (r + 1, len(rounds), [images[i].identifier for i in ids_r]))
         mine = [images[i] for i in list(ids_r)[rank::world]]          # the round's images dealt over the ranks
+        if lazy:                                                      # one at a time: read ahead, adopt, collect, unload
+            from ..volume_queue import LazyQueue, Dataset
+            mine = LazyQueue(Dataset(mine, "round_%d" % (r + 1)))
         eval_rng = np.random.RandomState(int(rng.randint(0, 2 ** 31 - 1)) + rank)   # (keeps `rng` in step on every rank)
         X, y = collect_points(unet, sampler, mine, views, n_classes, int(fit["batch_size"]),
                               log, args.eval_prob, eval_rng, map_method=args.map_method)

@@ -121,6 +121,54 @@ def decode_nifti_payload(header, payload, device, labels=False, path="", out=Non
     return out
 
 
+_ENCODE_SOURCES = {torch.float32: ("MPU_ENCODE_F32", 16, "f4"), torch.uint8: ("MPU_ENCODE_U8", 2, "u1"),
+                   torch.int32: ("MPU_ENCODE_I32", 2, "u1"), torch.int64: ("MPU_ENCODE_I64", 2, "u1")}
+
+
+def encode_nifti_payload(t, path="", out=None, bad=None, check=True):
+    """mpu_volume_encode (csrc/volume_encode.hip) on the current stream: a resident tensor of up to four axes [X,Y,Z,C] in C order
+    -> (payload, bad): the bytes np.asfortranarray(t).tobytes(order="F") has for an f32 tensor (NIfTI datatype 16), or for a u8 /
+    i32 / i64 label map stored as u8 (datatype 2), as a flat device tensor of that type, and the int64 [1] counter of the class
+    indices outside [0, 256) (None for f32). check: wait for the counter and raise ValueError naming `path` when it is not zero
+    (check=False: the caller does, after its own copy -- encoded_payload_to_host). out / bad: caller-owned device tensors."""
+    import ctypes as C
+    from . import _lib
+    if t.dtype not in _ENCODE_SOURCES:
+        raise ValueError("%s: no device encode for a %s tensor (f32 images; u8, i32, i64 label maps)" % (path, t.dtype))
+    if not 1 <= t.ndim <= 4 or not t.is_contiguous():
+        raise ValueError("%s: the device encode takes a contiguous tensor of 1 to 4 axes, got shape %r" % (path, tuple(t.shape)))
+    source, _, _ = _ENCODE_SOURCES[t.dtype]
+    image = t.dtype == torch.float32
+    shape4 = tuple(int(s) for s in t.shape) + (1,) * (4 - t.ndim)
+    out = _lib.owned(out, t.numel(), torch.float32 if image else torch.uint8, t.device, "out")
+    bad = None if image else _lib.owned(bad, 1, torch.int64, t.device, "bad")
+    _lib.call("mpu_volume_encode", _lib.ptr(t), getattr(_lib, source), (C.c_int64 * 4)(*shape4), 16 if image else 2,
+              _lib.ptr(out), _lib.ptr(bad), _lib.stream_ptr())
+    if check and bad is not None:
+        check_encoded_labels(bad, path)
+    return out, bad
+
+
+def check_encoded_labels(bad, path):
+    n_bad = int(bad.item())
+    if n_bad:
+        raise ValueError("%s: %d label voxels are outside [0, 256): they cannot be stored as uint8 class indices" % (path, n_bad))
+
+
+def encoded_payload_to_host(t, path=""):
+    """What `mp predict` hands its writer thread for a NIfTI output: (shape, NumPy dtype string, payload) with the payload bytes
+    of `t` (encode_nifti_payload) in a pinned host buffer, as a flat NumPy array. Encode, ONE device-to-host copy and the wait
+    for it happen here, on the calling thread's current stream; nothing of the result touches the device again."""
+    out, bad = encode_nifti_payload(t, path, check=False)
+    host = torch.empty(out.shape, dtype=out.dtype, pin_memory=True)
+    host.copy_(out, non_blocking=True)
+    n_bad = None if bad is None else bad.to("cpu", non_blocking=False)
+    torch.cuda.current_stream(t.device).synchronize()
+    if n_bad is not None:
+        check_encoded_labels(n_bad, path)
+    return tuple(int(s) for s in t.shape), _ENCODE_SOURCES[t.dtype][2], host.numpy()
+
+
 def adopt_payload(payload, device, bg_value="1pct", scaler="RobustScaler", identifier=None, fit_on="device"):
     """HostPayload -> Volume, on the CALLING thread's current stream: upload, decode, then as_volume's background value and
     scaler fit on the resident tensor."""

@@ -226,30 +226,29 @@ def _qform_params(affine):
     return q[1:], qfac, zooms
 
 
-def write_nifti(path, data, affine):
-    """nib.save(nib.Nifti1Image(data, affine), path): sform code 2 (aligned) carrying the affine, qform parameters from
-    the same affine with code 0 (nibabel), no intensity scaling, little endian."""
-    data = np.asarray(data)
-    if data.dtype == np.bool_:
-        data = data.astype(np.uint8)
-    key = data.dtype.newbyteorder("<").str[1:]
+def _nifti_header(shape, dtype, affine):
+    """The 348 header bytes of write_nifti for data of `shape` / `dtype` (validated here, with write_nifti's errors)."""
+    dtype = np.dtype(dtype)
+    key = dtype.newbyteorder("<").str[1:]
     if key not in _CODES:
-        raise NiftiError("cannot store dtype %s in a NIfTI-1 file" % data.dtype)
-    if not 1 <= data.ndim <= 7:
-        raise NiftiError("NIfTI-1 holds 1 to 7 dimensions, got %d" % data.ndim)
+        raise NiftiError("cannot store dtype %s in a NIfTI-1 file" % dtype)
+    shape = tuple(int(d) for d in shape)
+    ndim = len(shape)
+    if not 1 <= ndim <= 7:
+        raise NiftiError("NIfTI-1 holds 1 to 7 dimensions, got %d" % ndim)
     affine = np.asarray(affine, np.float64)
     if affine.shape != (4, 4):
         raise NiftiError("affine must be 4x4")
     (qb, qc, qd), qfac, zooms = _qform_params(affine)
-    dim = [data.ndim] + list(data.shape) + [1] * (7 - data.ndim)
+    dim = [ndim] + list(shape) + [1] * (7 - ndim)
     pixdim = [qfac] + list(zooms) + [1.0] * 4
-    if data.ndim < 3:
-        pixdim[1 + data.ndim:4] = [1.0] * (3 - data.ndim)
+    if ndim < 3:
+        pixdim[1 + ndim:4] = [1.0] * (3 - ndim)
     hdr = bytearray(348)
     struct.pack_into("<i", hdr, 0, 348)
     hdr[38:39] = b"r"
     struct.pack_into("<8h", hdr, 40, *dim)
-    struct.pack_into("<2h", hdr, 70, _CODES[key], data.dtype.itemsize * 8)
+    struct.pack_into("<2h", hdr, 70, _CODES[key], dtype.itemsize * 8)
     struct.pack_into("<8f", hdr, 76, *pixdim)
     struct.pack_into("<3f", hdr, 108, 352.0, float("nan"), float("nan"))
     struct.pack_into("<2h", hdr, 252, 0, 2)
@@ -257,11 +256,36 @@ def write_nifti(path, data, affine):
     struct.pack_into("<3f", hdr, 268, *affine[:3, 3])
     struct.pack_into("<12f", hdr, 280, *affine[:3].ravel())
     hdr[344:348] = b"n+1\0"
-    payload = np.asfortranarray(data.astype(data.dtype.newbyteorder("<"), copy=False)).tobytes(order="F")
-    with (gzip.open(path, "wb", compresslevel=1) if str(path).endswith(".gz") else open(path, "wb")) as f:
-        f.write(bytes(hdr))
+    return bytes(hdr)
+
+
+def write_nifti_payload(path, shape, dtype, affine, payload, compress=None):
+    """The file of nib.save(nib.Nifti1Image(data, affine), path) from its parts: the 348-byte header (sform code 2 (aligned)
+    carrying the affine, qform parameters from the same affine with code 0 (nibabel), no intensity scaling, little endian), the
+    four extension bytes, and `payload`: the data's bytes in Fortran order, little endian, as any bytes-like object (NumPy made
+    them in write_nifti; mpu_volume_encode makes them on the device for `mp predict`). compress: gzip at level 1; None decides
+    by the name (".gz")."""
+    hdr = _nifti_header(shape, dtype, affine)
+    nbytes = int(np.prod([int(d) for d in shape], dtype=np.int64)) * np.dtype(dtype).itemsize
+    view = memoryview(payload)
+    if view.nbytes != nbytes:
+        raise NiftiError("%s: payload of %d bytes for data of shape %r, dtype %s (%d bytes)"
+                         % (path, view.nbytes, tuple(shape), np.dtype(dtype), nbytes))
+    gz = str(path).endswith(".gz") if compress is None else bool(compress)
+    with (gzip.open(path, "wb", compresslevel=1) if gz else open(path, "wb")) as f:
+        f.write(hdr)
         f.write(b"\0\0\0\0")
-        f.write(payload)
+        f.write(view)
+
+
+def write_nifti(path, data, affine):
+    """nib.save(nib.Nifti1Image(data, affine), path): the payload made with NumPy, then write_nifti_payload."""
+    data = np.asarray(data)
+    if data.dtype == np.bool_:
+        data = data.astype(np.uint8)
+    _nifti_header(data.shape, data.dtype, affine)                 # (every error before the conversion pass)
+    payload = np.asfortranarray(data.astype(data.dtype.newbyteorder("<"), copy=False)).tobytes(order="F")
+    write_nifti_payload(path, data.shape, data.dtype, affine, payload)
 
 
 def volume_identifier(path):

@@ -198,7 +198,7 @@ class EagerQueue(BaseQueue):
 class LazyQueue(BaseQueue):
     """Volumes just in time. Iterating yields every entry's volume in list order; the file of the NEXT entry is read by one
     thread meanwhile (file work only), and an entry is unloaded when the loop moves on: at most the current and the next one
-    are loaded."""
+    are loaded. An entry that follows itself in the list is loaded once and kept for both turns."""
 
     def __init__(self, dataset, logger=None, seed=None, **kwargs):
         super().__init__(dataset, logger)
@@ -239,24 +239,35 @@ class LazyQueue(BaseQueue):
             return t
 
         ahead, nxt = start(entries[0]), entries[0]
+        held = None                                             # the entry whose volume the loop holds right now
         try:
             for i, e in enumerate(entries):
-                ahead.join()
+                if ahead is not None:
+                    ahead.join()
                 ahead, nxt = None, None
                 if id(e) in box:
                     raise box.pop(id(e))
                 vol = e.adopt()                                 # (before the next read starts: its payload is dropped here)
-                if i + 1 < len(entries):
+                held = e
+                # a list may name one entry twice in a row (mp train_fusion draws with replacement and repeats images to fill a
+                # round): the volume then stays for the next turn -- a read ahead would put a payload into the entry that the
+                # unload below drops again
+                again = i + 1 < len(entries) and entries[i + 1] is e
+                if i + 1 < len(entries) and not again:
                     ahead, nxt = start(entries[i + 1]), entries[i + 1]
                 try:
                     yield vol
                 finally:
                     del vol
-                    e.unload()
+                    if not again:
+                        e.unload()
+                        held = None
         finally:                                                # (a loop left early: nothing stays loaded, no thread is left)
             if ahead is not None:
                 ahead.join()
                 nxt.unload()
+            if held is not None:
+                held.unload()
 
 
 class LimitationQueue(BaseQueue):
