@@ -353,6 +353,25 @@ int64_t mpu_unet_workspace_probs_offset(const mpu_unet* m, int32_t batch);
  * It is what a training loop accumulates per step without a reduction of its own (reference: the `loss` Keras logs per batch,
  * mpunet/train/trainer.py:246-257). Valid until the next backward pass on that workspace. */
 int64_t mpu_unet_workspace_loss_mean_offset(const mpu_unet* m, int32_t batch);
+/* Test aid (no reference counterpart): the region table of the workspace plan of `batch`, read-only. The workspace is ONE caller-owned
+ * buffer that the plan cuts into regions, each starting at a multiple of 256 bytes, none aliasing another: region i + 1 starts at
+ * offset_i + roundup(bytes_i, 256) and the last one ends at mpu_unet_workspace_bytes(m, batch). Records 0 .. n-1 come in plan order:
+ * first every top-level region (parent = -1), interleaved with the sub-entries (parent = index of the top-level region they lie in,
+ * dotted names) of the regions that have an internal layout. `bytes` is the UNROUNDED length the plan asked for, so
+ * [offset + bytes, next offset) is padding that nothing may write. cls:
+ *   MPU_WS_TENSOR   a tensor with one writer at a time: "act/xin", "act/<role>/<level or block>" (C1 C2 N P dskip; C1b C2b Nb;
+ *                   U1 N1 C2u C3u N2), "probs", "loss_mean", the gradient ping-pong "gA" / "gB", every conv's "dz/<conv>";
+ *   MPU_WS_STATS    "stats": the saved statistics; sub-entries "stats.bn/<bn>" = mean, invstd, scale, shift (4 C floats);
+ *   MPU_WS_SCRATCH  "partial" (sub-entries "partial.rows" and "partial.trailer", the 1024 floats of the fused training head),
+ *                   "partial2", "wpartial" (sub-entries "wpartial.conv/<conv>": each conv's own weight-gradient scratch), "cpartial",
+ *                   "bnacc" (sub-entries "bnacc.fwd/<bn>", "bnacc.bwd/<bn>" and, dtype bf16x3, "bnacc.db/<conv>"), "coeffs", the bf16x3
+ *                   plane triples "x3x0/<conv>", "x3x1/<conv>", "x3dz/<conv>", and with a per-image loss "loss_scratch", "loss_coef".
+ * The "probs" and "loss_mean" records carry the offsets of the two queries above. The query moves no offset and costs the step path
+ * nothing: names and records are built only while a query runs (tests/test_unet_regions_host.py, tests/test_gpu_ws_audit.py). */
+enum { MPU_WS_TENSOR = 0, MPU_WS_STATS = 1, MPU_WS_SCRATCH = 2 };
+int32_t mpu_unet_workspace_num_regions(const mpu_unet* m, int32_t batch);
+int     mpu_unet_workspace_region_info(const mpu_unet* m, int32_t batch, int32_t idx, char* name, int32_t name_cap,
+                                       int64_t* offset, int64_t* bytes, int32_t* cls, int32_t* parent);
 int mpu_unet_forward(const mpu_unet* m, int32_t batch, const float* d_x, const float* d_params,
                      const void* d_packed, float* d_bn_state, void* d_workspace,
                      int32_t training, float* d_out, void* stream);
@@ -746,7 +765,9 @@ int mpu_debug_stamps_read(uint64_t* host_out, int32_t n);
  * Round 4: the NON-convolution launches of the step report too (their inputs and outputs are final when the callback runs):
  *   kind 3  BatchNormalization forward, training (mpunet/models/unet.py:127,144,165,176): in0 = x [B,H,W,C0], out = y
  *           (= gamma * xhat + beta), mask = the 2x2 max-pooled y of an encoder level (or NULL), aux0 / aux1 = batch mean /
- *           1/sqrt(var + eps) (f32 [C0]), w_off / b_off = float offsets of gamma / beta in the flat parameter buffer;
+ *           1/sqrt(var + eps) (f32 [C0]), w_off / b_off = float offsets of gamma / beta in the flat parameter buffer; the launch
+ *           also writes the folded scale and shift, f32 [C0] each, directly behind aux1 (aux0 .. aux0 + 4 C0 floats are the
+ *           BatchNorm's "stats.bn/<index>" entry of mpu_unet_workspace_region_info: mean, invstd, scale, shift);
  *   kind 4  BatchNormalization backward: in0 = dn, in1 = x (the layer's post-ReLU input), out = dz = 1[x > 0] * d(x),
  *           aux0 / aux1 = saved mean / invstd; dgamma / dbeta land at w_off / b_off of the flat GRADIENT buffer;
  *   kind 5  MaxPooling2D backward + skip add: in0 = n (the level's BN output), in1 = dskip, dz = dp (gradient of the pooled

@@ -3,6 +3,7 @@ ctypes binding of libmpunet_hip.so (include/mpunet_hip.h). There is no CPU
 fallback anywhere in this package: if the shared library is missing the import
 of any compute entry point raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -23,6 +24,7 @@ ABI_VERSION = 2                         # mpu_abi_version() this binding was wri
  MPU_LOSS_EXP_LOG) = range(6)
 MPU_LOSS_SPARSE_CE_LOGITS = 6           # mpu_unet_set_loss on a handle with softmax == 0 only; evaluated by mpu_eval_loss_logits
 MPU_GDL_SQUARE, MPU_GDL_SIMPLE, MPU_GDL_UNIFORM = 0, 1, 2
+MPU_WS_TENSOR, MPU_WS_STATS, MPU_WS_SCRATCH = 0, 1, 2       # class of a workspace region (mpu_unet_workspace_region_info)
 # mpu_optimizer_kind / mpu_optimizer_flag
 MPU_OPT_ADAM, MPU_OPT_SGD, MPU_OPT_RMSPROP, MPU_OPT_ADAMAX = range(4)
 MPU_OPT_NESTEROV, MPU_OPT_AMSGRAD, MPU_OPT_CENTERED = 1, 2, 4
@@ -138,6 +140,9 @@ _SIGS = {
                                        C.POINTER(i32), C.POINTER(i32)]),
     "mpu_unet_workspace_probs_offset": (i64, [c_p, i32]),
     "mpu_unet_workspace_loss_mean_offset": (i64, [c_p, i32]),
+    "mpu_unet_workspace_num_regions": (i32, [c_p, i32]),
+    "mpu_unet_workspace_region_info": (C.c_int, [c_p, i32, i32, C.c_char_p, i32, C.POINTER(i64), C.POINTER(i64),
+                                                 C.POINTER(i32), C.POINTER(i32)]),
     "mpu_unet_pack_weights": (C.c_int, [c_p, c_p, c_p, c_p]),
     "mpu_unet_prepare_inference": (C.c_int, [c_p, c_p, c_p, c_p, c_p]),
     "mpu_unet_forward": (C.c_int, [c_p, i32, c_p, c_p, c_p, c_p, c_p, i32, c_p, c_p]),
@@ -276,6 +281,23 @@ def check(status, what):
 
 def call(name, *args):
     check(getattr(load(), name)(*args), name)
+
+
+WsRegion = collections.namedtuple("WsRegion", "index name offset bytes cls parent")
+
+
+def workspace_regions(handle, batch):
+    """The region table of a U-Net handle's workspace plan (mpu_unet_workspace_region_info), in plan order: top-level regions
+    (parent -1) and the sub-entries of those with an internal layout (parent = index of their region)."""
+    lib = load()
+    name = C.create_string_buffer(64)
+    off, nbytes, cls, parent = i64(), i64(), i32(), i32()
+    out = []
+    for i in range(lib.mpu_unet_workspace_num_regions(handle, batch)):
+        check(lib.mpu_unet_workspace_region_info(handle, batch, i, name, 64, C.byref(off), C.byref(nbytes), C.byref(cls),
+                                                 C.byref(parent)), "mpu_unet_workspace_region_info")
+        out.append(WsRegion(i, name.value.decode(), off.value, nbytes.value, cls.value, parent.value))
+    return out
 
 
 def ptr(t):

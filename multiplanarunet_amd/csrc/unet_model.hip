@@ -142,39 +142,64 @@ struct Plan {
                                                     // (launch_split3), read by the grouped bf16 weight-gradient launches at the pass's end
 };
 
-Plan make_plan(const mpu_unet* m, int B) {
+// Read-only export of the plan (mpu_unet_workspace_region_info): one record per take() below, in plan order, and sub-entries (parent =
+// index of the region they lie in) for the regions with an internal layout. make_plan fills names and records ONLY when a query hands it
+// a sink; on the run path the sink is null and a take() is the two additions it always was.
+struct Region { std::string name; long offset, bytes; int cls, parent; };
+const char* const ACT_NAMES[T_ROLES] = {"act/xin", "act/C1", "act/C2", "act/N", "act/P", "act/dskip", "act/C1b", "act/C2b", "act/Nb",
+                                        "act/U1", "act/N1", "act/C2u", "act/C3u", "act/N2"};
+
+Plan make_plan(const mpu_unet* m, int B, std::vector<Region>* sink = nullptr) {
     const int D = m->cfg.depth, esz = m->cfg.dtype == MPU_BF16 ? 2 : 4;
     Plan P; long off = 0;
-    auto take = [&](long bytes) { long o = off; off += (bytes + 255) / 256 * 256; return o; };
-    auto act = [&](int lvl, int C) { return take((long)B * (m->cfg.H >> lvl) * (m->cfg.W >> lvl) * C * esz); };
+    // the ONE place that knows a region's name ("<stem>" or "<stem>/<k>"), unrounded length and class
+    auto note = [&](long o, long bytes, int cls, int parent, const char* stem, int k) {
+        sink->push_back(Region{k < 0 ? std::string(stem) : std::string(stem) + "/" + std::to_string(k), o, bytes, cls, parent});
+    };
+    auto take = [&](long bytes, int cls, const char* stem, int k = -1) {
+        long o = off; off += (bytes + 255) / 256 * 256;
+        if (sink) note(o, bytes, cls, -1, stem, k);
+        return o;
+    };
+    // a part of the region taken last (sub-entries move no offset; `at` in bytes from that region's start)
+    int parent = -1;
+    auto sub = [&](long at, long bytes, const char* stem, int k = -1) {
+        const Region& p = (*sink)[parent];
+        note(p.offset + at, bytes, p.cls, parent, stem, k);
+    };
+    auto act = [&](int role, int k, int lvl, int C) {
+        return take((long)B * (m->cfg.H >> lvl) * (m->cfg.W >> lvl) * C * esz, MPU_WS_TENSOR, ACT_NAMES[role], k);
+    };
     for (long& a : P.act) a = -1;
-    P.act[T(T_XIN)] = act(0, m->cin_pad);
+    P.act[T(T_XIN)] = act(T_XIN, -1, 0, m->cin_pad);
     for (int i = 0; i < D; ++i) {
-        for (int role : {T_C1, T_C2, T_N}) P.act[T(role, i)] = act(i, m->F[i]);
-        P.act[T(T_P, i)] = act(i + 1, m->F[i]); P.act[T(T_DSKIP, i)] = act(i, m->F[i]);
+        for (int role : {T_C1, T_C2, T_N}) P.act[T(role, i)] = act(role, i, i, m->F[i]);
+        P.act[T(T_P, i)] = act(T_P, i, i + 1, m->F[i]); P.act[T(T_DSKIP, i)] = act(T_DSKIP, i, i, m->F[i]);
     }
-    for (int role : {T_C1B, T_C2B, T_NB}) P.act[T(role)] = act(D, m->F[D]);
+    for (int role : {T_C1B, T_C2B, T_NB}) P.act[T(role)] = act(role, -1, D, m->F[D]);
     for (int j = 0; j < D; ++j)
-        for (int role : {T_U1, T_N1, T_C2U, T_C3U, T_N2}) P.act[T(role, j)] = act(D - 1 - j, m->F[D - 1 - j]);
+        for (int role : {T_U1, T_N1, T_C2U, T_C3U, T_N2}) P.act[T(role, j)] = act(role, j, D - 1 - j, m->F[D - 1 - j]);
     const long M0 = (long)B * m->cfg.H * m->cfg.W;
-    P.probs = take(M0 * m->cfg.n_classes * 4);
-    P.loss_mean = take(16);                          // the last backward pass's mean weighted per-pixel loss (one float)
+    P.probs = take(M0 * m->cfg.n_classes * 4, MPU_WS_TENSOR, "probs");
+    P.loss_mean = take(16, MPU_WS_TENSOR, "loss_mean");   // the last backward pass's mean weighted per-pixel loss (one float)
     long gmax = 0;
     for (int l = 0; l <= D; ++l) {
         const long e = (long)B * (m->cfg.H >> l) * (m->cfg.W >> l) * m->F[l];
         if (e > gmax) gmax = e;
     }
-    P.gA = take(gmax * esz); P.gB = take(gmax * esz);   // (every conv has its own dz buffer below: Plan::dz)
+    P.gA = take(gmax * esz, MPU_WS_TENSOR, "gA"); P.gB = take(gmax * esz, MPU_WS_TENSOR, "gB");   // (every conv has its own dz buffer below: Plan::dz)
     P.dz.assign(m->conv.size(), -1);
     for (size_t i = 0; i < m->conv.size(); ++i)
-        if (m->conv[i].mode != CONV1) P.dz[i] = act(m->conv[i].lvl, m->conv[i].Cout);
+        if (m->conv[i].mode != CONV1)
+            P.dz[i] = take((long)B * (m->cfg.H >> m->conv[i].lvl) * (m->cfg.W >> m->conv[i].lvl) * m->conv[i].Cout * esz, MPU_WS_TENSOR, "dz", (int)i);
     long pe = (long)RED_MAX_BLOCKS * 2 * m->cmax;
     const long he = (long)HEAD_BWD_MAX_BLOCKS * (m->head_C * m->cfg.n_classes + m->cfg.n_classes + 1);
     if (he > pe) pe = he;
     if (pe < (4L << 20)) pe = 4L << 20;         // room for the per-tile BN statistics rows of the fused conv epilogues
-    P.partial = take((pe + 1024) * 4);          // (+ 1024 floats the producers are never told about: T of the fused training head)
+    P.partial = take((pe + 1024) * 4, MPU_WS_SCRATCH, "partial");   // (+ 1024 floats the producers are never told about: T of the fused training head)
     P.partial_floats = pe;
-    P.partial2 = take((long)RED_MAX_BLOCKS * m->cmax * 4);
+    if (sink) { parent = (int)sink->size() - 1; sub(0, pe * 4, "partial.rows"); sub(pe * 4, 1024 * 4, "partial.trailer"); }
+    P.partial2 = take((long)RED_MAX_BLOCKS * m->cmax * 4, MPU_WS_SCRATCH, "partial2");
     // Weight-gradient scratch: every layer has its OWN region (K-split partials + bias-gradient partials), because the
     // second-stage reductions are deferred and run batched (flush_wgrad_reduces); sized exactly per layer.
     long we = 0;
@@ -195,14 +220,24 @@ Plan make_plan(const mpu_unet* m, int B) {
                 if (c.mode == CONV1) continue;
                 const long pin = (long)B * (m->cfg.H >> c.lvl_in) * (m->cfg.W >> c.lvl_in);
                 const long pout = (long)B * (m->cfg.H >> c.lvl) * (m->cfg.W >> c.lvl);
-                P.x3x0[i] = take(3 * pin * c.C0 * 2);
-                if (c.in1 >= 0) P.x3x1[i] = take(3 * pin * c.C1 * 2);
-                P.x3dz[i] = take(3 * pout * c.Cout * 2);
+                P.x3x0[i] = take(3 * pin * c.C0 * 2, MPU_WS_SCRATCH, "x3x0", (int)i);
+                if (c.in1 >= 0) P.x3x1[i] = take(3 * pin * c.C1 * 2, MPU_WS_SCRATCH, "x3x1", (int)i);
+                P.x3dz[i] = take(3 * pout * c.Cout * 2, MPU_WS_SCRATCH, "x3dz", (int)i);
             }
         }
     }
-    P.wpartial = take(we * 4);
+    P.wpartial = take(we * 4, MPU_WS_SCRATCH, "wpartial");
     P.wpartial_floats = we;
+    if (sink) {                                  // the per-conv slices (Plan::wscratch): a slice ends where the next conv's begins
+        parent = (int)sink->size() - 1;
+        for (size_t i = 0; i < m->conv.size(); ++i) {
+            if (m->conv[i].mode == CONV1) continue;
+            size_t j = i + 1;
+            while (j < m->conv.size() && m->conv[j].mode == CONV1) ++j;
+            const long end = j < m->conv.size() ? P.wscratch[j] : we;
+            sub(P.wscratch[i] * 4, (end - P.wscratch[i]) * 4, "wpartial.conv", (int)i);
+        }
+    }
     long ce = 0;        // split-K scratch of the forward / data-gradient convs (its own region: the weight gradient of the
     {                   // same layer may run next to the data gradient on the side stream): [ks <= 16][M][Cout] at the deep levels
         for (int l = 0; l <= D; ++l) {
@@ -212,7 +247,7 @@ Plan make_plan(const mpu_unet* m, int B) {
         }
         if (ce > (96L << 20)) ce = 96L << 20;          // 384 MB is plenty: larger layers fill the chip without a K split
     }
-    P.cpartial = take(ce * 4);
+    P.cpartial = take(ce * 4, MPU_WS_SCRATCH, "cpartial");
     P.cpartial_floats = ce;
     {   // accumulators of the fused BatchNorm sums: forward ones first, then the backward ones (each half zeroed by ONE launch)
         long e = 0;
@@ -225,13 +260,24 @@ Plan make_plan(const mpu_unet* m, int B) {
                 if (m->conv[i].mode != CONV1) { P.dbacc[i] = e; e += bn_acc_elems(m->conv[i].Cout); }
         }
         P.bnacc_elems = e;
-        P.bnacc = take(e * 8);
+        P.bnacc = take(e * 8, MPU_WS_SCRATCH, "bnacc");
+        if (sink) {
+            parent = (int)sink->size() - 1;
+            for (size_t i = 0; i < m->bn.size(); ++i) sub(P.bnacc_f[i] * 8, bn_acc_elems(m->bn[i].C) * 8, "bnacc.fwd", (int)i);
+            for (size_t i = 0; i < m->bn.size(); ++i) sub(P.bnacc_b[i] * 8, bn_acc_elems(m->bn[i].C) * 8, "bnacc.bwd", (int)i);
+            for (size_t i = 0; i < P.dbacc.size(); ++i)
+                if (P.dbacc[i] >= 0) sub(P.dbacc[i] * 8, bn_acc_elems(m->conv[i].Cout) * 8, "bnacc.db", (int)i);
+        }
     }
-    P.coeffs = take(3L * m->cmax * 4);
-    P.stats = take(m->n_stats * 4);
+    P.coeffs = take(3L * m->cmax * 4, MPU_WS_SCRATCH, "coeffs");
+    P.stats = take(m->n_stats * 4, MPU_WS_STATS, "stats");
+    if (sink) {                                     // per BatchNorm: mean, invstd, scale, shift (4 C floats, BN::st)
+        parent = (int)sink->size() - 1;
+        for (size_t i = 0; i < m->bn.size(); ++i) sub(m->bn[i].st * 4, 16L * m->bn[i].C, "stats.bn", (int)i);
+    }
     if (loss_is_per_image(m->loss.kind)) {          // (at the end: every other offset is the cross-entropy plan's)
-        P.loss_scratch = take(head_loss_scratch_doubles(B, (long)m->cfg.H * m->cfg.W, m->cfg.n_classes) * 8);
-        P.loss_coef = take((long)B * m->cfg.n_classes * 2 * 4);
+        P.loss_scratch = take(head_loss_scratch_doubles(B, (long)m->cfg.H * m->cfg.W, m->cfg.n_classes) * 8, MPU_WS_SCRATCH, "loss_scratch");
+        P.loss_coef = take((long)B * m->cfg.n_classes * 2 * 4, MPU_WS_SCRATCH, "loss_coef");
     }
     P.total = off;
     return P;
@@ -1018,6 +1064,25 @@ int64_t mpu_unet_workspace_probs_offset(const mpu_unet* m, int32_t batch) {
 int64_t mpu_unet_workspace_loss_mean_offset(const mpu_unet* m, int32_t batch) {
     if (!m || batch < 1) return -1;
     return make_plan(m, batch).loss_mean;
+}
+
+int32_t mpu_unet_workspace_num_regions(const mpu_unet* m, int32_t batch) {
+    if (!m || batch < 1) return 0;
+    std::vector<Region> recs;
+    make_plan(m, batch, &recs);
+    return (int32_t)recs.size();
+}
+int mpu_unet_workspace_region_info(const mpu_unet* m, int32_t batch, int32_t idx, char* name, int32_t name_cap, int64_t* offset,
+                                   int64_t* bytes, int32_t* cls, int32_t* parent) {
+    MPU_REQUIRE(m && name && name_cap > 0 && offset && bytes && cls && parent, "mpu_unet_workspace_region_info: null argument");
+    MPU_REQUIRE(batch >= 1, "mpu_unet_workspace_region_info: batch must be >= 1");
+    std::vector<Region> recs;
+    make_plan(m, batch, &recs);
+    MPU_REQUIRE(idx >= 0 && idx < (int)recs.size(), "mpu_unet_workspace_region_info: index out of range");
+    const Region& r = recs[idx];
+    snprintf(name, name_cap, "%s", r.name.c_str());
+    *offset = r.offset; *bytes = r.bytes; *cls = r.cls; *parent = r.parent;
+    return MPU_OK;
 }
 
 int mpu_unet_pack_weights(const mpu_unet* m, const float* d_params, void* d_packed, void* stream) {

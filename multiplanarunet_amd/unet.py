@@ -484,6 +484,12 @@ class UNet:
                   _lib.ptr(self.bn_state), _lib.ptr(ws), 1 if training else 0, _lib.ptr(out), _lib.stream_ptr())
         return out
 
+    def workspace_regions(self, batch):
+        """The workspace plan of `batch` as a list of records (index, name, offset, bytes, cls, parent): every region the library
+        cuts the workspace into, with byte offset, unrounded byte length and class (_lib.MPU_WS_TENSOR / _STATS / _SCRATCH), and the
+        sub-entries of regions with an internal layout (parent = index of their region). Read-only (a test aid)."""
+        return _lib.workspace_regions(self._h, int(batch))
+
     def _workspace_exact(self, batch):
         # plans for smaller batches fit inside a larger allocation
         return self._workspace(batch)

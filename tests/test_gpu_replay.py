@@ -442,6 +442,12 @@ def test_cfg1_bf16_step_every_non_conv_launch_against_fp64_on_its_own_inputs():
 
 
 # ---- small odd networks: every launch of one train step, kinds 0-7 in ONE pass ------------------------------------------------
+def train_step_launch_counts(D):
+    """Launches a tapped train step of depth D reports, by kind (the one statement of the completeness rule; tests/test_gpu_ws_audit.py
+    counts its intervals with it)."""
+    return {0: 5 * D + 2, 1: 6 * D + 1, 2: 5 * D + 2, 3: 3 * D + 1, 4: 3 * D + 1, 5: D, 6: 1, 7: 1}
+
+
 def _replay_train_step(K, C, depth, cf, B, H, W, dtype, tag=""):
     """One tapped forward_backward (alternating sample weights 1.0 / 0.33, labels zero on about half the pixels), every launch of
     kinds 0-7 checked by _StepChecks on ALL images, the fixed-point units' derived error added where a value comes out of an
@@ -461,7 +467,7 @@ def _replay_train_step(K, C, depth, cf, B, H, W, dtype, tag=""):
             ck.report("%s, FAILED" % tag)
         raise
     D = depth
-    want = {0: 5 * D + 2, 1: 6 * D + 1, 2: 5 * D + 2, 3: 3 * D + 1, 4: 3 * D + 1, 5: D, 6: 1, 7: 1}
+    want = train_step_launch_counts(D)
     seen = {k: ck.count(k) for k in range(8)}
     assert seen == want, (seen, want)
     assert tap.launches == sum(want.values()), (tap.launches, want)
@@ -671,6 +677,15 @@ def _replay_inference(K, C, depth, cf, B, H, W, tag="", seed=21):
     return {"recs": recs, "lines": lines, "worst": worst, "depth": depth}
 
 
+# K, C, depth, cf, B, H, W (the docstrings of the four tests below say what each is for)
+INFER_NETS = {
+    "A": (3, 1, 3, 1, 8, 128, 160),
+    "B": (5, 2, 2, 2, 3, 48, 40),
+    "C": (16, 1, 1, 1, 8, 128, 128),
+    "D": (3, 1, 4, 0.25, 5, 16, 32),
+}
+
+
 def _kinds(res):
     return [r["kind"] for r in res["recs"]]
 
@@ -681,7 +696,7 @@ def test_inference_net_a_ws_fused_pool_and_head_halo_splitk_every_launch_against
     schedules. The schedule switches of test_inference_net_a_under_schedule_switches_subprocess are read from the environment
     (once per process by the library): what each forces is asserted here."""
     import os
-    res = _replay_inference(3, 1, 3, 1, 8, 128, 160, tag="A")
+    res = _replay_inference(*INFER_NETS["A"], tag="A")
     lines, kinds = res["lines"], _kinds(res)
     unfused = os.environ.get("MPU_FUSED_POOL") == "0" and os.environ.get("MPU_FUSED_HEAD") == "0"
     if unfused:
@@ -699,13 +714,13 @@ def test_inference_net_a_ws_fused_pool_and_head_halo_splitk_every_launch_against
 def test_inference_net_b_channel_tails_unfused_head_every_launch_against_fp64():
     """Network B: K 5, 2 input channels, depth 2, cf 2 (90 / 181 / 362 filters: channel tails in every layer and in the scale /
     shift vectors), 3 images of 48 x 40; the head runs as its own kernel (kind 6)."""
-    res = _replay_inference(5, 2, 2, 2, 3, 48, 40, tag="B")
+    res = _replay_inference(*INFER_NETS["B"], tag="B")
     assert _kinds(res).count(6) == 1 and _kinds(res).count(10) == 0, _kinds(res)
 
 
 def test_inference_net_c_wide_fused_head_every_launch_against_fp64():
     """Network C: K 16, depth 1, 8 images of 128 x 128 (1024 tiles: exactly conv_ws's bound): the wide (K <= 16) fused head."""
-    res = _replay_inference(16, 1, 1, 1, 8, 128, 128, tag="C")
+    res = _replay_inference(*INFER_NETS["C"], tag="C")
     assert any(l.split()[1] == "ws" and "head=1" in l for l in res["lines"]), res["lines"]
     assert _kinds(res).count(10) == 1, _kinds(res)
 
@@ -713,7 +728,7 @@ def test_inference_net_c_wide_fused_head_every_launch_against_fp64():
 def test_inference_net_d_tiny_maps_separate_maxpool_every_launch_against_fp64():
     """Network D: K 3, depth 4, cf 0.25, 5 images of 16 x 32: the bottom works on 1 x 2 maps, the last pooling goes 2 x 4 -> 1 x 2,
     and W < 32 below level 0 keeps the layers off the patch kernels and the pooling mostly on the separate kernel (kind 9)."""
-    res = _replay_inference(3, 1, 4, 0.25, 5, 16, 32, tag="D")
+    res = _replay_inference(*INFER_NETS["D"], tag="D")
     assert _kinds(res).count(9) >= 1, _kinds(res)
 
 
