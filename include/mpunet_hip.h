@@ -690,6 +690,32 @@ int mpu_eval_loss(const mpu_loss_config* cfg, const float* d_pred, const uint8_t
 int mpu_eval_loss_logits(const float* d_logits, const uint8_t* d_y, const float* d_sw, int32_t B, int64_t ppi, int32_t n_classes,
                          void* d_scratch, float* d_loss, double* d_acc, void* stream);
 
+/* Connected components of a resident label volume, and the one post-processing step of `mp predict` (--largest_component; no
+ * reference counterpart): for every foreground class keep its largest connected component, send the rest to background.
+ * d_labels u8 [X][Y][Z] in C order (shape = {X, Y, Z}); connectivity 6, 18 or 26 = scipy.ndimage.generate_binary_structure(3, 1 / 2 / 3).
+ * Two voxels are connected when they are neighbours under that structure and carry the same label c with 1 <= c < n_classes;
+ * label 0 and labels >= n_classes join no component and are never rewritten. All classes are labelled in one pass. A component
+ * is named by the linear C-order index of its first voxel (its smallest index), so the result does not depend on scheduling.
+ *
+ * mpu_label_components: d_roots i32 [X * Y * Z]: d_roots[i] = the name of voxel i's component, or -1 where the label joins none.
+ * mpu_keep_largest_components: d_out u8 [X][Y][Z] = d_labels, except that the voxels of a class whose bit is set in class_mask
+ *   (bit c = class c) that lie outside that class's winning component become 0. The winner is the largest component; among
+ *   equally large ones the one with the smallest first index (np.argmax(np.bincount(...)) over ndimage.label's numbering).
+ *   d_out == d_labels (in place) is allowed, any other overlap is MPU_EINVAL. d_report i64 [n_classes][3]: components found,
+ *   voxels kept, voxels removed; the row of an unmasked class reports its components and voxels with removed = 0, row 0 is zero.
+ * Counts, names, the selection and the output are exact integers: two calls give identical bytes.
+ * MPU_EUNSUPPORTED: n_classes outside [1, 16], a dimension < 1, X * Y * Z outside [1, 2^31 - 1] (i32 indices). MPU_EINVAL:
+ * connectivity not in {6, 18, 26}; bit 0 or a bit >= n_classes set in class_mask; a NULL or misaligned pointer (d_roots 4,
+ * d_report 8, d_scratch 16 bytes; the label volumes need no alignment, 16 bytes gives the vector path). Every check precedes the
+ * first HIP call. d_scratch: mpu_components_scratch_bytes(shape) bytes (-1 + mpu_last_error() outside the ranges above), caller-owned,
+ * contents irrelevant before and after; nothing outside it and the named outputs is written. A fixed sequence of launches
+ * (4 / 7) on `stream`, no host synchronisation, no memset: the calls may be captured into a HIP graph. */
+int64_t mpu_components_scratch_bytes(const int64_t shape[3]);
+int mpu_label_components(const uint8_t* d_labels, const int64_t shape[3], int32_t connectivity, int32_t n_classes,
+                         int32_t* d_roots, void* d_scratch, void* stream);
+int mpu_keep_largest_components(const uint8_t* d_labels, const int64_t shape[3], int32_t connectivity, int32_t n_classes,
+                                uint32_t class_mask, uint8_t* d_out, int64_t* d_report, void* d_scratch, void* stream);
+
 /* Measurement aid (bench.py roofline leg; no reference counterpart): when
  * enabled, every MFMA convolution launch is bracketed by HIP events recorded on
  * its own stream. mpu_profile_summary synchronises on them and returns the summed

@@ -180,6 +180,9 @@ _SIGS = {
     "mpu_eval_loss_scratch_bytes": (i64, [i32, i64, i32]),
     "mpu_eval_loss": (C.c_int, [C.POINTER(LossConfig), c_p, c_p, c_p, i32, i64, i32, c_p, c_p, c_p, c_p]),
     "mpu_eval_loss_logits": (C.c_int, [c_p, c_p, c_p, i32, i64, i32, c_p, c_p, c_p, c_p]),
+    "mpu_components_scratch_bytes": (i64, [C.POINTER(i64)]),
+    "mpu_label_components": (C.c_int, [c_p, C.POINTER(i64), i32, i32, c_p, c_p, c_p]),
+    "mpu_keep_largest_components": (C.c_int, [c_p, C.POINTER(i64), i32, i32, C.c_uint32, c_p, c_p, c_p, c_p]),
     "mpu_geometry_set_fast_path": (C.c_int, [i32]),
     "mpu_geometry_check_cell_division": (C.c_int, [C.POINTER(Axis), i64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "mpu_probe_mfma_bf16": (C.c_int, [i32, i32, c_p, C.POINTER(f64), c_p]),

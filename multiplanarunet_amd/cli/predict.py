@@ -6,6 +6,9 @@ Outputs <out_dir>/nii_files/<id>_PRED.nii.gz for NIfTI inputs (mpunet/bin/predic
 Rank 0 writes through ONE prediction_writer.PredictionWriter: the compute thread makes a NIfTI file's payload bytes on the device
 (mpu_volume_encode) and fetches them with one copy; gzip, the write and the rename onto the final name run on the writer's thread
 while the next volume is predicted. The writer is closed before run() returns or raises: every file is complete by then.
+--largest_component (no reference counterpart; postprocess.py): rank 0 filters the fused label map on the device -- per class, only
+the largest connected component stays -- before the Dice evaluation and before the file is made, so that the saved file,
+results.csv and the log describe the same map.
 """
 import os
 from argparse import ArgumentParser
@@ -44,7 +47,38 @@ def get_argparser():
     p.add_argument("--dtype", default="bf16", choices=("bf16", "f32", "bf16x3"),
                    help="bf16 (default, the benchmarked mode), f32 (exact-f32 MFMAs: the parity mode), bf16x3 (f32 storage, three bf16 "
                         "MFMAs per product: f32-grade results at 2.6x the f32 speed)")
+    p.add_argument("--largest_component", action="store_true",
+                   help="keep only the largest connected component of every foreground class of the fused label map (on the device; "
+                        "off by default)")
+    p.add_argument("--cc_connectivity", type=int, default=None, choices=(6, 18, 26),
+                   help="voxel neighbourhood of --largest_component (default 26)")
+    p.add_argument("--cc_classes", type=str, default=None,
+                   help="comma-separated classes --largest_component filters, e.g. 1,3 (default: all foreground classes)")
     return p
+
+
+def component_filter_plan(args, n_classes=None):
+    """The --largest_component flags, checked: None when the filter is off, else (connectivity, classes or None = all foreground
+    classes). ValueError on a combination that cannot be served; with n_classes also on a class outside 1 .. n_classes - 1."""
+    on = bool(getattr(args, "largest_component", False))
+    conn, classes = getattr(args, "cc_connectivity", None), getattr(args, "cc_classes", None)
+    if not on:
+        if conn is not None or classes is not None:
+            raise ValueError("--cc_connectivity / --cc_classes need --largest_component")
+        return None
+    if getattr(args, "no_argmax", False):
+        raise ValueError("--largest_component filters a label map: it cannot be combined with --no_argmax (a probability volume is "
+                         "not filtered)")
+    if classes is not None:
+        try:
+            classes = sorted({int(c) for c in str(classes).split(",") if c.strip() != ""})
+        except ValueError:
+            raise ValueError("--cc_classes: expected comma-separated class numbers, got %r" % (args.cc_classes,))
+        if not classes:
+            raise ValueError("--cc_classes: no class named")
+        if n_classes is not None and (classes[0] < 1 or classes[-1] > int(n_classes) - 1):
+            raise ValueError("--cc_classes %s: classes must be in 1 .. n_classes - 1 = %d" % (args.cc_classes, int(n_classes) - 1))
+    return (26 if conn is None else int(conn)), classes
 
 
 def best_model_path(model_dir):
@@ -80,7 +114,10 @@ def run(args):
     from ..nifti import volume_identifier
     from ..prediction_writer import PredictionWriter
     project_dir = os.path.abspath(args.project_dir)
+    cc = component_filter_plan(args)                      # (flag combinations: refused before anything is looked at)
     validate_project_dir(project_dir)
+    if cc is not None:                                    # the classes against the project's, before anything is loaded or created
+        cc = component_filter_plan(args, load_hparams(project_dir)["build"]["n_classes"])
     for req in ("views.npz", "model"):
         if not os.path.exists(os.path.join(project_dir, req)):
             raise RuntimeError("Invalid project folder: needs train_hparams.yaml, views.npz and model/ (missing %s)" % req)
@@ -164,6 +201,14 @@ def run(args):
                 probs, labels = multi_view_predict(model, v, views, build["dim"], fit["real_space_span"], fm,
                                                    sum_fusion=args.sum_fusion, batch_size=None,
                                                    want_probs=args.no_argmax, per_view_eval=pve, map_method=args.map_method)
+            if rank == 0 and cc is not None:                  # the map that is evaluated, logged and saved from here on
+                from ..postprocess import keep_largest_component
+                labels = labels.contiguous()
+                labels, table = keep_largest_component(labels, build["n_classes"], connectivity=cc[0], classes=cc[1], out=labels,
+                                                       report=True)
+                for c in (cc[1] if cc[1] is not None else range(1, build["n_classes"])):
+                    log("%s: class %d: %d components found, %d voxels removed (largest component, %d-connectivity)"
+                        % (v.identifier, c, int(table[c, 0]), int(table[c, 2]), cc[0]))
             if rank == 0 and args.save_input_files:
                 sub = out_base                            # the volume as it was read: unscaled image, label map
                 os.makedirs(sub, exist_ok=True)
