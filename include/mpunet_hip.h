@@ -716,6 +716,44 @@ int mpu_label_components(const uint8_t* d_labels, const int64_t shape[3], int32_
 int mpu_keep_largest_components(const uint8_t* d_labels, const int64_t shape[3], int32_t connectivity, int32_t n_classes,
                                 uint32_t class_mask, uint8_t* d_out, int64_t* d_report, void* d_scratch, void* stream);
 
+/* Exact Euclidean distance transform of a resident label volume with anisotropic voxel spacing, and the surface-distance table of
+ * `mp predict --surface_metrics` (no reference counterpart; the host route is scipy.ndimage.distance_transform_edt twice per class).
+ * d_labels u8 [X][Y][Z] in C order (shape = {X, Y, Z}), no alignment required; spacing = {sx, sy, sz}, finite and > 0.
+ * The FEATURE voxels (the targets distances are measured to) are chosen by a predicate on the labels:
+ *   MPU_EDT_EQUAL label == value, MPU_EDT_NOT_EQUAL label != value, MPU_EDT_BORDER the border voxels of the mask label == value:
+ *   in the mask with at least one of the six face neighbours outside it, a neighbour outside the volume counting as outside the
+ *   mask (M & ~binary_erosion(M, generate_binary_structure(3, 1)), scipy's border_value = 0; the surface medpy's hd / assd use).
+ *
+ * mpu_edt_squared: d_out f64 [X][Y][Z]: for every voxel p
+ *     d2(p) = min over feature voxels q of fl( fl(wx dx^2) + fl( fl(wy dy^2) + fl(wz dz^2) ) ),   w_a = fl(spacing_a * spacing_a),
+ *   dx, dy, dz the index differences, their squares converted to f64, every fl one rounded f64 operation (no FMA). +inf everywhere
+ *   when no voxel is a feature. The three separable passes each take the true minimum of their line, so the result IS this
+ *   all-pairs minimum, bit for bit. take_root != 0 stores sqrt(d2) instead (the device's sqrt).
+ * mpu_surface_table: d_pred, d_truth u8 label volumes of the same shape; for every class c whose bit is set in class_mask
+ *   (classes 1 .. n_classes - 1; a label >= n_classes belongs to no class), with bP / bT the border voxels of pred == c / truth == c,
+ *   D_T / D_P the squared transforms to bT / bP and the two directed lists D_T[bP], D_P[bT], row c of d_table ([n_classes][8] words
+ *   of 8 bytes) holds
+ *     [0] i64 |bP|   [1] i64 |bT|   [2] i64 how many entries of both lists are <= fl(tolerance * tolerance)
+ *     [3] f64 the maximum of both lists   [4] f64 sum of sqrt over D_T[bP]   [5] f64 sum of sqrt over D_P[bT]
+ *     [6], [7] f64 the two order statistics (of both lists together, SQUARED values) that np.percentile(., 95) (linear method)
+ *     interpolates between: ranks floor(vi) and floor(vi) + 1 with vi = fl((n - 1) * 0.95), n = [0] + [1], both the last element
+ *     when vi >= n - 1. Found by an exact radix select on the bit patterns.
+ *   All rows of classes not asked for (and row 0) are zero. Counts, [3], [6] and [7] are exact; the sums are two-stage f64 sums in a
+ *   fixed order: two calls give identical bytes. An empty border set leaves +inf in the other direction's list; the caller applies its
+ *   convention (surface.py: NaN). HD = sqrt([3]), ASSD = ([4] / [0] + [5] / [1]) / 2, NSD = [2] / ([0] + [1]).
+ * MPU_EUNSUPPORTED: n_classes outside [1, 16], a dimension < 1, X * Y * Z outside [1, 2^31 - 1]. MPU_EINVAL: a spacing or tolerance
+ * that is not finite and > 0; an unknown predicate; value outside 0 .. 255; bit 0 or a bit >= n_classes in class_mask; a NULL or
+ * misaligned pointer (d_out / d_table 8, d_scratch 16 bytes). Every check precedes the first HIP call. d_scratch:
+ * mpu_surface_scratch_bytes(shape) bytes (-1 + mpu_last_error() outside the ranges above; 32 bytes per voxel, 5 per Z line, a header),
+ * caller-owned, contents irrelevant before and after; nothing outside it and the named outputs is written. A fixed sequence of
+ * launches on `stream`, no host synchronisation, no memset. */
+enum { MPU_EDT_EQUAL = 0, MPU_EDT_NOT_EQUAL = 1, MPU_EDT_BORDER = 2 };
+int64_t mpu_surface_scratch_bytes(const int64_t shape[3]);
+int mpu_edt_squared(const uint8_t* d_labels, const int64_t shape[3], const double spacing[3], int32_t predicate, int32_t value,
+                    int32_t take_root, double* d_out, void* d_scratch, void* stream);
+int mpu_surface_table(const uint8_t* d_pred, const uint8_t* d_truth, const int64_t shape[3], const double spacing[3], int32_t n_classes,
+                      uint32_t class_mask, double tolerance, void* d_table, void* d_scratch, void* stream);
+
 /* Measurement aid (bench.py roofline leg; no reference counterpart): when
  * enabled, every MFMA convolution launch is bracketed by HIP events recorded on
  * its own stream. mpu_profile_summary synchronises on them and returns the summed

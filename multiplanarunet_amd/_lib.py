@@ -24,7 +24,8 @@ ABI_VERSION = 2                         # mpu_abi_version() this binding was wri
  MPU_LOSS_EXP_LOG) = range(6)
 MPU_LOSS_SPARSE_CE_LOGITS = 6           # mpu_unet_set_loss on a handle with softmax == 0 only; evaluated by mpu_eval_loss_logits
 MPU_GDL_SQUARE, MPU_GDL_SIMPLE, MPU_GDL_UNIFORM = 0, 1, 2
-MPU_WS_TENSOR, MPU_WS_STATS, MPU_WS_SCRATCH = 0, 1, 2       # class of a workspace region (mpu_unet_workspace_region_info)
+MPU_EDT_EQUAL, MPU_EDT_NOT_EQUAL, MPU_EDT_BORDER = 0, 1, 2   # feature predicate of mpu_edt_squared
+MPU_WS_TENSOR, MPU_WS_STATS, MPU_WS_SCRATCH = 0, 1, 2      # class of a workspace region (mpu_unet_workspace_region_info)
 # mpu_optimizer_kind / mpu_optimizer_flag
 MPU_OPT_ADAM, MPU_OPT_SGD, MPU_OPT_RMSPROP, MPU_OPT_ADAMAX = range(4)
 MPU_OPT_NESTEROV, MPU_OPT_AMSGRAD, MPU_OPT_CENTERED = 1, 2, 4
@@ -183,6 +184,9 @@ _SIGS = {
     "mpu_components_scratch_bytes": (i64, [C.POINTER(i64)]),
     "mpu_label_components": (C.c_int, [c_p, C.POINTER(i64), i32, i32, c_p, c_p, c_p]),
     "mpu_keep_largest_components": (C.c_int, [c_p, C.POINTER(i64), i32, i32, C.c_uint32, c_p, c_p, c_p, c_p]),
+    "mpu_surface_scratch_bytes": (i64, [C.POINTER(i64)]),
+    "mpu_edt_squared": (C.c_int, [c_p, C.POINTER(i64), C.POINTER(f64), i32, i32, i32, c_p, c_p, c_p]),
+    "mpu_surface_table": (C.c_int, [c_p, c_p, C.POINTER(i64), C.POINTER(f64), i32, C.c_uint32, f64, c_p, c_p, c_p]),
     "mpu_geometry_set_fast_path": (C.c_int, [i32]),
     "mpu_geometry_check_cell_division": (C.c_int, [C.POINTER(Axis), i64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "mpu_probe_mfma_bf16": (C.c_int, [i32, i32, c_p, C.POINTER(f64), c_p]),

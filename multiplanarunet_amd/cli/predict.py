@@ -9,6 +9,9 @@ while the next volume is predicted. The writer is closed before run() returns or
 --largest_component (no reference counterpart; postprocess.py): rank 0 filters the fused label map on the device -- per class, only
 the largest connected component stays -- before the Dice evaluation and before the file is made, so that the saved file,
 results.csv and the log describe the same map.
+--surface_metrics [--nsd_tolerance MM] (no reference counterpart; surface.py): rank 0 also evaluates that saved map against the labels
+by surface distances on the device -- HD, HD95, ASSD and the voxel-border NSD per foreground class, with the voxel sizes of the
+affine -- and writes csv/surface_results.csv. No other output changes, and without the flag surface.py is not imported.
 """
 import os
 from argparse import ArgumentParser
@@ -54,7 +57,32 @@ def get_argparser():
                    help="voxel neighbourhood of --largest_component (default 26)")
     p.add_argument("--cc_classes", type=str, default=None,
                    help="comma-separated classes --largest_component filters, e.g. 1,3 (default: all foreground classes)")
+    p.add_argument("--surface_metrics", action="store_true",
+                   help="also evaluate the saved label map against the labels by surface distances, per foreground class: HD, HD95, "
+                        "ASSD and NSD (on the device; csv/surface_results.csv; off by default)")
+    p.add_argument("--nsd_tolerance", type=float, default=None,
+                   help="tolerance of the NSD of --surface_metrics, in the units of the affine (default 1.0)")
     return p
+
+
+def surface_metrics_plan(args):
+    """The --surface_metrics flags, checked: None when the evaluation is off, else the NSD tolerance. ValueError on a combination
+    that cannot be served."""
+    on, tol = bool(getattr(args, "surface_metrics", False)), getattr(args, "nsd_tolerance", None)
+    if not on:
+        if tol is not None:
+            raise ValueError("--nsd_tolerance needs --surface_metrics")
+        return None
+    if getattr(args, "no_eval", False):
+        raise ValueError("--surface_metrics is an evaluation: it cannot be combined with --no_eval")
+    if getattr(args, "no_argmax", False):
+        raise ValueError("--surface_metrics evaluates a label map: it cannot be combined with --no_argmax")
+    if getattr(args, "f", None) and not getattr(args, "l", None):
+        raise ValueError("--surface_metrics needs labels: give -l with -f")
+    tol = 1.0 if tol is None else float(tol)
+    if not (tol > 0.0) or tol == float("inf"):
+        raise ValueError("--nsd_tolerance must be finite and > 0, got %r" % (args.nsd_tolerance,))
+    return tol
 
 
 def component_filter_plan(args, n_classes=None):
@@ -115,6 +143,7 @@ def run(args):
     from ..prediction_writer import PredictionWriter
     project_dir = os.path.abspath(args.project_dir)
     cc = component_filter_plan(args)                      # (flag combinations: refused before anything is looked at)
+    sm = surface_metrics_plan(args)
     validate_project_dir(project_dir)
     if cc is not None:                                    # the classes against the project's, before anything is loaded or created
         cc = component_filter_plan(args, load_hparams(project_dir)["build"]["n_classes"])
@@ -162,7 +191,7 @@ def run(args):
     nii = os.path.join(out_dir, "nii_files")
     if rank == 0:
         os.makedirs(nii, exist_ok=True)
-    results, per_view = {}, {}
+    results, per_view, surface = {}, {}, {}
 
     def plan(item):
         """(write a NIfTI file?, output folder, output file) of a volume or a dataset entry."""
@@ -187,6 +216,8 @@ def run(args):
     try:
         for v in todo:
             as_nii, out_base, dst = plan(v)
+            if sm is not None and v.labels is None:
+                raise ValueError("--surface_metrics needs labels: %s has none" % v.identifier)
             if world > 1:
                 res = D.multi_view_predict_sharded(model, v, views, build["dim"], fit["real_space_span"], fm,
                                                    sum_fusion=args.sum_fusion, batch_size=None, want_probs=args.no_argmax,
@@ -236,6 +267,13 @@ def run(args):
                     d = dice_all(v.labels, labels, n_classes=build["n_classes"], ignore_zero=True)
                     results[v.identifier] = d
                     log("%s: dices %s mean %.4f" % (v.identifier, np.round(d, 4), float(np.nanmean(d))))
+                if sm is not None:                        # the map that was saved against the labels, on the device
+                    from ..surface import surface_distances, voxel_sizes
+                    s = surface_distances(labels.contiguous(), v.labels.reshape(labels.shape).contiguous(), build["n_classes"],
+                                          voxel_sizes(v.affine), tolerance=sm)
+                    surface[v.identifier] = s
+                    log("%s: surface distances (tolerance %g): hd95 %s assd %s nsd %s"
+                        % (v.identifier, sm, np.round(s["hd95"][1:], 4), np.round(s["assd"][1:], 4), np.round(s["nsd"][1:], 4)))
     except BaseException:
         if writer is not None:                            # (this error wins; what was queued is still written, completely)
             try:
@@ -261,6 +299,14 @@ def run(args):
                         view, _, md, mean = rows[i]
                         f.write("%s,%d,%s,%.5f,%s\n" % (k, i, " ".join("%.6g" % x for x in np.asarray(view).ravel()), mean,
                                                         ",".join("%.5f" % x for x in md)))
+    if rank == 0 and surface:                           # one row per (image, foreground class)
+        os.makedirs(os.path.join(out_dir, "csv"), exist_ok=True)
+        with open(os.path.join(out_dir, "csv", "surface_results.csv"), "w") as f:
+            f.write("image,class,hd,hd95,assd,nsd,n_pred_border,n_truth_border\n")
+            for k, s in surface.items():
+                for c in range(1, build["n_classes"]):
+                    f.write("%s,%d,%.6f,%.6f,%.6f,%.6f,%d,%d\n" % (k, c, s["hd"][c], s["hd95"][c], s["assd"][c], s["nsd"][c],
+                                                                   int(s["n_pred_border"][c]), int(s["n_truth_border"][c])))
     return results
 
 
