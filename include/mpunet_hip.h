@@ -853,6 +853,20 @@ int mpu_debug_stamps_read(uint64_t* host_out, int32_t n);
  *           BatchNorm whose output y is;
  *   kind 10 head combine: in0 = the partial logits f32 [2][B*H*W][Cout] of a kind-8 launch, out = probabilities f32
  *           [B,H,W,Cout] (softmax of partial[0] + partial[1] + bh; bh at b_off, Wh at w_off).
+ * Two forms of the train step are NOT taken while a tap is installed -- the fused training head (head_bn_forward /
+ * head_bn_backward / head_bn_bwd_apply) and the pool-backward recompute (launch_maxpool_bwd_bn) -- unless
+ * mpu_unet_set_launch_tap_fused(m, 1) asks for them (default 0: the tapped step is the unfused one, launch for launch). They report as
+ *   kind 3  also for the fused head's BatchNormalization, with out = NULL (its y is not stored): statistics, w_off / b_off as above;
+ *   kind 11 head_bn_forward: in0 = c3 [B,H,W,64] (the BatchNorm's input), out = probabilities f32 [B,H,W,Cout], aux0 / aux1 = batch
+ *           mean / invstd with scale and shift directly behind (as kind 3), w_off / b_off = Wh / bh, conv_index = that BatchNorm;
+ *   kind 12 head_bn_backward + head_bn_bwd_apply, ONE record after both launches: in0 = c3, in1 = probabilities, dz = labels,
+ *           mask = sample weights or NULL, out = dz3 = 1[c3 > 0] * d(c3), aux0 / aux1 = mean / invstd, aux2 = the [3][64]
+ *           BatchNorm-backward coefficients k1 | k2 | k3 the launch wrote, w_off / b_off = Wh / bh (dWh / dbh in the gradient
+ *           buffer; dgamma / dbeta at the gamma / beta offsets of that BatchNorm's kind-3 record), conv_index = that BatchNorm;
+ *   kind 13 launch_maxpool_bwd_bn (both kernels), ONE record: in0 = x (the level's BatchNorm input), in1 = dskip, dz = dp
+ *           [B,H/2,W/2,C0], mask = the level's STORED BatchNorm output n (the launch does not read it: a reference takes its
+ *           arg-max from it), out = dz of the level's second conv, aux0 / aux1 = mean / invstd (+ scale, shift), aux2 = k1 | k2 | k3
+ *           [3][C0], w_off / b_off = gamma / beta offsets (dgamma / dbeta in the gradient buffer), conv_index = that BatchNorm.
  * The callback runs on the calling thread; NULL removes the tap. Not for use under graph capture. */
 typedef struct mpu_launch_info {
     int32_t kind, conv_index, mode, dtype;      /* mode: 0 3x3, 1 up-conv 2x2, 3 1x1 (the LAYER's mode); kinds >= 3: conv_index = BN index */
@@ -860,10 +874,13 @@ typedef struct mpu_launch_info {
     int32_t n_off, n_cnt, relu, _pad;
     const void* in0; const void* in1; const void* dz; const void* mask; const void* out;
     int64_t w_off, b_off;                       /* float offsets of the layer's kernel / bias in the flat buffers */
-    const void* aux0; const void* aux1;         /* kinds 3, 4: batch mean, 1/sqrt(var + eps); kind 8: post_scale, post_shift */
+    const void* aux0; const void* aux1;         /* kinds 3, 4, 11-13: batch mean, 1/sqrt(var + eps); kind 8: post_scale, post_shift */
+    const void* aux2;                           /* kinds 12, 13: the BatchNorm-backward coefficients k1 | k2 | k3, f32 [3][C0] (else NULL) */
 } mpu_launch_info;
 typedef void (*mpu_launch_tap_fn)(void* user, const mpu_launch_info* info);
 int mpu_unet_set_launch_tap(mpu_unet* m, mpu_launch_tap_fn fn, void* user);
+/* on != 0: a tapped train step also takes the fused training head and the pool-backward recompute (kinds 11-13); 0 (default): not. */
+int mpu_unet_set_launch_tap_fused(mpu_unet* m, int32_t on);
 
 #ifdef __cplusplus
 }

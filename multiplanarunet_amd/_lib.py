@@ -201,6 +201,7 @@ _SIGS = {
     "mpu_env_describe": (i64, [C.c_char_p, i64]),
     "mpu_conv2d_wgrad": (C.c_int, [i32, i32, c_p, i32, c_p, i32, c_p, i32, i32, i32, i32, c_p, c_p, c_p]),
     "mpu_unet_set_launch_tap": (C.c_int, [c_p, c_p, c_p]),
+    "mpu_unet_set_launch_tap_fused": (C.c_int, [c_p, i32]),
     "mpu_unet_adam_pack": (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, c_p, f64, f64, f64, f64, c_p, c_p]),
     "mpu_debug_stamps_read": (C.c_int, [c_p, i32]),
     "mpu_debug_tail_events": (C.c_int, [i32, c_p]),
@@ -228,7 +229,7 @@ class LaunchInfo(C.Structure):
                 ("B", i32), ("H", i32), ("W", i32), ("C0", i32), ("C1", i32), ("Cout", i32),
                 ("n_off", i32), ("n_cnt", i32), ("relu", i32), ("_pad", i32),
                 ("in0", c_p), ("in1", c_p), ("dz", c_p), ("mask", c_p), ("out", c_p),
-                ("w_off", i64), ("b_off", i64), ("aux0", c_p), ("aux1", c_p)]
+                ("w_off", i64), ("b_off", i64), ("aux0", c_p), ("aux1", c_p), ("aux2", c_p)]
 
 
 LAUNCH_TAP_FN = C.CFUNCTYPE(None, c_p, C.POINTER(LaunchInfo))

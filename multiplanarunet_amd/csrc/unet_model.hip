@@ -65,6 +65,7 @@ struct mpu_unet {
     int cmax = 0;
     int x3 = 0;                              // MPU_F32X3: cfg.dtype holds MPU_F32 (storage, every elementwise kernel), the MFMA kernels split
     mpu_launch_tap_fn tap = nullptr; void* tap_user = nullptr;      // test aid: mpu_unet_set_launch_tap
+    int tap_fused = 0;                       // ... mpu_unet_set_launch_tap_fused: the fused head and the pool recompute also run under a tap
     // Round 6: the last training forward ran the fused head (head_bn_forward: no post-BatchNorm tensor of the last block exists);
     // its backward pass must take head_bn_backward / head_bn_bwd_apply. A backward pass belongs to exactly one training forward.
     mutable int head_fused_fwd = 0;
@@ -317,17 +318,17 @@ double conv_flops(const Run& r, const Conv& c) {
     return 2.0 * (double)r.pix(c.lvl) * taps * c.lCin * c.lCout;
 }
 
-// test aid: report a launch to the tap -- the one writer of mpu_launch_info (kinds 0-2: the convs; 3-7: see tap_aux)
+// test aid: report a launch to the tap -- the one writer of mpu_launch_info (kinds 0-2: the convs; 3-7, 11-13: see tap_aux)
 void tap(const Run& r, int kind, int index, int mode, int lvl, int C0, int C1, int Cout, const void* in0, const void* in1, const void* dz,
          const void* mask, const void* out, long w_off, long b_off, int n_off = 0, int n_cnt = 0, int relu = 0,
-         const void* aux0 = nullptr, const void* aux1 = nullptr) {
+         const void* aux0 = nullptr, const void* aux1 = nullptr, const void* aux2 = nullptr) {
     if (!r.m->tap) return;
     mpu_launch_info li{};
     li.kind = kind; li.conv_index = index; li.mode = mode; li.dtype = r.m->cfg.dtype;
     li.B = r.B; li.H = r.m->cfg.H >> lvl; li.W = r.m->cfg.W >> lvl; li.C0 = C0; li.C1 = C1; li.Cout = Cout;
     li.n_off = n_off; li.n_cnt = n_cnt; li.relu = relu;
     li.in0 = in0; li.in1 = in1; li.dz = dz; li.mask = mask; li.out = out; li.w_off = w_off; li.b_off = b_off;
-    li.aux0 = aux0; li.aux1 = aux1;
+    li.aux0 = aux0; li.aux1 = aux1; li.aux2 = aux2;
     r.m->tap(r.m->tap_user, &li);
 }
 // ... a conv launch of layer `c` (kind 0 forward, 1 data gradient, 2 weight gradient) at level `lvl`
@@ -335,10 +336,11 @@ void tap_conv(const Run& r, int kind, const Conv& c, int lvl, int C0, int C1, co
               const void* mask, const void* out, int n_off, int n_cnt, int relu) {
     tap(r, kind, (int)(&c - &r.m->conv[0]), c.mode, lvl, C0, C1, c.Cout, in0, in1, dz, mask, out, c.w, c.b, n_off, n_cnt, relu);
 }
-// ... a non-convolution launch (kinds 3-7 of mpu_launch_info)
+// ... a non-convolution launch (kinds 3-7 and 11-13 of mpu_launch_info)
 void tap_aux(const Run& r, int kind, int index, int lvl, int C0, int Cout, const void* in0, const void* in1, const void* dz,
-             const void* mask, const void* out, long w_off, long b_off, const void* aux0 = nullptr, const void* aux1 = nullptr) {
-    tap(r, kind, index, 0, lvl, C0, 0, Cout, in0, in1, dz, mask, out, w_off, b_off, 0, 0, 0, aux0, aux1);
+             const void* mask, const void* out, long w_off, long b_off, const void* aux0 = nullptr, const void* aux1 = nullptr,
+             const void* aux2 = nullptr) {
+    tap(r, kind, index, 0, lvl, C0, 0, Cout, in0, in1, dz, mask, out, w_off, b_off, 0, 0, 0, aux0, aux1, aux2);
 }
 
 // fused head request of the last conv (inference): weights, class count, scratch for the partial logits [2][M][k]
@@ -508,11 +510,11 @@ int conv_wgrad(Run& r, size_t ci_) {
 }
 
 // Round 6: the training step's head as the three head_bn_* passes (unet_ops.hip): bf16 or bf16x3 (accumulator mode), a 64-channel last block
-// feeding a softmax head -- or a linear one that trains (MPU_LOSS_SPARSE_CE_LOGITS attached) --, no launch tap (the replay tests check
-// the unfused kernels launch by launch)
+// feeding a softmax head -- or a linear one that trains (MPU_LOSS_SPARSE_CE_LOGITS attached). Under a launch tap only where
+// mpu_unet_set_launch_tap_fused asked for it (kinds 11 and 12; by default the replay tests see the unfused kernels launch by launch)
 bool head_train_fused_wanted(const Run& r) {
     const mpu_unet* m = r.m;
-    return env(ENV_HEAD_TRAIN_FUSED) != 0 && r.acc_mode && !m->tap && (m->cfg.softmax || m->loss.kind == MPU_LOSS_SPARSE_CE_LOGITS) &&
+    return env(ENV_HEAD_TRAIN_FUSED) != 0 && r.acc_mode && (!m->tap || m->tap_fused) && (m->cfg.softmax || m->loss.kind == MPU_LOSS_SPARSE_CE_LOGITS) &&
            m->F[0] == 64 && head_train_fused_shape_ok(m->cfg.dtype, m->head_C, m->cfg.n_classes);
 }
 
@@ -653,6 +655,9 @@ int run_forward(const Run& r, const float* d_x, int training, float* d_out) {
         RC(launch_head_bn_forward(m->cfg.dtype, r.t(b.x), M0, r.acc_f(b), BN_ACC_F, r.params + b.g, r.params + b.b, r.state + b.mm,
                                   r.state + b.mv, r.stat(b, 0), r.stat(b, 1), r.stat(b, 2), r.stat(b, 3), BN_EPS, BN_MOM,
                                   m->cfg.n_classes, r.params + m->head_w, m->cfg.n_classes, r.params + m->head_b, m->cfg.softmax, out, r.st));
+        const int bi = (int)(&b - &m->bn[0]);
+        tap_aux(r, 11, bi, 0, b.C, m->cfg.n_classes, r.t(b.x), nullptr, nullptr, nullptr, out, m->head_w, m->head_b, r.stat(b, 0), r.stat(b, 1));
+        tap_aux(r, 3, bi, 0, b.C, b.C, r.t(b.x), nullptr, nullptr, nullptr, nullptr, b.g, b.b, r.stat(b, 0), r.stat(b, 1));   // (its y is not stored)
     } else {
         const void* prev = r.t(m->conv.back().in0);
         RC(launch_head_forward(m->cfg.dtype, prev, M0, m->head_C, m->cfg.n_classes, r.params + m->head_w,
@@ -720,6 +725,8 @@ int run_backward(Run& r, const uint8_t* d_y, const float* d_sw, float* d_loss, c
                                     m->cfg.n_classes, tsum, r.grads + m->head_b, r.params + b.g, r.params + b.b, r.stat(b, 0), r.stat(b, 1),
                                     r.grads + b.g, r.grads + b.b, r.grads + m->head_w, (float*)r.at(P.coeffs),
                                     r.dz(b.conv), r.st, hl));
+        tap_aux(r, 12, (int)(&b - &m->bn[0]), 0, b.C, m->cfg.n_classes, c3, r.at(P.probs), d_y, d_sw, r.dz(b.conv), m->head_w, m->head_b,
+                r.stat(b, 0), r.stat(b, 1), r.at(P.coeffs));
     } else {
         RC(launch_head_backward(dt, last, (const float*)r.at(P.probs), d_y, d_sw, M0, (long)m->cfg.H * m->cfg.W,
                                 m->head_C, m->cfg.n_classes, r.params + m->head_w, m->cfg.n_classes,
@@ -769,17 +776,20 @@ int run_backward(Run& r, const uint8_t* d_y, const float* d_sw, float* d_loss, c
         const void* dskip = r.t(T(T_DSKIP, i));
         int bwd_rows = 0;
         // Round 6 (MPU_POOL_BWD_RECOMPUTE): neither the post-BatchNorm tensor n is read nor the summed gradient written -- both
-        // passes recompute them from the BatchNorm input, the skip gradient and the pooled gradient (same bits; no launch tap:
-        // the replay tests check the two-tensor kernels)
+        // passes recompute them from the BatchNorm input, the skip gradient and the pooled gradient (same bits; under a launch tap
+        // only where mpu_unet_set_launch_tap_fused asked for it: kind 13 -- by default the replay tests see the two-tensor kernels)
         int fused_pool = 0;
         // (from 4 M elements: measured R6av at configs[1] -- levels 0 / 1 / 2 50.0 -> 41.6, 28.7 -> 26.4, 17.2 -> 16.2 us; the
         //  2 M elements x 512 channels of level 3 lose 1.6 us to the all-channel coefficient prologue of the second pass)
-        if (env(ENV_POOL_BWD_RECOMPUTE) != 0 && r.acc_mode && !(eb.C & 63) && !m->tap &&
+        if (env(ENV_POOL_BWD_RECOMPUTE) != 0 && r.acc_mode && !(eb.C & 63) && (!m->tap || m->tap_fused) &&
             r.pix(i) * eb.C >= (env(ENV_POOL_BWD_RECOMPUTE) > 1 ? 0L : 4L << 20)) {
             fused_pool = launch_maxpool_bwd_bn(dt, dskip, gB, r.B, H, W, eb.C, r.t(eb.x), r.stat(eb, 0), r.stat(eb, 1),
                                                r.stat(eb, 2), r.stat(eb, 3), r.params + eb.g, r.grads + eb.g, r.grads + eb.b,
                                                (float*)r.at(P.coeffs), r.dz(i2), r.acc_b(eb), BN_ACC_B, r.st);
             if (fused_pool < 0) return fused_pool;
+            if (fused_pool)
+                tap_aux(r, 13, c2.bn, i, eb.C, eb.C, r.t(eb.x), dskip, gB, r.t(eb.y), r.dz(i2), eb.g, eb.b, r.stat(eb, 0), r.stat(eb, 1),
+                        r.at(P.coeffs));
         }
         if (!fused_pool) {
             RC(launch_maxpool_bwd_add_stats(dt, r.t(eb.y), dskip, gB, r.B, H, W, eb.C, gA, r.t(eb.x),
@@ -1030,6 +1040,12 @@ int mpu_unet_set_loss(mpu_unet* m, const mpu_loss_config* cfg) {
 int mpu_unet_set_launch_tap(mpu_unet* m, mpu_launch_tap_fn fn, void* user) {
     MPU_REQUIRE(m, "mpu_unet_set_launch_tap: null model");
     m->tap = fn; m->tap_user = user;
+    return MPU_OK;
+}
+
+int mpu_unet_set_launch_tap_fused(mpu_unet* m, int32_t on) {
+    MPU_REQUIRE(m, "mpu_unet_set_launch_tap_fused: null model");
+    m->tap_fused = on != 0;
     return MPU_OK;
 }
 

@@ -1611,8 +1611,8 @@ int launch_head_backward(int dtype, const void* n, const float* probs, const uin
 // labels, c3 -> T, dbh, loss: partial rows, summed by head_bwd_finalize_kernel) and head_bn_bwd_apply (recomputes dzh and dn2 per
 // pixel, forms the BatchNorm-backward coefficients from T / dbh / Wh in its prologue, writes dz3; its first workgroup writes
 // dgamma, dbeta and dWh). dn2 stays in fp32 registers (the unfused path rounds it to bf16 in HBM), n2 in dWh is unrounded:
-// both closer to the fp64 oracle. Switch MPU_HEAD_TRAIN_FUSED=0; not taken while a launch tap is installed (the replay tests
-// check the unfused kernels launch by launch).
+// both closer to the fp64 oracle. Switch MPU_HEAD_TRAIN_FUSED=0; while a launch tap is installed, taken only after
+// mpu_unet_set_launch_tap_fused(m, 1) (the replay tests then check these three passes as kinds 11 and 12, else the unfused kernels).
 // ------------------------------------------------------------------------------------------------------------------- //
 template <typename T, int K>
 __global__ __launch_bounds__(256) void head_bn_forward_kernel(const T* __restrict__ x, long M, const long long* __restrict__ acc,

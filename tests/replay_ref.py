@@ -190,3 +190,129 @@ def acc_stats_error(M, mean, inv):
     d_mean = acc_sum_error(M, BN_ACC_F[0]) / M
     d_var = acc_sum_error(M, BN_ACC_F[1]) / M + 2.0 * np.abs(mean) * d_mean
     return d_mean, 0.5 * np.asarray(inv, np.float64) ** 3 * d_var
+
+
+# ---- the fused forms of the train step (kinds 11-13 of mpu_launch_info; mpu_unet_set_launch_tap_fused) ----------------------------
+# The fused training head (head_bn_forward / head_bn_backward / head_bn_bwd_apply) and the pool-backward recompute
+# (maxpool_bwd_add_kernel<T, true, true> + maxpool_bwd_bn_fold_kernel) store no post-BatchNorm tensor: they RECOMPUTE it per element
+# as rounding(fmaf(x, scale, shift)) and the replay recomputes that recomputation from the device coefficients, in emulated float32.
+U_F32 = 2.0 ** -24
+
+
+def storage_round(a, bf16):
+    """fp64 -> float32 -> the storage format (bf16, or f32 as it is) -> fp64: the rounding of a kernel's store of an f32 register."""
+    t = torch.as_tensor(a, dtype=torch.float64).to(torch.float32)
+    return (t.to(torch.bfloat16) if bf16 else t).to(torch.float64)
+
+
+def fma32(a, b, c):
+    """fmaf(a, b, c) of float32 values held in fp64: the product of two 24-bit significands is exact in fp64, so
+    float32(float64(a) * float64(b) + float64(c)) differs from the single rounding of the exact a * b + c only where the fp64 sum
+    itself lands on a float32 tie (tests/test_replay_bounds_host.py compares with exact rational arithmetic)."""
+    a, b, c = (torch.as_tensor(v, dtype=torch.float64) for v in (a, b, c))
+    return (a * b + c).to(torch.float32).to(torch.float64)
+
+
+def head_bn_n2(x, scale, shift, bf16):
+    """The post-BatchNorm tensor the fused head never stores: storage-rounding(fmaf(x, scale, shift)) with the DEVICE scale / shift."""
+    return storage_round(fma32(x, scale, shift), bf16)
+
+
+def loss_grad_at_logits(p, y, w, loss):
+    """d sum(loss(p, y, w)) / d logits from GIVEN probabilities p [..., K] (the device's, fp64): the gradient g at p by autograd of
+    `loss` (oracle/unet_ref.py keras_sparse_ce), then the softmax backward at p, p * (g - sum_k p_k g_k). Also the loss itself."""
+    p = torch.as_tensor(p, dtype=torch.float64).detach().clone().requires_grad_(True)
+    l = loss(p, y, w.to(p.dtype))
+    l.sum().backward()
+    g, pd = p.grad, p.detach()
+    return pd * (g - (pd * g).sum(-1, keepdim=True)), l.detach()
+
+
+def bn_bwd_coeffs(dgamma, dbeta, M, mean, inv, gamma):
+    """(k1, k2, k3) of dz = [x > 0] * (k1 * dn + k2 * x + k3): bn_bwd's affine form, from the sums given."""
+    k1 = gamma * inv
+    k2 = -k1 * (dgamma / M) * inv
+    return k1, k2, -k1 * (dbeta / M) - k2 * mean
+
+
+def bn_bwd_coeff_bounds(tol, extra, dgamma, dbeta, M, mean, inv, gamma):
+    """Per-channel bounds of (k1, k2, k3) that follow from the bounds of the sums they are made of: dgamma and dbeta are held to
+    e_g = tol * max |dgamma| + extra and e_b = tol * max |dbeta| + extra (extra: the accumulator units' share), and
+    k2_c = -(k1_c inv_c / M) dgamma_c, k3_c = -(k1_c / M) dbeta_c - k2_c mean_c are linear in them:
+      k1: tol * max |k1| (no sum in it);  k2_c: |k1_c inv_c| / M * e_g;  k3_c: |k1_c| / M * e_b + |mean_c| * (the bound of k2_c).
+    A fraction of the VECTOR's maximum would not follow: a channel with a large 1/std turns the same error of dgamma into a larger
+    error of k2. (The f32 rounding of a coefficient, 2^-24 of itself, is below each of these: e_g >= tol |dgamma_c|.)"""
+    k1 = (gamma * inv).abs()
+    e_g, e_b = tol * dgamma.abs().max() + extra, tol * dbeta.abs().max() + extra
+    b2 = k1 * inv.abs() / M * e_g
+    return tol * k1.max() * torch.ones_like(k1), b2, k1 / M * e_b + mean.abs() * b2
+
+
+def bn_bwd_sums(dn, x, mean, inv):
+    """(dgamma, dbeta) of bn_bwd over the pixels given (additive over chunks of pixels)."""
+    red = tuple(range(x.dim() - 1))
+    return (dn * ((x - mean) * inv)).sum(red), dn.sum(red)
+
+
+def bn_bwd_apply(dn, x, mean, inv, gamma, dgamma, dbeta, M):
+    """dz of bn_bwd (plain form) from sums over ALL M pixels, on the pixels given."""
+    dxx = gamma * inv * (dn - dbeta / M - (x - mean) * inv * dgamma / M)
+    return torch.where(x > 0, dxx, torch.zeros((), dtype=x.dtype))
+
+
+def head_bn_bwd_sums(c3, dzh, Wh, mean, inv, gamma, beta):
+    """The fused head's backward sums over the pixels given (additive over chunks): dn2 = dzh @ Wh^T (nothing rounded), then
+    (dn2, dgamma, dbeta, dWh) with dWh = (gamma * xhat + beta)^T dzh -- the post-BatchNorm value BEFORE its storage rounding."""
+    Cn, K = Wh.shape
+    dn2 = dzh @ Wh.T
+    dgamma, dbeta = bn_bwd_sums(dn2, c3, mean, inv)
+    n2 = gamma * ((c3 - mean) * inv) + beta
+    return dn2, dgamma, dbeta, n2.reshape(-1, Cn).T @ dzh.reshape(-1, K)
+
+
+def pool_bwd_bn_elementwise(dn, x, k1, k2, k3, bf16):
+    """What maxpool_bwd_bn_fold_kernel stores, from the DEVICE coefficients in emulated float32, and the bound of every element:
+    ref = [x > 0] * storage-rounding(fmaf(k1, dn, fmaf(k2, x, k3))); |got - ref| <= u |ref| + 4 * 2^-24 (|k1 dn| + |k2 x| + |k3|) --
+    one storage rounding (u = 2^-8 / 2^-24) plus the float32 roundings of the two fmas."""
+    dn, x = torch.as_tensor(dn, dtype=torch.float64), torch.as_tensor(x, dtype=torch.float64)
+    k1, k2, k3 = (torch.as_tensor(k, dtype=torch.float64) for k in (k1, k2, k3))
+    ref = torch.where(x > 0, storage_round(fma32(k1, dn, fma32(k2, x, k3)), bf16), torch.zeros((), dtype=torch.float64))
+    lim = (U_BF16 if bf16 else U_F32) * ref.abs() + 4 * U_F32 * ((k1 * dn).abs() + (k2 * x).abs() + k3.abs())
+    return ref, lim
+
+
+def one_value_bound(ref, terms, bf16=None):
+    """Per-element bound of a BatchNorm over ONE value per channel (M = 1: x = mean, the output is beta and the gradient zero, both
+    far below the terms of the affine the kernels evaluate, so no fraction of a maximum applies): 4 * 2^-24 * `terms` -- the f32
+    roundings of the coefficients and of the fma(s); terms = |x scale| + |shift| forward, |k1 dn| + |k2 x| + |k3| backward -- plus,
+    bf16 given, one storage rounding u |ref| of the result (forward). NumPy arrays."""
+    lim = 4 * U_F32 * np.abs(terms)
+    return lim if bf16 is None else lim + (U_BF16 if bf16 else U_F32) * np.abs(ref)
+
+
+def tied_windows(n):
+    """(windows whose maximum is attained more than once, windows) of the 2 x 2 pooling of NumPy [B, H, W, C]."""
+    B, H, W, Cn = n.shape
+    win = n.reshape(B, H // 2, 2, W // 2, 2, Cn).transpose(0, 1, 3, 5, 2, 4).reshape(-1, 4)
+    return int(((win == win.max(-1, keepdims=True)).sum(-1) > 1).sum()), int(win.shape[0])
+
+
+class ChannelErr:
+    """conv_bound_ratios over a tensor seen one chunk of pixels at a time: add(got, ref) per chunk, ratios(tol) at the end."""
+
+    def __init__(self):
+        self.err = self.cmax = None
+
+    def add(self, got, ref):
+        got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64)
+        Cn = ref.shape[-1]
+        e, c = np.abs(got - ref).reshape(-1, Cn).max(0), np.abs(ref).reshape(-1, Cn).max(0)
+        self.err = e if self.err is None else np.maximum(self.err, e)
+        self.cmax = c if self.cmax is None else np.maximum(self.cmax, c)
+
+    def ratios(self, tol):
+        tmax = float(self.cmax.max()) + 1e-300
+        lim = np.where(self.cmax >= DEAD * tmax, tol * self.cmax, tol * DEAD * tmax)
+        ratio = self.err / lim
+        c = int(ratio.argmax())
+        return float(self.err.max() / tmax), float(ratio[c]), c

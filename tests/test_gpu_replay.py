@@ -29,9 +29,12 @@ all images, in bf16 and bf16x3 (T1 also f32):
   T4  K 8, depth 1, cf 1, 2 x 32 x 32                                 the widest head that trains (TRAIN_MAX_CLASSES)
 Completeness from the depth D: forward convs and weight gradients 5 D + 2 (each conv index once), data gradients 6 D + 1, BatchNorm
 forward and backward 3 D + 1 each, pool backward D, head forward and head backward one each (D = 4: 22 / 25 / 22 / 13 / 13 / 4 / 1 / 1).
-Two forms of the step switch themselves off under a tap and are therefore NOT replayed: the fused training head (unet_model.hip:
-!m->tap in head_train_fused_wanted) and the pool-backward recompute. Both are pinned bit for bit against the unfused kernels in
-tests/test_gpu_unet.py.
+Two forms of the step switch themselves off under a tap -- the fused training head (unet_model.hip: head_train_fused_wanted) and the
+pool-backward recompute --, so the replays above see the unfused kernels; tests/test_gpu_unet.py pins the two forms against those bit
+for bit. mpu_unet_set_launch_tap_fused(m, 1) keeps them on under the tap: they are the DEFAULT of the benchmarked bf16 step, and
+_replay_fused_step (FUSED_CASES H1-H5, P1-P4) replays them as kinds 11 (head_bn_forward), 12 (head_bn_backward + head_bn_bwd_apply)
+and 13 (both pool-recompute kernels) against fp64 -- at the ragged last pixel group of both storages, in the second grid-stride round
+of each head pass, at every channel width of the pool passes and on a 7-workgroup grid (bounds: _StepChecks._kind11 / 12 / 13).
 
 The INFERENCE forward (run_forward_infer: every `mp predict`, the benchmark's predict leg) is replayed the same way
 (_replay_inference, four small networks and three schedule switches). Its launches report as kind 0 (conv without a BatchNorm),
@@ -162,7 +165,7 @@ class _StepChecks:
       kind 7 head backward                   dn: out; dWh / dbh: reduce, after the pass
     worst[...] holds the worst error of each family as a FRACTION OF ITS BOUND."""
 
-    def __init__(self, m, B, dtype, imgs, kinds=range(8), derived=True):
+    def __init__(self, m, B, dtype, imgs, kinds=range(8), derived=True, by_image=False, elem_imgs=None):
         import replay_ref as R
         from oracle import unet_ref as U
         self.R, self.U, self.m, self.B, self.dtype = R, U, m, B, dtype
@@ -179,10 +182,18 @@ class _StepChecks:
         self.head_out, self.x3_per_channel = None, 0.0
         self.acc_mode = derived and dtype in ("bf16", "bf16x3") and _env_on("MPU_BN_ATOMIC") and _env_on("MPU_BN_FOLD") and _env_on("MPU_FUSED_BN_STATS")
         self.seen = []                                         # (kind, conv_index) of every launch checked
+        self.all_kinds = {}                                    # kind -> launches reported, checked or not
         self.worst = {}
         self.later = []                                        # (what, index, offset into grads, reference, tol, absolute extra)
         self.stats_plain = 0.0                                 # worst statistics error as a fraction of the bound WITHOUT the derived term
         self._bad = None
+        # kinds 11-13 (the fused forms, mpu_unet_set_launch_tap_fused): evaluated image by image; by_image: kind 3 as well (the large
+        # cases); elem_imgs: the images whose ELEMENTS are compared (default: all) -- every reduction runs over the whole batch
+        self.by_image = by_image
+        self.elem_imgs = list(range(B)) if elem_imgs is None else sorted(set(elem_imgs))
+        self.bn_offs = {}                                      # BatchNorm index -> (gamma, beta) offsets, from its kind-3 record
+        self.ties = []                                         # per kind-13 launch: (level's C, tied windows, windows)
+        self.fused_probs = None                                # the kind-11 launch's output
 
     # -- device tensors as stored: bf16, or f32 (dtypes "bf16x3", "f32"); fp64 on the host, exact
     def rows(self, ptr, shape, imgs=None):
@@ -202,6 +213,7 @@ class _StepChecks:
             self.hold(what + ", per channel", li, e_c, 1.0, ("channel %d" % c, tuple(ref.shape), note))
 
     def check(self, li):
+        self.all_kinds[li.kind] = self.all_kinds.get(li.kind, 0) + 1
         if li.kind not in self.kinds:
             return
         self.seen.append((li.kind, li.conv_index))
@@ -273,10 +285,34 @@ class _StepChecks:
 
     def _kind3(self, li):
         R, B, H, W, Cc = self.R, self.B, li.H, li.W, li.C0
-        x = self.rows(li.in0, (B, H, W, Cc)); got = self.rows(li.out, (B, H, W, Cc)).numpy()
+        self.bn_offs[li.conv_index] = (li.w_off, li.b_off)
+        if self.by_image and B * H * W > 1:
+            return self._kind3_by_image(li)
+        x = self.rows(li.in0, (B, H, W, Cc))
         mean_d, inv_d = _d2h_f32(self.hip, li.aux0, (Cc,)), _d2h_f32(self.hip, li.aux1, (Cc,))
         g, bt = self.params[li.w_off:li.w_off + Cc], self.params[li.b_off:li.b_off + Cc]
         mu, inv = (t.numpy() for t in R.bn_stats(x))
+        self._hold_stats(li, mean_d, inv_d, mu, inv)
+        if not li.out:                                   # the fused head's BatchNorm: its y is not stored (kind 11 checks what is made of it)
+            return
+        got = self.rows(li.out, (B, H, W, Cc)).numpy()
+        ref = R.bn_out(x, torch.tensor(mean_d), torch.tensor(inv_d), torch.tensor(g), torch.tensor(bt)).numpy()
+        if B * H * W == 1:
+            # ONE value per channel (the bottom of a one-image 2 x 2 case): x = mean, the output is beta, and the terms of the affine
+            # the kernel evaluates, x * scale + (beta - mean * scale) with scale = gamma / sqrt(eps) ~ 30 gamma, cancel entirely: a
+            # fraction of the channel's maximum has nothing to do with its error. Per element instead: one storage rounding of the
+            # result plus the f32 roundings of shift and of the fma, 4 * 2^-24 * (|x scale_d| + |shift_d|) (cf. kind 13's bound)
+            _m, _i, scale_d, shift_d = self._stats4(li)
+            lim = R.one_value_bound(ref, np.abs(x.numpy() * scale_d) + np.abs(shift_d), self.bf16)
+            self.hold("BatchNorm forward over one value", li, float((np.abs(got - ref) / (lim + 1e-300)).max()), 1.0)
+            return
+        self.hold_tensor("BatchNorm forward", li, got, ref, self.tol["out"], True)
+        if li.mask:                                      # pooled = 2x2 max of the STORED (rounded) output, exactly
+            pg = self.rows(li.mask, (B, H // 2, W // 2, Cc)).numpy()
+            self.hold("BatchNorm forward, pooled output", li, float(not np.array_equal(pg, R.pool2x2(got))), 0.5)
+
+    def _hold_stats(self, li, mean_d, inv_d, mu, inv):
+        R, B, H, W, Cc = self.R, self.B, li.H, li.W, li.C0
         # statistics, on their own line: tol of the vector maximum, plus -- accumulator mode, a multiple of 64 channels (the folded
         # kernel's shapes) -- the error derived from the units: d_mean = adds * 2^-25 / M, d_inv = inv^3 / 2 * (adds * 2^-17 / M + ...)
         M = B * H * W
@@ -287,11 +323,37 @@ class _StepChecks:
             c = int((err / (plain + extra + 1e-300)).argmax())
             self.hold("BatchNorm statistics", li, err[c], plain + (extra if np.ndim(extra) == 0 else extra[c]),
                       (what, "channel %d" % c, "M = %d" % M, "error %.3g" % err[c], "tol * max %.3g" % plain))
-        ref = R.bn_out(x, torch.tensor(mean_d), torch.tensor(inv_d), torch.tensor(g), torch.tensor(bt)).numpy()
-        self.hold_tensor("BatchNorm forward", li, got, ref, self.tol["out"], True)
-        if li.mask:                                      # pooled = 2x2 max of the STORED (rounded) output, exactly
-            pg = self.rows(li.mask, (B, H // 2, W // 2, Cc)).numpy()
-            self.hold("BatchNorm forward, pooled output", li, float(not np.array_equal(pg, R.pool2x2(got))), 0.5)
+
+    def hold_channels(self, what, li, ce, tol, shape):
+        e_t, e_c, c = ce.ratios(tol)
+        self.hold(what, li, e_t, tol, ("tensor-wise", shape))
+        self.hold(what + ", per channel", li, e_c, 1.0, ("channel %d" % c, shape))
+
+    def _kind3_by_image(self, li):
+        """Kind 3 with every reference evaluated one image at a time (the same formulas and bounds; sums over the whole batch)."""
+        R, B, H, W, Cc = self.R, self.B, li.H, li.W, li.C0
+        shape = (B, H, W, Cc)
+        mean_d, inv_d = _d2h_f32(self.hip, li.aux0, (Cc,)), _d2h_f32(self.hip, li.aux1, (Cc,))
+        g, bt = (torch.tensor(self.params[o:o + Cc]) for o in (li.w_off, li.b_off))
+        s = torch.zeros(Cc, dtype=torch.float64); ss = torch.zeros(Cc, dtype=torch.float64)
+        for i in range(B):
+            x = self.rows(li.in0, shape, [i]).reshape(-1, Cc)
+            s += x.sum(0); ss += (x * x).sum(0)
+        M = B * H * W
+        mu = s / M
+        inv = 1.0 / torch.sqrt((ss / M - mu * mu).clamp_min(0.0) + R.BN_EPS)          # (replay_ref.bn_stats, from the sums)
+        self._hold_stats(li, mean_d, inv_d, mu.numpy(), inv.numpy())
+        if not li.out:
+            return
+        ce, pooled_bad = R.ChannelErr(), 0
+        for i in self.elem_imgs:
+            x = self.rows(li.in0, shape, [i]); got = self.rows(li.out, shape, [i]).numpy()
+            ce.add(got, R.bn_out(x, torch.tensor(mean_d), torch.tensor(inv_d), g, bt).numpy())
+            if li.mask:
+                pooled_bad += int(not np.array_equal(self.rows(li.mask, (B, H // 2, W // 2, Cc), [i]).numpy(), R.pool2x2(got)))
+        self.hold_channels("BatchNorm forward", li, ce, self.tol["out"], shape)
+        if li.mask:
+            self.hold("BatchNorm forward, pooled output", li, float(pooled_bad), 0.5)
 
     def _kind4(self, li):
         R, B, H, W, Cc = self.R, self.B, li.H, li.W, li.C0
@@ -303,6 +365,14 @@ class _StepChecks:
         extra = R.acc_sum_error(B * H * W, R.BN_ACC_B) if self.acc_mode and not Cc & 63 else 0.0
         self.later.append(("dgamma", li.conv_index, li.w_off, dgamma.numpy(), self.tol["reduce"], extra))
         self.later.append(("dbeta", li.conv_index, li.b_off, dbeta.numpy(), self.tol["reduce"], extra))
+        if B * H * W == 1:
+            # ONE value per channel (the bottom of a one-image 2 x 2 case): xhat = 0 (up to the statistics' own rounding) and
+            # dn - dbeta / M = 0, the gradient is zero and there is no maximum to take a fraction of. What the f32 evaluation of k1 * dn + k2 * x + k3 (k3 = -k1 * dn,
+            # rounded) may leave: 4 * 2^-24 * (|k1 dn| + |k2 x| + |k3|), the f32 term of kind 13's per-element bound
+            k1, k2, k3 = R.bn_bwd_coeffs(dgamma, dbeta, 1, torch.tensor(mean_d), torch.tensor(inv_d), torch.tensor(g))
+            lim = R.one_value_bound(None, ((k1 * dn).abs() + (k2 * x).abs() + k3.abs()).numpy())
+            self.hold("BatchNorm backward over one value (zero gradient)", li, float((np.abs(got - ref.numpy()) / (lim + 1e-300)).max()), 1.0)
+            return
         self.hold_tensor("BatchNorm backward", li, got, ref.numpy(), self.tol["out"], True)
 
     def _kind5(self, li):
@@ -337,6 +407,147 @@ class _StepChecks:
         got = self.rows(li.out, (B, H, W, Cc)).numpy()
         self.hold_tensor("head backward", li, got, dn.numpy(), self.tol["out"], False)
 
+    def _stats4(self, li):
+        """mean, invstd, scale, shift of a launch's BatchNorm: f32 [4][C0] from aux0 on (aux1 = the second row)."""
+        Cc = li.C0
+        assert li.aux0 and li.aux1 == li.aux0 + 4 * Cc, ("mean and invstd are not neighbours", li.kind, li.conv_index)
+        return _d2h_f32(self.hip, li.aux0, (4, Cc))
+
+    def _kind11(self, li):
+        """head_bn_forward: probabilities against head_fwd(n2, Wh, bh) in fp64, n2 = storage-rounding(fmaf(c3, scale_d, shift_d)) in
+        emulated float32 from the DEVICE scale and shift: probs (2e-5 absolute, kind 6's bound). The folded scale / shift themselves
+        against gamma * inv_d and beta - mean_d * scale_d: 4 * 2^-24 of the terms (a rounded product; a product and a difference)."""
+        R, B, H, W, Cc, K = self.R, self.B, li.H, li.W, li.C0, li.Cout
+        mean_d, inv_d, scale_d, shift_d = self._stats4(li)
+        g_off, b_off = self.m_bn_offsets(li.conv_index)
+        g, bt = self.params[g_off:g_off + Cc], self.params[b_off:b_off + Cc]
+        e = max(float((np.abs(scale_d - g * inv_d) / (4 * R.U_F32 * np.abs(g * inv_d) + 1e-300)).max()),
+                float((np.abs(shift_d - (bt - mean_d * scale_d)) / (4 * R.U_F32 * (np.abs(bt) + np.abs(mean_d * scale_d)) + 1e-300)).max()))
+        self.hold("fused head: folded scale / shift", li, e, 1.0)
+        got = _d2h_f32(self.hip, li.out, (B, H, W, K))
+        self.head_out = self.fused_probs = got
+        Wh, bh = self._head(li)
+        e = 0.0
+        for i in self.elem_imgs:
+            n2 = R.head_bn_n2(self.rows(li.in0, (B, H, W, Cc), [i]), torch.tensor(scale_d), torch.tensor(shift_d), self.bf16)
+            e = max(e, float(np.abs(got[i:i + 1] - R.head_fwd(n2, Wh, bh).numpy()).max()))
+        self.hold("fused head forward (absolute)", li, e, self.tol["probs"])
+
+    def m_bn_offsets(self, bn_index):
+        """(gamma, beta) float offsets of BatchNorm `bn_index` (creation order = the library's index)."""
+        names = [n[:-len("/gamma")] for n in self.m._keras_order() if n.endswith("/gamma")]
+        return self.m._tensors[names[bn_index] + "/gamma"][1], self.m._tensors[names[bn_index] + "/beta"][1]
+
+    def _kind12(self, li):
+        """head_bn_backward + head_bn_bwd_apply. In fp64 with nothing rounded in between: dzh from the DEVICE probabilities, labels
+        and weights (keras_sparse_ce), dn2 = dzh @ Wh^T, BatchNorm backward of dn2 at c3 with the device statistics -> dz3, dgamma,
+        dbeta; dWh = (gamma * xhat + beta)^T dzh, dbh = sum dzh. dz3: out, tensor-wise and per channel; the four reductions: reduce
+        (no accumulator term: fp32 partial rows), after the pass; aux2 against fp64 k1, k2, k3: reduce of each vector's maximum."""
+        R, B, H, W, Cc, K = self.R, self.B, li.H, li.W, li.C0, li.Cout
+        shape, M = (B, H, W, Cc), B * H * W
+        st = self._stats4(li)
+        mean_d, inv_d = torch.tensor(st[0]), torch.tensor(st[1])
+        g_off, b_off = self.bn_offs[li.conv_index]             # (of that BatchNorm's kind-3 record)
+        g, bt = torch.tensor(self.params[g_off:g_off + Cc]), torch.tensor(self.params[b_off:b_off + Cc])
+        probs = torch.tensor(_d2h_f32(self.hip, li.in1, (B, H, W, K)))
+        yy = torch.tensor(_d2h_u8(self.hip, li.dz, (B, H, W)).astype(np.int64))
+        ww = torch.tensor(_d2h_f32(self.hip, li.mask, (B,)) if li.mask else np.ones(B))
+        dzh, _l = R.loss_grad_at_logits(probs, yy, ww, self.U.keras_sparse_ce)
+        Wh, _bh = self._head(li)
+        dgamma = torch.zeros(Cc, dtype=torch.float64); dbeta = torch.zeros(Cc, dtype=torch.float64)
+        dWh = torch.zeros(Cc, K, dtype=torch.float64)
+        for i in range(B):
+            _dn2, dg_i, db_i, dW_i = R.head_bn_bwd_sums(self.rows(li.in0, shape, [i]), dzh[i:i + 1], Wh, mean_d, inv_d, g, bt)
+            dgamma += dg_i; dbeta += db_i; dWh += dW_i
+        self.later.append(("fused head dWh", -1, li.w_off, dWh.numpy().ravel(), self.tol["reduce"], 0.0))
+        self.later.append(("fused head dbh", -1, li.b_off, dzh.sum((0, 1, 2)).numpy(), self.tol["reduce"], 0.0))
+        self.later.append(("fused head dgamma", li.conv_index, g_off, dgamma.numpy(), self.tol["reduce"], 0.0))
+        self.later.append(("fused head dbeta", li.conv_index, b_off, dbeta.numpy(), self.tol["reduce"], 0.0))
+        coef = _d2h_f32(self.hip, li.aux2, (3, Cc))
+        for name, dev, ref in zip(("k1", "k2", "k3"), coef, R.bn_bwd_coeffs(dgamma, dbeta, M, mean_d, inv_d, g)):
+            ref = ref.numpy()
+            self.hold("fused head coefficients", li, np.abs(dev - ref).max(), self.tol["reduce"] * np.abs(ref).max(), name)
+        ce = R.ChannelErr()
+        for i in self.elem_imgs:
+            x = self.rows(li.in0, shape, [i])
+            ce.add(self.rows(li.out, shape, [i]).numpy(), R.bn_bwd_apply(dzh[i:i + 1] @ Wh.T, x, mean_d, inv_d, g, dgamma, dbeta, M).numpy())
+        self.hold_channels("fused head backward (dz3)", li, ce, self.tol["out"], shape)
+
+    def _kind13(self, li):
+        """launch_maxpool_bwd_bn (both kernels). (a) dn = storage-rounding(dskip + dp routed to the first maximum of the STORED n),
+        BatchNorm backward of it in fp64 with the device statistics: dgamma, dbeta (after the pass) and k1, k2, k3 to reduce + the
+        accumulator units' half unit per add (the coefficients: that bound of the sums carried through their formula, per channel:
+        replay_ref.bn_bwd_coeff_bounds); its dz to out, tensor-wise and per channel. (b) EVERY output element against
+        [x > 0] * storage-rounding(fmaf(k1_d, dn, fmaf(k2_d, x, k3_d))) from the DEVICE coefficients in emulated float32, to
+        u |ref| + 4 * 2^-24 (|k1 dn| + |k2 x| + |k3|). (c) the stored n has windows whose maximum is attained more than once.
+        Why the coefficients are not held to reduce (+ the units' term) of each VECTOR's maximum: on the 7-workgroup grid of case P3 the
+        CPU emulation of a correct kernel (tests/test_replay_bounds_host.py) puts k2 at 2.25 (C 64) and 1.09 (C 128) of that bound in
+        f32 storage while dgamma and dbeta are within theirs -- k2_c = -(k1_c inv_c / M) dgamma_c scales the error of dgamma with the
+        channel's 1/std. The per-channel bound follows from the sums' bounds (0.32 / 0.21 there) and is tighter for small 1/std.
+        What this replay cannot see: in f32 storage (bf16x3) the windows that tie are windows of several ZEROS of the post-ReLU input,
+        where dz is masked and xhat is equal, so routing to the last maximum gives the same dz, dgamma and dbeta -- no power against
+        a wrong tie-break there. In bf16 storage different positive x round to the same n and a wrong tie-break fails (b)."""
+        R, B, H, W, Cc = self.R, self.B, li.H, li.W, li.C0
+        shape, pshape, M = (B, H, W, Cc), (B, H // 2, W // 2, Cc), B * H * W
+        st = self._stats4(li)
+        mean_d, inv_d = torch.tensor(st[0]), torch.tensor(st[1])
+        g = torch.tensor(self.params[li.w_off:li.w_off + Cc])
+        coef = _d2h_f32(self.hip, li.aux2, (3, Cc))
+
+        def dn_of(i):
+            n_ = self.rows(li.mask, shape, [i]).numpy()
+            dn = R.storage_round(R.pool_bwd_skip(n_, self.rows(li.in1, shape, [i]).numpy(), self.rows(li.dz, pshape, [i]).numpy()), self.bf16)
+            return n_, dn, self.rows(li.in0, shape, [i])
+
+        dgamma = torch.zeros(Cc, dtype=torch.float64); dbeta = torch.zeros(Cc, dtype=torch.float64)
+        tied = windows = 0
+        for i in range(B):
+            n_, dn, x = dn_of(i)
+            dg_i, db_i = R.bn_bwd_sums(dn, x, mean_d, inv_d)
+            dgamma += dg_i; dbeta += db_i
+            t_i, w_i = R.tied_windows(n_)
+            tied += t_i; windows += w_i
+        self.ties.append((Cc, tied, windows))
+        print("replay (kind 13, C=%d %dx%d): %d of %d windows (%.3g) attain their maximum more than once" % (Cc, H, W, tied, windows, tied / windows))
+        self.hold("pool recompute: tied windows present", li, float(tied == 0), 0.5)
+        extra = R.acc_sum_error(M, R.BN_ACC_B)
+        self.later.append(("pool recompute dgamma", li.conv_index, li.w_off, dgamma.numpy(), self.tol["reduce"], extra))
+        self.later.append(("pool recompute dbeta", li.conv_index, li.b_off, dbeta.numpy(), self.tol["reduce"], extra))
+        lims = R.bn_bwd_coeff_bounds(self.tol["reduce"], extra, dgamma, dbeta, M, mean_d, inv_d, g)
+        for name, dev, ref, lim in zip(("k1", "k2", "k3"), coef, R.bn_bwd_coeffs(dgamma, dbeta, M, mean_d, inv_d, g), lims):
+            self.hold("pool recompute coefficients", li, float((np.abs(dev - ref.numpy()) / (lim.numpy() + 1e-300)).max()), 1.0, name)
+        ce, e = R.ChannelErr(), 0.0
+        for i in self.elem_imgs:
+            _n, dn, x = dn_of(i)
+            got = self.rows(li.out, shape, [i])
+            ce.add(got.numpy(), R.bn_bwd_apply(dn, x, mean_d, inv_d, g, dgamma, dbeta, M).numpy())
+            ref, lim = R.pool_bwd_bn_elementwise(dn, x, *coef, self.bf16)
+            e = max(e, float(((got - ref).abs() / (lim + 1e-300)).max()))
+        self.hold("pool recompute, per element (device coefficients)", li, e, 1.0, shape)
+        self.hold_channels("pool recompute backward (dz)", li, ce, self.tol["out"], shape)
+
+    def check_returned(self, probs, loss, y, sw):
+        """After the pass: the probabilities forward_backward returned are the kind-11 launch's output bit for bit, and the per-pixel
+        loss it returned (written by head_bn_backward) against fp64 Keras sparse cross-entropy of the DEVICE probabilities: per image
+        sum and the logged mean (UNet.loss_mean) to 1e-5 relative (tests/test_gpu_losses.py's bound for this loss), and, beside
+        that, every pixel to 1e-5 |L| + w * (K + 2) * 2^-24 (the f32 sum of K clipped probabilities and the two logarithms'
+        difference, each rounded once)."""
+        p = self.fused_probs
+        B, K = self.B, p.shape[-1]
+        assert np.array_equal(probs.cpu().numpy().astype(np.float64).reshape(p.shape), p), "returned probabilities are not the kind-11 output"
+        ww = torch.tensor(np.asarray(sw, np.float64))
+        yy = torch.tensor(np.asarray(y).reshape(p.shape[:-1]).astype(np.int64))
+        want = self.U.keras_sparse_ce(torch.tensor(p), yy, ww).numpy().reshape(B, -1)
+        got = loss.cpu().numpy().astype(np.float64).reshape(B, -1)
+        lim = 1e-5 * np.abs(want) + ww.numpy()[:, None] * (K + 2) * self.R.U_F32
+        r_pix = float((np.abs(got - want) / lim).max())
+        r_img = float((np.abs(got.sum(1) - want.sum(1)) / (1e-5 * np.abs(want.sum(1)))).max())
+        r_mean = abs(float(self.m.loss_mean().item()) - want.mean()) / (1e-5 * abs(want.mean()))
+        for what, r in (("fused head loss, per pixel", r_pix), ("fused head loss, per image (1e-5 relative)", r_img),
+                        ("fused head loss, mean (1e-5 relative)", r_mean)):
+            self.worst[what] = max(self.worst.get(what, 0.0), r)
+        assert r_pix <= 1.0 and r_img <= 1.0 and r_mean <= 1.0, ("loss against fp64 of the device probabilities", r_pix, r_img, r_mean)
+
     def count(self, kind):
         return sum(k == kind for k, _i in self.seen)
 
@@ -360,12 +571,12 @@ class _StepChecks:
                  if self.dtype == "bf16x3" else ""))
 
 
-def _run_tapped_step(m, x, y, sw, checks, schedule_log=False):
+def _run_tapped_step(m, x, y, sw, checks, schedule_log=False, want_loss=False):
     from replay_tap import tapped
     with tapped(m, checks.check, schedule_log=schedule_log) as tap:
-        probs, _loss = m.forward_backward(x, y, sw)
+        probs, loss = m.forward_backward(x, y, sw)
         torch.cuda.synchronize()
-    return tap, probs
+    return (tap, probs, loss) if want_loss else (tap, probs)
 
 
 def _replay_conv_launches(B, dim, cf, dtype="bf16", tol_act=1.2e-2, tol_w=2e-3):
@@ -442,10 +653,16 @@ def test_cfg1_bf16_step_every_non_conv_launch_against_fp64_on_its_own_inputs():
 
 
 # ---- small odd networks: every launch of one train step, kinds 0-7 in ONE pass ------------------------------------------------
-def train_step_launch_counts(D):
+def train_step_launch_counts(D, fused_levels=None, fused_head=True):
     """Launches a tapped train step of depth D reports, by kind (the one statement of the completeness rule; tests/test_gpu_ws_audit.py
-    counts its intervals with it)."""
-    return {0: 5 * D + 2, 1: 6 * D + 1, 2: 5 * D + 2, 3: 3 * D + 1, 4: 3 * D + 1, 5: D, 6: 1, 7: 1}
+    counts its intervals with it). fused_levels = n: the step with the fused forms on (mpu_unet_set_launch_tap_fused) -- the fused
+    head (kind 11 + the kind-3 record of its BatchNorm, then kind 12 in place of kinds 7 and 4; fused_head=False: a network whose
+    last block has no 64 filters keeps kinds 6, 7 and that kind 4) and n encoder levels on the pool-backward recompute (kind 13 in
+    place of kinds 5 and 4)."""
+    if fused_levels is None:
+        return {0: 5 * D + 2, 1: 6 * D + 1, 2: 5 * D + 2, 3: 3 * D + 1, 4: 3 * D + 1, 5: D, 6: 1, 7: 1}
+    n, h = fused_levels, int(bool(fused_head))
+    return {0: 5 * D + 2, 1: 6 * D + 1, 2: 5 * D + 2, 3: 3 * D + 1, 4: 3 * D + 1 - n - h, 5: D - n, 6: 1 - h, 7: 1 - h, 11: h, 12: h, 13: n}
 
 
 def _replay_train_step(K, C, depth, cf, B, H, W, dtype, tag=""):
@@ -540,6 +757,115 @@ def test_train_net_t3_under_schedule_switches_subprocess(switches):
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_gpu_replay.py"), "-x", "-q", "-s", "-k",
                         "test_train_step_small_odd_networks_every_launch_against_fp64 and T3 and bf16 and not bf16x3"],
                        env=dict(os.environ, **switches), capture_output=True, text=True, cwd=os.path.dirname(here))
+    print("\n".join(l for l in r.stdout.splitlines() if l.startswith("replay (")))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "1 passed" in r.stdout, r.stdout[-2000:]
+
+
+# ---- the fused forms of the step: fused training head (kinds 11, 12) and pool-backward recompute (kind 13) ----------------------
+# K, C, depth, cf, B, H, W; dtypes; the environment the case needs (a fresh interpreter where it differs from this one's: the library
+# reads a switch once per process); n = encoder levels the recompute takes; large = kinds 3, 11, 12, 13 only, image by image
+FUSED_CASES = {
+    "H1": ((3, 1, 1, 1, 3, 10, 14), ("bf16", "bf16x3"), {}, 0, False),     # M = 420 = 4 mod 8 = 4 mod 16: ragged last pixel group in both storages
+    "H2": ((2, 1, 1, 1, 1, 2, 2), ("bf16", "bf16x3"), {}, 0, False),       # M = 4 < G: one partial group; statistics over 4 values
+    "H3": ((8, 1, 1, 1, 2, 18, 22), ("bf16",), {}, 0, False),              # M = 792 = 8 mod 16; the widest head of bf16 storage
+    "H3w": ((4, 1, 1, 1, 2, 18, 22), ("bf16x3",), {}, 0, False),           # ... and of f32 storage (16 K = 64 lanes), ragged there
+    "H4": ((3, 1, 1, 1, 5, 232, 232), ("bf16",), {}, 1, True),             # M = 269 120 > 262 144: second, ragged round of head_bn_backward
+    "H5": ((3, 1, 1, 1, 5, 460, 460), ("bf16",), {}, 1, True),             # M = 1 058 000 > 1 048 576: second round of forward and apply
+    "P1": (TRAIN_NETS["T3"], ("bf16", "bf16x3"), {"MPU_POOL_BWD_RECOMPUTE": "2"}, 2, False),
+    "P2": (TRAIN_NETS["T2"], ("bf16", "bf16x3"), {"MPU_POOL_BWD_RECOMPUTE": "2"}, 3, False),   # level 0 (C 32) refused: kinds 5 and 4 remain
+                                                                           # (32 filters at level 0: no fused head either -- kinds 6, 7)
+    "P3": (TRAIN_NETS["T3"], ("bf16", "bf16x3"), {"MPU_POOL_BWD_RECOMPUTE": "2", "MPU_POOL_BWD_BLOCKS": "7"}, 2, False),
+    "P4": ((3, 1, 5, 1, 1, 32, 32), ("bf16x3",), {"MPU_POOL_BWD_RECOMPUTE": "2"}, 5, True),    # C 1024 in f32 storage: cpr = 256; level 4 on 2 x 2 maps
+}
+
+
+def _replay_fused_step(case, dtype):
+    """One tapped forward_backward with mpu_unet_set_launch_tap_fused on. Small cases: every launch of every kind on all images;
+    large ones: kinds 3, 11, 12, 13 with the references evaluated image by image. Completeness: train_step_launch_counts(D, n) by
+    kind, the kind-4 launches are exactly the BatchNorms neither the fused head nor a recomputed level took over, `head=1` on one
+    forward and one backward line of the schedule log (none where the last block has no 64 filters: P2), `pool=1` on n backward lines; every kind-13 launch saw tied windows."""
+    import time
+    from multiplanarunet_amd import _lib
+    t0 = time.time()
+    (K, C, depth, cf, B, H, W), _dtypes, _env, n, large = FUSED_CASES[case]
+    # H5 measured 15.3 s with every element of all five images compared: its reductions stay on the whole batch, its per-element
+    # comparisons run on the first, the middle and the last image -- pixels 846 400 .. 1 058 000, which hold the second grid round
+    # of head_bn_forward and head_bn_bwd_apply (from pixel 1 048 576 on)
+    elem_imgs = (0, B // 2, B - 1) if case == "H5" else None
+    head = int(int(64 * cf) == 64)                           # the fused head needs 64 filters in the last block (unet_model.hip)
+    m, x, y, sw = _train_case(K, C, depth, cf, B, H, W, dtype, seed=51, sw_period=2)
+    _lib.call("mpu_unet_set_launch_tap_fused", m._h, 1)
+    ck = _StepChecks(m, B, dtype, range(B), kinds=(3, 11, 12, 13) if large else tuple(range(8)) + (11, 12, 13), by_image=large,
+                     elem_imgs=elem_imgs)
+    tag = "%s K=%d depth=%d cf=%s B=%d %dx%d" % (case, K, depth, cf, B, H, W)
+    try:
+        tap, probs, loss = _run_tapped_step(m, x, y, sw, ck, schedule_log=True, want_loss=True)
+    except AssertionError:
+        try:
+            ck.finish()
+        finally:
+            ck.report("%s, FAILED" % tag)
+        raise
+    finally:
+        _lib.call("mpu_unet_set_launch_tap_fused", m._h, 0)
+    D = depth
+    want = train_step_launch_counts(D, n, head)
+    seen = {k: ck.all_kinds.get(k, 0) for k in want}
+    assert seen == want and sum(ck.all_kinds.values()) == tap.launches == sum(want.values()), (ck.all_kinds, want, tap.launches)
+    assert sorted(i for k, i in ck.seen if k == 3) == list(range(3 * D + 1)), ck.seen
+    taken = {i for k, i in ck.seen if k in (12, 13)}
+    assert len(taken) == n + head, ck.seen
+    if not large:
+        for kind in (0, 2):
+            assert sorted(i for k, i in ck.seen if k == kind) == list(range(5 * D + 2)), (kind, ck.seen)
+        assert sorted(i for k, i in ck.seen if k == 4) == sorted(set(range(3 * D + 1)) - taken), ck.seen
+    lines = tap.log.splitlines()
+    assert sum(l.startswith("bn_fold fwd") and "head=1" in l for l in lines) == head, lines
+    assert sum(l.startswith("bn_fold bwd") and "head=1" in l for l in lines) == head, lines
+    assert sum(l.startswith("bn_fold bwd") and "pool=1" in l for l in lines) == n, lines
+    assert len(ck.ties) == n and all(t > 0 for _c, t, _w in ck.ties), ck.ties
+    try:
+        try:
+            if head:
+                ck.check_returned(probs, loss, y, sw)
+            else:
+                assert np.array_equal(probs.cpu().numpy().astype(np.float64).reshape(ck.head_out.shape), ck.head_out)
+        finally:
+            ck.finish()
+    finally:
+        ck.report(tag)
+    print("replay (%s, %s): %.1f s; tied windows per kind-13 launch (C, tied, windows): %s" % (case, dtype, time.time() - t0, ck.ties))
+    return ck
+
+
+@pytest.mark.parametrize("case,dtype", [(c, d) for c, v in FUSED_CASES.items() for d in v[1]],
+                         ids=["%s-%s" % (c, d) for c, v in FUSED_CASES.items() for d in v[1]])
+def test_train_step_fused_head_and_pool_recompute_every_launch_against_fp64(case, dtype):
+    """The two forms of the step that are the DEFAULT of the benchmarked bf16 step and used to switch themselves off under a tap,
+    launch by launch against fp64 (FUSED_CASES; bounds: _StepChecks._kind11 / _kind12 / _kind13, tests/replay_ref.py). A case whose
+    switches this interpreter does not have runs in a fresh one (one at a time, with a timeout).
+    Measured (one MI355X; the table per case and dtype is in DESIGN.md, section 2), worst error as a fraction of its bound -- bf16:
+    probabilities <= 0.016, per-pixel loss <= 0.25, dz3 <= 0.31 (per channel 0.32: one storage rounding), the head's and the pool's
+    coefficients and reductions <= 7e-5, pool dz 0.23 (per channel 0.31), pool per element 0 (every element IS the emulated value);
+    bf16x3: probabilities <= 0.011, dz3 per channel <= 0.32 (H2), head reductions <= 0.30, pool reductions and coefficients <= 0.14
+    and, on P3's 7-workgroup grid (f32 chains of 34 windows per thread), 0.27; 21 % of the windows of every kind-13 launch tie.
+    P4 (bf16x3, C 64 ... 1024, 1.8 s): head reductions <= 0.14, pool reductions and coefficients <= 0.20, pool dz per channel 0.21,
+    statistics 0.83 (level 4: 4 values), 9.6 % tied windows at C 1024. A BatchNorm over ONE value (the bottom of H2 and P4): forward
+    0.91 (bf16: one storage rounding reaches its unit roundoff) / 0.25 (H2 bf16x3) / 0.22 (P4), backward 0.17 / 0.29 (H2).
+    0.1-3.7 s per case (6-8 s with a fresh interpreter's start-up), H4 2.1 s; H5 took 15.3 s with every element of all five images
+    compared, hence its per-element comparisons on the first, the middle and the last image (_replay_fused_step): 12.2 s."""
+    import os, subprocess, sys
+    env = FUSED_CASES[case][2]
+    if all(os.environ.get(k) == v for k, v in env.items()):
+        _replay_fused_step(case, dtype)
+        return
+    here = os.path.dirname(os.path.abspath(__file__))
+    sel = "test_train_step_fused_head_and_pool_recompute_every_launch_against_fp64 and %s-%s" % (case, dtype)
+    if dtype == "bf16":
+        sel += " and not bf16x3"
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_gpu_replay.py"), "-x", "-q", "-s", "-k", sel],
+                       env=dict(os.environ, **env), capture_output=True, text=True, cwd=os.path.dirname(here), timeout=600)
     print("\n".join(l for l in r.stdout.splitlines() if l.startswith("replay (")))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert "1 passed" in r.stdout, r.stdout[-2000:]

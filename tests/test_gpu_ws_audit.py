@@ -18,7 +18,8 @@ compared, exactly, with what that launch may write (tests/ws_audit.py; host test
     last tap (deferred grouped weight gradients and reductions).
 
 Cases: T1-T4 (test_gpu_replay.TRAIN_NETS) in bf16 and bf16x3 and T1 in f32; T3 bf16 under the step's three schedule switch sets
-(a fresh interpreter each); the inference forward of networks A-D (INFER_NETS) in bf16, A also under its three switch sets; and
+(a fresh interpreter each); T3 in bf16 and bf16x3 with the fused forms on (mpu_unet_set_launch_tap_fused, MPU_POOL_BWD_RECOMPUTE=2:
+the fused head's kinds 11 / 12 and the pool recompute's kind 13 on both encoder levels; a fresh interpreter each); the inference forward of networks A-D (INFER_NETS) in bf16, A also under its three switch sets; and
 one UNTAPPED train_step per network, where the fused training head and the pool-backward recompute run.
 """
 import collections
@@ -41,8 +42,11 @@ SLACK = 4096                    # bytes of the carved buffer behind the plan's t
 
 # Writes the tap cannot declare: (kind, region) -> (conv_index of the launch, passes that must use it, reason). No wildcards.
 EXEMPT = {
-    (0, "act/xin"): (0, ("train", "infer"), "the cast and channel padding of the input batch is an unreported launch in front of the first conv"),
+    (0, "act/xin"): (0, ("train", "train_fused", "infer"), "the cast and channel padding of the input batch is an unreported launch in front of the first conv"),
     (7, "loss_mean"): (-1, ("train",), "the head backward stores the pass's mean loss (one float) beside its declared dn"),
+    # (with the fused forms on: T3, the one net audited with them; the launch's index is its last BatchNorm's, 3 * depth = 6)
+    (12, "loss_mean"): (6, ("train_fused",), "head_bn_backward stores the pass's mean loss (one float), as the unfused head backward does"),
+    (12, "partial.trailer"): (6, ("train_fused",), "T [64][K] of the fused head: the finalizer of head_bn_backward writes it behind the partial rows, head_bn_bwd_apply reads it"),
 }
 
 
@@ -67,7 +71,7 @@ class Auditor:
     def __init__(self, m, B, fill, run, cov, passes, wpartial_by_conv=False):
         self.arena, self.ws, self.total = _carve_workspace(m, B, fill)
         self.regions = m.workspace_regions(B)
-        self.m, self.run, self.cov, self.by_conv = m, run, cov, wpartial_by_conv
+        self.m, self.run, self.cov, self.by_conv, self.fused = m, run, cov, wpartial_by_conv, passes == "train_fused"
         self.prev = self.ws.clone()
         self.watch = A.watched(self.regions, self.ws.numel(), wpartial_by_conv)
         self.exempt = [(k, name, idx) for (k, name), (idx, ps, _why) in EXEMPT.items() if passes in ps]
@@ -85,8 +89,8 @@ class Auditor:
         ws, prev, base, n = self.ws, self.prev, self.ws.data_ptr(), self.ws.numel()
         what = "interval %d (%s)" % (self.n, "behind the last tap" if li is None else "kind %d, index %d" % (li.kind, li.conv_index))
         try:
-            decl = [] if li is None else A.declared(li, self.regions, base, n, self.m.n_classes)
-            allow = A.allowed(li, self.regions, base, n, self.m.n_classes, self.exempt, self.pending, self.by_conv)
+            decl = [] if li is None else A.declared(li, self.regions, base, n, self.m.n_classes, self.fused)
+            allow = A.allowed(li, self.regions, base, n, self.m.n_classes, self.exempt, self.pending, self.by_conv, self.fused)
             for d in decl:                                   # coverage of first writes, before `prev` moves on
                 if self.cov.first_write(self.run, d.region):
                     self.cov.add(self.run, (self.n, d.field, d.region), A.changed(prev[d.lo:d.hi], ws[d.lo:d.hi]))
@@ -118,16 +122,20 @@ def _finish(cov, tag, dtype, t0, auds, extra=""):
 
 
 # ---- tapped train step ------------------------------------------------------------------------------------------------------------
-def _audit_train_step(net, dtype):
+def _audit_train_step(net, dtype, fused_levels=None):
+    """fused_levels = n: with the fused forms on (mpu_unet_set_launch_tap_fused): the fused head and n recomputed encoder levels."""
+    from multiplanarunet_amd import _lib
     from replay_tap import tapped
     t0 = time.time()
     K, C, depth, cf, B, H, W = TRAIN_NETS[net]
     by_conv = not (_env_on("MPU_WGRAD_GROUP") or _env_on("MPU_WGRAD_BATCHED_REDUCE"))      # every weight gradient its own launch
-    want = train_step_launch_counts(depth)
+    want = {k: v for k, v in train_step_launch_counts(depth, fused_levels).items() if v}
+    passes = "train" if fused_levels is None else "train_fused"
     cov, auds, lines = A.Coverage(), [], None
     for run, fill in enumerate(A.POISONS):
         m, x, y, sw = _train_case(K, C, depth, cf, B, H, W, dtype, seed=51, sw_period=2)
-        aud = Auditor(m, B, fill, run, cov, "train", by_conv)
+        _lib.call("mpu_unet_set_launch_tap_fused", m._h, int(fused_levels is not None))
+        aud = Auditor(m, B, fill, run, cov, passes, by_conv)
         auds.append(aud)
         with tapped(m, aud.on_launch, schedule_log=True) as tap:
             m.forward_backward(x, y, sw)
@@ -136,9 +144,9 @@ def _audit_train_step(net, dtype):
         lines = tap.log.splitlines()
         assert tap.launches == aud.n - 1 == sum(want.values()), (tap.launches, aud.n, want)
         assert dict(collections.Counter(aud.kinds)) == want, (collections.Counter(aud.kinds), want)
-        assert aud.used == {k for k, (_i, ps, _w) in EXEMPT.items() if "train" in ps}, ("exemptions used", aud.used)
+        assert aud.used == {k for k, (_i, ps, _w) in EXEMPT.items() if passes in ps}, ("exemptions used", aud.used)
         t = A.by_name(aud.regions, "partial.trailer")       # (the audit held it interval by interval; the sum of it)
-        assert bool((aud.ws[t.offset:t.offset + t.bytes] == fill).all())
+        assert bool((aud.ws[t.offset:t.offset + t.bytes] == fill).all()) == (fused_levels is None)
     assert auds[0].kinds == auds[1].kinds
     _finish(cov, net, dtype, t0, auds, "; wpartial by conv: %s" % ("on" if by_conv else "off"))
     return lines
@@ -152,14 +160,27 @@ def test_train_step_writes_stay_in_declared_regions(net, dtype):
         _assert_t3_schedule(lines)
 
 
+@pytest.mark.parametrize("dtype", ["bf16", "bf16x3"])
+def test_train_step_t3_fused_forms_writes_stay_in_declared_regions(dtype):
+    """T3 with the fused training head (kinds 11, 12) and the pool-backward recompute on both encoder levels (kind 13): the forms
+    the benchmarked step takes. MPU_POOL_BWD_RECOMPUTE=2 (T3's levels are below the default's size threshold) is read once per
+    process: a fresh interpreter, with a timeout, unless this one already has it."""
+    if os.environ.get("MPU_POOL_BWD_RECOMPUTE") == "2":
+        lines = _audit_train_step("T3", dtype, fused_levels=2)
+        assert sum("head=1" in l for l in lines) == 2 and sum(l.startswith("bn_fold bwd") and "pool=1" in l for l in lines) == 2, lines
+        return
+    k = "test_train_step_t3_fused_forms_writes_stay_in_declared_regions and %s" % (dtype if dtype == "bf16x3" else "bf16 and not bf16x3")
+    _subprocess(k, {"MPU_POOL_BWD_RECOMPUTE": "2"}, "ws audit (", timeout=600)
+
+
 def test_train_step_t1_f32_writes_stay_in_declared_regions():
     _audit_train_step("T1", "f32")
 
 
-def _subprocess(k, switches, prefix):
+def _subprocess(k, switches, prefix, timeout=None):
     here = os.path.dirname(os.path.abspath(__file__))
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-s", "-k", k],
-                       env=dict(os.environ, **switches), capture_output=True, text=True, cwd=os.path.dirname(here))
+                       env=dict(os.environ, **switches), capture_output=True, text=True, cwd=os.path.dirname(here), timeout=timeout)
     out = "\n".join(l for l in r.stdout.splitlines() if l.startswith(prefix))
     print(out)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]

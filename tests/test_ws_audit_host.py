@@ -74,6 +74,30 @@ def test_clean_interval_passes():
     assert [d[:4] for d in A.declared(bn, REGIONS, BASE, BUF)] == [("out", "act/b", 512, 640), ("aux0", "stats.bn/0", 6912, 6976)]
 
 
+def test_fused_kinds_declare_their_writes():
+    """Kinds 11-13 (mpu_unet_set_launch_tap_fused): head_bn_forward declares the statistics and the probabilities, the kind-3
+    record of its BatchNorm (out = NULL) the statistics alone, kinds 12 and 13 the dz tensor; the trailer of `partial` is the
+    kind-12 interval's by exemption only."""
+    st = dict(aux0=BASE + 6912, aux1=BASE + 6912 + 16)
+    fwd = launch(11, C0=4, Cout=3, out=BASE + 1024, **st)               # probabilities: 16 pixels x 3 classes x 4 bytes in "gA"
+    assert [d[:4] for d in A.declared(fwd, REGIONS, BASE, BUF)] == [("aux0", "stats.bn/0", 6912, 6976), ("out", "gA", 1024, 1216)]
+    assert [d[:4] for d in A.declared(launch(3, C0=4, **st), REGIONS, BASE, BUF, fused=True)] == [("aux0", "stats.bn/0", 6912, 6976)]
+    with pytest.raises(AssertionError, match="outside the fused forms"):
+        A.declared(launch(3, C0=4, **st), REGIONS, BASE, BUF)
+    prev, now = buffers()
+    now[1024:1216] = 1
+    now[6912:6976] = 2
+    assert audit(fwd, prev, now) == [] and audit(launch(3, C0=4, **st), prev, now, fused=True) == [Finding("gA", 0, 192, 1024)]
+    for kind in (12, 13):
+        bwd = launch(kind, C0=8, Cout=3, out=BASE + 0)
+        assert [d[:4] for d in A.declared(bwd, REGIONS, BASE, BUF)] == [("out", "act/a", 0, 256)]
+        prev, now = buffers()
+        now[0:256] = 1
+        now[2304:2304 + 64] = 3                                         # T of the fused head in the trailer
+        assert audit(bwd, prev, now) == [Finding("partial.trailer", 0, 64, 2304)]
+        assert audit(bwd, prev, now, exempt=[(kind, "partial.trailer", None)]) == []
+
+
 def test_one_byte_into_a_gap_fails():
     prev, now = buffers()
     now[0:512] = 1

@@ -10,7 +10,8 @@ taps are compared, exactly, with what that launch may write:
   * a byte of no region -- the tail between a region's unrounded length and the next multiple of 256, and everything between
     the plan's total and the end of the buffer -- never changes (gaps());
   * SCRATCH regions are free, except the 1024 trailing floats of `partial` ("partial.trailer": the fused training head alone
-    writes them, and it is off under a tap) and, where the caller asks for it (wpartial_by_conv: ungrouped weight gradients),
+    writes them; it is off under a tap unless mpu_unet_set_launch_tap_fused asked for it, and then only its kind-12 interval may:
+    the caller's exemption table) and, where the caller asks for it (wpartial_by_conv: ungrouped weight gradients),
     `wpartial`, which a weight-gradient launch may change only inside its own conv's slice ("wpartial.conv/<i>");
   * exemptions are whole regions that a launch of one kind may change although the tap cannot declare it (the caller's table).
 
@@ -73,7 +74,7 @@ def _esz(li):
     return 2 if li.dtype == BF16 else 4
 
 
-def outputs(li, n_classes=None):
+def outputs(li, n_classes=None, fused=False):
     """[(field, device pointer, bytes)]: what a launch of li.kind writes through the pointers of mpu_launch_info, sized from its
     own shapes as the replay reads them (include/mpunet_hip.h; tests/test_gpu_replay.py: _StepChecks, _replay_inference)."""
     e, px = _esz(li), li.B * li.H * li.W
@@ -84,14 +85,15 @@ def outputs(li, n_classes=None):
         out.append(("out", li.out, px * li.Cout * e))
     if k == 1:
         out.append(("out", li.out, px * li.n_cnt * e))                   # the channel-sliced data gradient: the declared channels only
-    if k in (3, 4, 5, 7):
-        out.append(("out", li.out, px * li.C0 * e))
-    if k == 3:
+    assert k != 3 or li.out or fused, "kind 3 without an output outside the fused forms"
+    if k in (4, 5, 7, 12, 13) or (k == 3 and li.out):                    # (fused: kind 3 of the fused head's BatchNorm stores no y)
+        out.append(("out", li.out, px * li.C0 * e))                      # kinds 12, 13: the dz of the conv in front of the BatchNorm
+    if k in (3, 11):
         if li.mask:
             out.append(("mask", li.mask, pooled * li.C0 * e))
-        assert li.aux1 == li.aux0 + 4 * li.C0, "kind 3: mean and invstd are not neighbours"
+        assert li.aux1 == li.aux0 + 4 * li.C0, "kind %d: mean and invstd are not neighbours" % k
         out.append(("aux0", li.aux0, 4 * li.C0 * 4))                     # mean, invstd and, directly behind them, scale and shift
-    if k in (6, 10):
+    if k in (6, 10, 11):                                                 # (kind 11, head_bn_forward: statistics AND probabilities)
         out.append(("out", li.out, px * li.Cout * 4))
     if k == 8:
         if li.mask:
@@ -101,17 +103,17 @@ def outputs(li, n_classes=None):
             out.append(("dz", li.dz, 2 * px * n_classes * 4))
     if k == 9:
         out.append(("out", li.out, pooled * li.C0 * e))
-    assert k in range(11), "unknown launch kind %d" % k
+    assert k in range(14), "unknown launch kind %d" % k
     assert all(p for _f, p, _n in out), ("a declared output is NULL", k, li.conv_index)
     return out
 
 
-def declared(li, regions, base, total, n_classes=None):
+def declared(li, regions, base, total, n_classes=None, fused=False):
     """The declared outputs of `li` that lie in the buffer starting at device pointer `base`, as Declared records. An output
     outside the buffer (the caller's own probabilities tensor) is none of the audit's business. One that starts in the buffer
     must start inside a TENSOR or STATS region and is clipped to it: what it stores past that region's end is a finding."""
     out = []
-    for field, p, n in outputs(li, n_classes):
+    for field, p, n in outputs(li, n_classes, fused):
         lo = p - base
         if lo < 0 or lo >= total:
             continue
@@ -138,7 +140,7 @@ def free_scratch(regions, wpartial_by_conv=False):
     return [(a, b) for a, b in out if b > a]
 
 
-def allowed(li, regions, base, total, n_classes=None, exempt=(), pending_wgrad=None, wpartial_by_conv=False):
+def allowed(li, regions, base, total, n_classes=None, exempt=(), pending_wgrad=None, wpartial_by_conv=False, fused=False):
     """The byte ranges the interval that ends at the tap of `li` may change. li None: the interval behind the last tap.
     exempt: (kind, region name, conv_index or None) triples of the caller's table; pending_wgrad: the conv whose weight gradient
     the PREVIOUS tap reported (kind 2 reports before its launch, so its stores fall into this interval)."""
@@ -147,7 +149,7 @@ def allowed(li, regions, base, total, n_classes=None, exempt=(), pending_wgrad=N
         s = by_name(regions, "wpartial.conv/%d" % pending_wgrad)
         out.append((s.offset, s.offset + s.bytes))
     if li is not None:
-        out += [(d.lo, d.hi) for d in declared(li, regions, base, total, n_classes)]
+        out += [(d.lo, d.hi) for d in declared(li, regions, base, total, n_classes, fused)]
         for kind, name, index in exempt:
             if kind == li.kind and (index is None or index == li.conv_index):
                 r = by_name(regions, name)
