@@ -716,6 +716,33 @@ int mpu_label_components(const uint8_t* d_labels, const int64_t shape[3], int32_
 int mpu_keep_largest_components(const uint8_t* d_labels, const int64_t shape[3], int32_t connectivity, int32_t n_classes,
                                 uint32_t class_mask, uint8_t* d_out, int64_t* d_report, void* d_scratch, void* stream);
 
+/* Two more filters of a resident label map on the same labelling (`mp predict --min_component_voxels`, `--fill_holes`; no reference
+ * counterpart). Shapes, classes, connectivity, class_mask, d_out (d_labels itself or no overlap), alignment, error codes and the
+ * order of the checks are those of mpu_keep_largest_components; labels >= n_classes ("foreign") are never rewritten, are not
+ * background, belong to no class and cast no vote. All results are exact integers: two calls give identical bytes.
+ *
+ * mpu_remove_small_components: d_out = d_labels, except that every connected component (under `connectivity`) of a class in
+ *   class_mask with fewer than min_voxels voxels becomes 0. min_voxels >= 1 (else MPU_EINVAL); 1 is the identity. d_report i64
+ *   [n_classes][3]: components found, voxels kept, voxels removed; an unmasked class reports removed = 0, row 0 is zero. 7 launches.
+ *   d_scratch: mpu_components_scratch_bytes(shape).
+ * mpu_fill_holes: the background is {label == 0}. A CAVITY is a connected component of the background under `connectivity` (6 is
+ *   scipy.ndimage.binary_fill_holes' default structure) that contains no voxel with an index of 0 or dim - 1 on any axis -- a volume
+ *   with a dimension of 1 has none. Each cavity is filled whole with the winner of a face vote: the pairs (p in the cavity, q one of
+ *   the six face neighbours of p inside the volume) with 1 <= label(q) < n_classes are counted per class; the largest count wins, a
+ *   tie goes to the smallest class. A cavity without a vote, or whose winner is not in class_mask, is left as it is. d_report i64
+ *   [n_classes][2]: cavities and voxels given to class c; row 0: cavities and voxels left unfilled. With n_classes = 2 and
+ *   class_mask = 2 the result is binary_fill_holes(labels == 1, generate_binary_structure(3, level)). 9 + 2 (n_classes - 1) launches
+ *   (one vote and one fold per class, integer atomics). d_scratch: mpu_fill_holes_scratch_bytes(shape) bytes (25 per voxel and a
+ *   header; -1 + mpu_last_error() outside the ranges).
+ * Scratch is caller-owned, contents irrelevant before and after; nothing outside it and the named outputs is written. A fixed
+ * sequence of launches on `stream`, no host synchronisation, no memset: the calls may be captured into a HIP graph. */
+int64_t mpu_fill_holes_scratch_bytes(const int64_t shape[3]);
+int mpu_remove_small_components(const uint8_t* d_labels, const int64_t shape[3], int32_t connectivity, int32_t n_classes,
+                                uint32_t class_mask, int64_t min_voxels, uint8_t* d_out, int64_t* d_report, void* d_scratch,
+                                void* stream);
+int mpu_fill_holes(const uint8_t* d_labels, const int64_t shape[3], int32_t connectivity, int32_t n_classes, uint32_t class_mask,
+                   uint8_t* d_out, int64_t* d_report, void* d_scratch, void* stream);
+
 /* Exact Euclidean distance transform of a resident label volume with anisotropic voxel spacing, and the surface-distance table of
  * `mp predict --surface_metrics` (no reference counterpart; the host route is scipy.ndimage.distance_transform_edt twice per class).
  * d_labels u8 [X][Y][Z] in C order (shape = {X, Y, Z}), no alignment required; spacing = {sx, sy, sz}, finite and > 0.
@@ -753,6 +780,26 @@ int mpu_edt_squared(const uint8_t* d_labels, const int64_t shape[3], const doubl
                     int32_t take_root, double* d_out, void* d_scratch, void* stream);
 int mpu_surface_table(const uint8_t* d_pred, const uint8_t* d_truth, const int64_t shape[3], const double spacing[3], int32_t n_classes,
                       uint32_t class_mask, double tolerance, void* d_table, void* d_scratch, void* stream);
+
+/* Opening and closing of the classes of a resident label map by a Euclidean ball (`mp predict --open_mm / --close_mm`; no reference
+ * counterpart), as two thresholds of the exact transform above -- hence in the units of `spacing`, correct on anisotropic voxels.
+ * With r2 = fl(radius * radius) and d2 as mpu_edt_squared defines it (same weights, one rounded operation each):
+ *   dilate(M) = {p : d2(p, M) <= r2}   erode(M) = {p : d2(p, not M) > r2}   close = erode(dilate(M))   open = dilate(erode(M)).
+ * Distances are measured to voxels inside the volume only and nothing is assumed outside it: an object on the volume face is not
+ * shaved there (unlike scipy's border_value = 0). No feature voxel gives +inf: an empty mask stays empty, a full one full.
+ * The classes of class_mask are processed in ascending order, each on the map the earlier ones left: MPU_MORPH_CLOSE sets to c only
+ * voxels whose current label is 0 (never another class or a foreign label), MPU_MORPH_OPEN sets to 0 only voxels of class c. d2 is
+ * symmetric in its two voxels, so closing is extensive and opening anti-extensive, exactly. d_report i64 [n_classes][2]: voxels
+ * added, voxels removed (rows of classes not asked for, and row 0, are zero). d_out == d_labels (in place) is allowed, any other
+ * overlap is MPU_EINVAL. Every comparison is exact: two calls give identical bytes.
+ * MPU_EUNSUPPORTED / MPU_EINVAL as mpu_surface_table, and MPU_EINVAL for an unknown op, a radius that is not finite and > 0, a
+ * misaligned d_report (8 bytes). Every check precedes the first HIP call. d_scratch: mpu_surface_scratch_bytes(shape) bytes (the two
+ * f64 volumes of the transform; the one-byte mask between the two transforms lies in the key-list region), caller-owned, contents
+ * irrelevant before and after; nothing outside it and the named outputs is written. 1 + 12 launches per class on `stream`, no host
+ * synchronisation, no memset. */
+enum { MPU_MORPH_OPEN = 0, MPU_MORPH_CLOSE = 1 };
+int mpu_morph_ball(const uint8_t* d_labels, const int64_t shape[3], const double spacing[3], int32_t n_classes, uint32_t class_mask,
+                   int32_t op, double radius, uint8_t* d_out, int64_t* d_report, void* d_scratch, void* stream);
 
 /* Measurement aid (bench.py roofline leg; no reference counterpart): when
  * enabled, every MFMA convolution launch is bracketed by HIP events recorded on

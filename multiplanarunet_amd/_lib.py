@@ -25,6 +25,7 @@ ABI_VERSION = 2                         # mpu_abi_version() this binding was wri
 MPU_LOSS_SPARSE_CE_LOGITS = 6           # mpu_unet_set_loss on a handle with softmax == 0 only; evaluated by mpu_eval_loss_logits
 MPU_GDL_SQUARE, MPU_GDL_SIMPLE, MPU_GDL_UNIFORM = 0, 1, 2
 MPU_EDT_EQUAL, MPU_EDT_NOT_EQUAL, MPU_EDT_BORDER = 0, 1, 2   # feature predicate of mpu_edt_squared
+MPU_MORPH_OPEN, MPU_MORPH_CLOSE = 0, 1                     # op of mpu_morph_ball
 MPU_WS_TENSOR, MPU_WS_STATS, MPU_WS_SCRATCH = 0, 1, 2      # class of a workspace region (mpu_unet_workspace_region_info)
 # mpu_optimizer_kind / mpu_optimizer_flag
 MPU_OPT_ADAM, MPU_OPT_SGD, MPU_OPT_RMSPROP, MPU_OPT_ADAMAX = range(4)
@@ -184,6 +185,10 @@ _SIGS = {
     "mpu_components_scratch_bytes": (i64, [C.POINTER(i64)]),
     "mpu_label_components": (C.c_int, [c_p, C.POINTER(i64), i32, i32, c_p, c_p, c_p]),
     "mpu_keep_largest_components": (C.c_int, [c_p, C.POINTER(i64), i32, i32, C.c_uint32, c_p, c_p, c_p, c_p]),
+    "mpu_fill_holes_scratch_bytes": (i64, [C.POINTER(i64)]),
+    "mpu_remove_small_components": (C.c_int, [c_p, C.POINTER(i64), i32, i32, C.c_uint32, i64, c_p, c_p, c_p, c_p]),
+    "mpu_fill_holes": (C.c_int, [c_p, C.POINTER(i64), i32, i32, C.c_uint32, c_p, c_p, c_p, c_p]),
+    "mpu_morph_ball": (C.c_int, [c_p, C.POINTER(i64), C.POINTER(f64), i32, C.c_uint32, i32, f64, c_p, c_p, c_p, c_p]),
     "mpu_surface_scratch_bytes": (i64, [C.POINTER(i64)]),
     "mpu_edt_squared": (C.c_int, [c_p, C.POINTER(i64), C.POINTER(f64), i32, i32, i32, c_p, c_p, c_p]),
     "mpu_surface_table": (C.c_int, [c_p, c_p, C.POINTER(i64), C.POINTER(f64), i32, C.c_uint32, f64, c_p, c_p, c_p]),

@@ -9,6 +9,11 @@ while the next volume is predicted. The writer is closed before run() returns or
 --largest_component (no reference counterpart; postprocess.py): rank 0 filters the fused label map on the device -- per class, only
 the largest connected component stays -- before the Dice evaluation and before the file is made, so that the saved file,
 results.csv and the log describe the same map.
+--open_mm R, --close_mm R, --fill_holes [--hole_connectivity], --min_component_voxels N [--clean_connectivity], --clean_classes (no
+reference counterpart; postprocess.py): rank 0 cleans the fused label map on the device BEFORE that filter, in the fixed order open ->
+close -> fill holes -> size threshold (closing seals gaps so that holes become cavities; the size filters then judge the repaired
+objects), with the voxel sizes of the affine as the spacing of the ball; one log line per stage and class and csv/cleanup_results.csv
+from the report tables. Without these flags nothing of it is imported or launched.
 --surface_metrics [--nsd_tolerance MM] (no reference counterpart; surface.py): rank 0 also evaluates that saved map against the labels
 by surface distances on the device -- HD, HD95, ASSD and the voxel-border NSD per foreground class, with the voxel sizes of the
 affine -- and writes csv/surface_results.csv. No other output changes, and without the flag surface.py is not imported.
@@ -57,6 +62,22 @@ def get_argparser():
                    help="voxel neighbourhood of --largest_component (default 26)")
     p.add_argument("--cc_classes", type=str, default=None,
                    help="comma-separated classes --largest_component filters, e.g. 1,3 (default: all foreground classes)")
+    p.add_argument("--open_mm", type=float, default=None,
+                   help="open every class of the fused label map by a Euclidean ball of this radius, in the units of the affine (on "
+                        "the device; off by default). Clean-up stages run in the order open, close, fill holes, size threshold, "
+                        "then --largest_component")
+    p.add_argument("--close_mm", type=float, default=None, help="close every class by a Euclidean ball of this radius (background only "
+                                                                "is given to a class)")
+    p.add_argument("--fill_holes", action="store_true",
+                   help="fill every background cavity with the class that borders it most (face vote; a tie: the smallest class)")
+    p.add_argument("--hole_connectivity", type=int, default=None, choices=(6, 18, 26),
+                   help="background connectivity of --fill_holes (default 6, scipy's binary_fill_holes)")
+    p.add_argument("--min_component_voxels", type=int, default=None,
+                   help="remove every connected component of a class with fewer voxels than this")
+    p.add_argument("--clean_connectivity", type=int, default=None, choices=(6, 18, 26),
+                   help="voxel neighbourhood of --min_component_voxels (default 26)")
+    p.add_argument("--clean_classes", type=str, default=None,
+                   help="comma-separated classes the four clean-up operations work on, e.g. 1,3 (default: all foreground classes)")
     p.add_argument("--surface_metrics", action="store_true",
                    help="also evaluate the saved label map against the labels by surface distances, per foreground class: HD, HD95, "
                         "ASSD and NSD (on the device; csv/surface_results.csv; off by default)")
@@ -109,6 +130,68 @@ def component_filter_plan(args, n_classes=None):
     return (26 if conn is None else int(conn)), classes
 
 
+CLEANUP_STAGES = ("open", "close", "fill_holes", "small_components")      # the order they run in
+
+
+def cleanup_plan(args, n_classes=None):
+    """The clean-up flags (--open_mm, --close_mm, --fill_holes, --min_component_voxels and what qualifies them), checked: None when
+    none of the four is given, else a dict with open_mm / close_mm (a radius or None), hole_connectivity (None: no hole filling),
+    min_voxels (None: no size threshold), clean_connectivity and classes (None = all foreground classes). ValueError on a
+    combination that cannot be served; with n_classes also on a class outside 1 .. n_classes - 1."""
+    g = lambda k: getattr(args, k, None)
+    open_mm, close_mm, fill, min_voxels = g("open_mm"), g("close_mm"), bool(g("fill_holes")), g("min_component_voxels")
+    if g("hole_connectivity") is not None and not fill:
+        raise ValueError("--hole_connectivity needs --fill_holes")
+    if g("clean_connectivity") is not None and min_voxels is None:
+        raise ValueError("--clean_connectivity needs --min_component_voxels")
+    classes = g("clean_classes")
+    if open_mm is None and close_mm is None and not fill and min_voxels is None:
+        if classes is not None:
+            raise ValueError("--clean_classes needs at least one of --open_mm, --close_mm, --fill_holes, --min_component_voxels")
+        return None
+    if getattr(args, "no_argmax", False):
+        raise ValueError("--open_mm / --close_mm / --fill_holes / --min_component_voxels clean a label map: they cannot be combined "
+                         "with --no_argmax (a probability volume is not cleaned)")
+    for flag, r in (("--open_mm", open_mm), ("--close_mm", close_mm)):
+        if r is not None and (not (float(r) > 0.0) or float(r) == float("inf")):
+            raise ValueError("%s must be finite and > 0, got %r" % (flag, r))
+    if min_voxels is not None and int(min_voxels) < 1:
+        raise ValueError("--min_component_voxels must be >= 1, got %r" % (min_voxels,))
+    if classes is not None:
+        try:
+            classes = sorted({int(c) for c in str(classes).split(",") if c.strip() != ""})
+        except ValueError:
+            raise ValueError("--clean_classes: expected comma-separated class numbers, got %r" % (args.clean_classes,))
+        if not classes:
+            raise ValueError("--clean_classes: no class named")
+        if n_classes is not None and (classes[0] < 1 or classes[-1] > int(n_classes) - 1):
+            raise ValueError("--clean_classes %s: classes must be in 1 .. n_classes - 1 = %d" % (args.clean_classes, int(n_classes) - 1))
+    return dict(open_mm=None if open_mm is None else float(open_mm), close_mm=None if close_mm is None else float(close_mm),
+                hole_connectivity=(6 if g("hole_connectivity") is None else int(g("hole_connectivity"))) if fill else None,
+                min_voxels=None if min_voxels is None else int(min_voxels),
+                clean_connectivity=26 if g("clean_connectivity") is None else int(g("clean_connectivity")), classes=classes)
+
+
+def run_cleanup(labels, plan, n_classes, spacing):
+    """The stages of a cleanup_plan on a resident label map, in place, in the order of CLEANUP_STAGES: closing seals gaps so that
+    holes become cavities, the size threshold then judges the repaired objects. -> [(stage, counts' names, table)] per stage run."""
+    from .. import postprocess as PP
+    K, cls, done = int(n_classes), plan["classes"], []
+    if plan["open_mm"] is not None:
+        _, t = PP.open_ball(labels, K, plan["open_mm"], spacing, classes=cls, out=labels, report=True)
+        done.append(("open", ("voxels_added", "voxels_removed"), t))
+    if plan["close_mm"] is not None:
+        _, t = PP.close_ball(labels, K, plan["close_mm"], spacing, classes=cls, out=labels, report=True)
+        done.append(("close", ("voxels_added", "voxels_removed"), t))
+    if plan["hole_connectivity"] is not None:
+        _, t = PP.fill_holes(labels, K, plan["hole_connectivity"], classes=cls, out=labels, report=True)
+        done.append(("fill_holes", ("cavities", "voxels_filled"), t))
+    if plan["min_voxels"] is not None:
+        _, t = PP.remove_small_components(labels, K, plan["min_voxels"], plan["clean_connectivity"], classes=cls, out=labels, report=True)
+        done.append(("small_components", ("components", "voxels_kept", "voxels_removed"), t))
+    return done
+
+
 def best_model_path(model_dir):
     """get_best_model (mpunet/utils/utils.py:88-110) over this build's .npz and the reference's .h5 checkpoints."""
     from ..formats import get_best_model
@@ -144,9 +227,12 @@ def run(args):
     project_dir = os.path.abspath(args.project_dir)
     cc = component_filter_plan(args)                      # (flag combinations: refused before anything is looked at)
     sm = surface_metrics_plan(args)
+    cl = cleanup_plan(args)
     validate_project_dir(project_dir)
     if cc is not None:                                    # the classes against the project's, before anything is loaded or created
         cc = component_filter_plan(args, load_hparams(project_dir)["build"]["n_classes"])
+    if cl is not None:
+        cl = cleanup_plan(args, load_hparams(project_dir)["build"]["n_classes"])
     for req in ("views.npz", "model"):
         if not os.path.exists(os.path.join(project_dir, req)):
             raise RuntimeError("Invalid project folder: needs train_hparams.yaml, views.npz and model/ (missing %s)" % req)
@@ -191,7 +277,7 @@ def run(args):
     nii = os.path.join(out_dir, "nii_files")
     if rank == 0:
         os.makedirs(nii, exist_ok=True)
-    results, per_view, surface = {}, {}, {}
+    results, per_view, surface, cleanup = {}, {}, {}, []
 
     def plan(item):
         """(write a NIfTI file?, output folder, output file) of a volume or a dataset entry."""
@@ -232,6 +318,14 @@ def run(args):
                 probs, labels = multi_view_predict(model, v, views, build["dim"], fit["real_space_span"], fm,
                                                    sum_fusion=args.sum_fusion, batch_size=None,
                                                    want_probs=args.no_argmax, per_view_eval=pve, map_method=args.map_method)
+            if rank == 0 and cl is not None:                  # open -> close -> fill holes -> size threshold, before the filter below
+                from .. import surface as edt            # (the ball's spacing: the voxel sizes of the affine)
+                labels = labels.contiguous()
+                for stage, names, table in run_cleanup(labels, cl, build["n_classes"], edt.voxel_sizes(v.affine)):
+                    for c in ([0] if stage == "fill_holes" else []) + list(cl["classes"] or range(1, build["n_classes"])):
+                        log("%s: class %d: %s: %s" % (v.identifier, c, stage, ", ".join("%d %s" % (int(x), k.replace("_", " "))
+                                                                                       for k, x in zip(names, table[c]))))
+                        cleanup.append((v.identifier, c, stage, dict(zip(names, (int(x) for x in table[c])))))
             if rank == 0 and cc is not None:                  # the map that is evaluated, logged and saved from here on
                 from ..postprocess import keep_largest_component
                 labels = labels.contiguous()
@@ -299,6 +393,13 @@ def run(args):
                         view, _, md, mean = rows[i]
                         f.write("%s,%d,%s,%.5f,%s\n" % (k, i, " ".join("%.6g" % x for x in np.asarray(view).ravel()), mean,
                                                         ",".join("%.5f" % x for x in md)))
+    if rank == 0 and cleanup:                           # one row per (image, class, stage); class 0 of fill_holes: left unfilled
+        os.makedirs(os.path.join(out_dir, "csv"), exist_ok=True)
+        cols = ("voxels_added", "voxels_removed", "cavities", "voxels_filled", "components", "voxels_kept")
+        with open(os.path.join(out_dir, "csv", "cleanup_results.csv"), "w") as f:
+            f.write("image,class,stage," + ",".join(cols) + "\n")
+            for ident, c, stage, counts in cleanup:
+                f.write("%s,%d,%s,%s\n" % (ident, c, stage, ",".join(str(counts.get(k, "")) for k in cols)))
     if rank == 0 and surface:                           # one row per (image, foreground class)
         os.makedirs(os.path.join(out_dir, "csv"), exist_ok=True)
         with open(os.path.join(out_dir, "csv", "surface_results.csv"), "w") as f:

@@ -26,6 +26,8 @@
 //             index, which is np.argmax(np.bincount(...)) over ndimage.label's raster numbering; component and voxel totals
 //             per class. Block-local in LDS first, then at most 3 * n_classes global atomics per workgroup.
 //   apply     out = labels with the voxels of a masked class outside its winner set to 0; block 0 writes the report.
+// The same labelling and count serve the size threshold of `mp predict --min_component_voxels` (select<SMALL>, drop) and -- on a
+// one-byte map of the background -- the hole filling of `--fill_holes` (the fh_* kernels; their protocol stands above them).
 //
 // Visibility (the per-XCD L2s are not coherent with each other, a CU's L1 is never refreshed): inside a launch the ONLY
 // communication between workgroups is agent-scope atomic read-modify-writes on parent[] (atomicMin) whose returned old value is
@@ -260,8 +262,10 @@ __global__ __launch_bounds__(CC_THREADS) void cc_count_kernel(const int* __restr
         if (s_cnt[t]) atomicAdd(sizes + s_key[t], s_cnt[t]);
 }
 
+// SMALL (mpu_remove_small_components): `best` is not the key of the winner but the SUM of the sizes below min_voxels
+template <bool SMALL>
 __global__ __launch_bounds__(CC_THREADS) void cc_select_kernel(const uint8_t* __restrict__ labels, const int* __restrict__ roots,
-                                                               const int* __restrict__ sizes, int n, CcHeader* hdr) {
+                                                               const int* __restrict__ sizes, int n, CcHeader* hdr, long long min_voxels) {
     __shared__ unsigned long long s_best[CC_MAXK], s_total[CC_MAXK], s_ncomp[CC_MAXK];
     if (threadIdx.x < CC_MAXK) { s_best[threadIdx.x] = 0ull; s_total[threadIdx.x] = 0ull; s_ncomp[threadIdx.x] = 0ull; }
     __syncthreads();
@@ -276,14 +280,16 @@ __global__ __launch_bounds__(CC_THREADS) void cc_select_kernel(const uint8_t* __
             if (r[k] < 0 || r[k] != i) continue;
             const int c = (int)labels[i] & (CC_MAXK - 1);                         // (a root carries 1 <= c < n_classes <= 16)
             const unsigned long long size = (unsigned long long)(unsigned)(sizes[i] - i);
-            atomicMax(&s_best[c], (size << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i));
+            if (SMALL) { if ((long long)size < min_voxels) atomicAdd(&s_best[c], size); }
+            else atomicMax(&s_best[c], (size << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i));
             atomicAdd(&s_total[c], size);
             atomicAdd(&s_ncomp[c], 1ull);
         }
     }
     __syncthreads();
     if (threadIdx.x < CC_MAXK && s_ncomp[threadIdx.x]) {
-        atomicMax(&hdr->best[threadIdx.x], s_best[threadIdx.x]);
+        if (SMALL) atomicAdd(&hdr->best[threadIdx.x], s_best[threadIdx.x]);
+        else atomicMax(&hdr->best[threadIdx.x], s_best[threadIdx.x]);
         atomicAdd(&hdr->total[threadIdx.x], s_total[threadIdx.x]);
         atomicAdd(&hdr->ncomp[threadIdx.x], s_ncomp[threadIdx.x]);
     }
@@ -349,6 +355,187 @@ __global__ __launch_bounds__(CC_THREADS) void cc_apply_kernel(const uint8_t* lab
     }
 }
 
+// ---- mpu_remove_small_components: label -> count -> select<SMALL> -> drop ------------------------------------------------------
+__device__ __forceinline__ void store4b(uint8_t* out, long i0, int n, uint32_t w) {
+    if (i0 + 4 <= n && (((uintptr_t)out) & 3) == 0) { *(uint32_t*)(out + i0) = w; return; }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (i0 + k < n) out[i0 + k] = (uint8_t)(w >> (8 * k));
+}
+
+// out = labels with the voxels of a masked class whose component has fewer than min_voxels voxels set to 0; block 0 writes the
+// report. labels / out may be the same pointer (a voxel is read and written by the same thread, and by no other).
+__global__ __launch_bounds__(CC_THREADS) void cc_drop_small_kernel(const uint8_t* labels, const int* __restrict__ roots,
+                                                                   const int* __restrict__ sizes, int n, int K, unsigned class_mask,
+                                                                   long long min_voxels, const CcHeader* __restrict__ hdr, uint8_t* out,
+                                                                   long long* __restrict__ report) {
+    if (blockIdx.x == 0 && (int)threadIdx.x < K) {
+        const int c = (int)threadIdx.x;
+        const long long total = (long long)hdr->total[c], removed = ((class_mask >> c) & 1u) ? (long long)hdr->best[c] : 0ll;
+        report[3 * c + 0] = (long long)hdr->ncomp[c];
+        report[3 * c + 1] = total - removed;
+        report[3 * c + 2] = removed;
+    }
+    const bool aligned4 = (((uintptr_t)labels) & 3) == 0;
+    const long ngroups = ((long)n + 3) / 4, stride = (long)gridDim.x * CC_THREADS;
+    for (long g = (long)blockIdx.x * CC_THREADS + threadIdx.x; g < ngroups; g += stride) {
+        const long i0 = g * 4;
+        uint32_t w = load4(labels, i0, n, aligned4);
+        if (w != 0u) {
+            int r[4];
+            load4i(roots, i0, n, r);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (r[k] < 0) continue;                                           // (1 <= c < K from here on: flatten named it)
+                const unsigned c = (w >> (8 * k)) & 0xffu;
+                if (((class_mask >> c) & 1u) && (long long)(sizes[r[k]] - r[k]) < min_voxels) w &= ~(0xffu << (8 * k));
+            }
+        }
+        store4b(out, i0, n, w);
+    }
+}
+
+// ---- mpu_fill_holes ---------------------------------------------------------------------------------------------------------------
+// The background {label == 0} is labelled by cc_label on a one-byte map (1 = background) as "class 1 of 2". Per ROOT of a background
+// component two u64 words: best[r] and cnt[r] (only root words are ever read or written).
+//   background  bg[i] = labels[i] == 0
+//   (cc_label)  roots[i] = first voxel of i's background component, -1 off the background
+//   init        best[r] = cnt[r] = 0 at every root
+//   border      best[r] = FH_OPEN for the root of every background voxel with an index of 0 or dim - 1 on some axis: not a cavity
+//   vote c      cnt[r] += the face neighbours with label c of every voxel of cavity r      }  once per class c = 1 .. K - 1: the
+//   fold c      best[r] = max(best[r], cnt[r] << 4 | 15 - c) where cnt[r] > 0; cnt[r] = 0    }  running best of (count, smallest class)
+//   fill        out = labels, the voxels of a cavity whose winner is in class_mask set to the winner; cavities and voxels per class
+//               (row 0: left unfilled) meet in LDS, then in the header
+//   report      header -> report
+// cnt <= 6 * voxels < 2^34, so the key fits 64 bits with room. Communication inside a launch is by atomic adds / maxima on root
+// words alone, and no launch reads a word that the same launch modifies (vote reads best, adds to cnt).
+constexpr unsigned long long FH_OPEN = ~0ull;
+
+__global__ __launch_bounds__(CC_THREADS) void fh_background_kernel(const uint8_t* __restrict__ labels, uint8_t* __restrict__ bg, int n) {
+    const bool aligned4 = (((uintptr_t)labels) & 3) == 0;
+    const long ngroups = ((long)n + 3) / 4, stride = (long)gridDim.x * CC_THREADS;
+    for (long g = (long)blockIdx.x * CC_THREADS + threadIdx.x; g < ngroups; g += stride) {
+        const uint32_t w = load4(labels, g * 4, n, aligned4);
+        uint32_t b = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (((w >> (8 * k)) & 0xffu) == 0u) b |= 1u << (8 * k);
+        store4b(bg, g * 4, n, b);                                                 // (positions >= n of the last group are not stored)
+    }
+}
+
+__global__ __launch_bounds__(CC_THREADS) void fh_init_kernel(const int* __restrict__ roots, unsigned long long* __restrict__ best,
+                                                             unsigned long long* __restrict__ cnt, int n) {
+    const long stride = (long)gridDim.x * CC_THREADS;
+    for (long i = (long)blockIdx.x * CC_THREADS + threadIdx.x; i < n; i += stride)
+        if (roots[i] == (int)i) { best[i] = 0ull; cnt[i] = 0ull; }
+}
+
+// one thread per voxel of the six faces would do; all voxels are walked (the coordinates decide) to keep the indexing in one place
+__global__ __launch_bounds__(CC_THREADS) void fh_border_kernel(const int* __restrict__ roots, CcDims d, unsigned long long* best) {
+    const long stride = (long)gridDim.x * CC_THREADS;
+    for (long i = (long)blockIdx.x * CC_THREADS + threadIdx.x; i < d.n; i += stride) {
+        const int r = roots[i];
+        if (r < 0) continue;
+        int x, y, z;
+        coords((unsigned)i, d, x, y, z);
+        if (x != 0 && y != 0 && z != 0 && x != d.X - 1 && y != d.Y - 1 && z != d.Z - 1) continue;
+        // a stale read only repeats the maximum; the atomic is what marks
+        if (__hip_atomic_load(best + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != FH_OPEN) atomicMax(best + r, FH_OPEN);
+    }
+}
+
+__global__ __launch_bounds__(CC_THREADS) void fh_vote_kernel(const uint8_t* __restrict__ labels, const int* __restrict__ roots,
+                                                             const unsigned long long* __restrict__ best, unsigned long long* cnt,
+                                                             CcDims d, int c) {
+    const long ngroups = ((long)d.n + 3) / 4, stride = (long)gridDim.x * CC_THREADS;
+    const long sYZ = (long)d.Y * d.Z;
+    for (long g = (long)blockIdx.x * CC_THREADS + threadIdx.x; g < ngroups; g += stride) {
+        const long i0 = g * 4;
+        int r[4];
+        load4i(roots, i0, d.n, r);
+        if (r[0] < 0 && r[1] < 0 && r[2] < 0 && r[3] < 0) continue;
+        int x, y, z;
+        coords((unsigned)i0, d, x, y, z);
+        int cur = -1;
+        unsigned long long votes = 0ull;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (r[k] >= 0) {
+                const long i = i0 + k;
+                int v = 0;
+                if (x > 0) v += (int)labels[i - sYZ] == c;
+                if (x < d.X - 1) v += (int)labels[i + sYZ] == c;
+                if (y > 0) v += (int)labels[i - d.Z] == c;
+                if (y < d.Y - 1) v += (int)labels[i + d.Z] == c;
+                if (z > 0) v += (int)labels[i - 1] == c;
+                if (z < d.Z - 1) v += (int)labels[i + 1] == c;
+                if (v) {
+                    if (r[k] != cur) {
+                        if (votes && best[cur] != FH_OPEN) atomicAdd(cnt + cur, votes);
+                        cur = r[k]; votes = 0ull;
+                    }
+                    votes += (unsigned long long)v;
+                }
+            }
+            next_coords(d, x, y, z);
+        }
+        if (votes && best[cur] != FH_OPEN) atomicAdd(cnt + cur, votes);
+    }
+}
+
+__global__ __launch_bounds__(CC_THREADS) void fh_fold_kernel(const int* __restrict__ roots, unsigned long long* __restrict__ best,
+                                                             unsigned long long* __restrict__ cnt, int n, int c) {
+    const long stride = (long)gridDim.x * CC_THREADS;
+    for (long i = (long)blockIdx.x * CC_THREADS + threadIdx.x; i < n; i += stride) {
+        if (roots[i] != (int)i) continue;
+        const unsigned long long v = cnt[i];
+        if (v == 0ull) continue;                                                 // (an open component never counts: v > 0 is a cavity)
+        const unsigned long long key = (v << 4) | (unsigned long long)(15 - c);
+        if (key > best[i]) best[i] = key;
+        cnt[i] = 0ull;
+    }
+}
+
+// labels / out may be the same pointer: a voxel is read and written by the same thread, and by no other
+__global__ __launch_bounds__(CC_THREADS) void fh_fill_kernel(const uint8_t* labels, const int* __restrict__ roots,
+                                                             const unsigned long long* __restrict__ best, int n, unsigned class_mask,
+                                                             CcHeader* hdr, uint8_t* out) {
+    __shared__ unsigned long long s_vox[CC_MAXK], s_cav[CC_MAXK];
+    if (threadIdx.x < CC_MAXK) { s_vox[threadIdx.x] = 0ull; s_cav[threadIdx.x] = 0ull; }
+    __syncthreads();
+    const bool aligned4 = (((uintptr_t)labels) & 3) == 0;
+    const long ngroups = ((long)n + 3) / 4, stride = (long)gridDim.x * CC_THREADS;
+    for (long g = (long)blockIdx.x * CC_THREADS + threadIdx.x; g < ngroups; g += stride) {
+        const long i0 = g * 4;
+        uint32_t w = load4(labels, i0, n, aligned4);
+        int r[4];
+        load4i(roots, i0, n, r);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (r[k] < 0) continue;                                               // (label 0 from here on)
+            const unsigned long long b = best[r[k]];
+            if (b == FH_OPEN) continue;
+            unsigned win = b ? 15u - (unsigned)(b & 15ull) : 0u;                    // 0: no vote at all
+            if (!((class_mask >> win) & 1u)) win = 0u;                            // (bit 0 is never set)
+            atomicAdd(&s_vox[win], 1ull);
+            if (r[k] == (int)(i0 + k)) atomicAdd(&s_cav[win], 1ull);
+            w |= win << (8 * k);
+        }
+        store4b(out, i0, n, w);
+    }
+    __syncthreads();
+    if (threadIdx.x < CC_MAXK && s_vox[threadIdx.x]) {
+        atomicAdd(&hdr->total[threadIdx.x], s_vox[threadIdx.x]);
+        if (s_cav[threadIdx.x]) atomicAdd(&hdr->ncomp[threadIdx.x], s_cav[threadIdx.x]);
+    }
+}
+
+__global__ void fh_report_kernel(const CcHeader* __restrict__ hdr, int K, long long* __restrict__ report) {
+    const int c = (int)threadIdx.x;
+    if (c < K) { report[2 * c + 0] = (long long)hdr->ncomp[c]; report[2 * c + 1] = (long long)hdr->total[c]; }
+}
+
 inline int cc_grid(long work_items) {
     const long b = (work_items + CC_THREADS - 1) / CC_THREADS;
     return (int)(b < 1 ? 1 : (b > CC_MAX_BLOCKS ? CC_MAX_BLOCKS : b));
@@ -372,6 +559,25 @@ int cc_check_shape(const char* who, const int64_t* shape, int32_t n_classes, lon
 int cc_check_connectivity(const char* who, int32_t connectivity) {
     if (connectivity != 6 && connectivity != 18 && connectivity != 26)
         return fail(MPU_EINVAL, "%s: connectivity must be 6, 18 or 26, got %ld", who, (long)connectivity);
+    return MPU_OK;
+}
+
+inline long fh_round(long bytes) { return (bytes + 255) / 256 * 256; }
+// every check of a filter entry (mpu_remove_small_components, mpu_fill_holes), in the order of mpu_keep_largest_components
+int cc_check_filter(const char* who, const int64_t* shape, int32_t connectivity, int32_t n_classes, uint32_t class_mask,
+                    const uint8_t* d_labels, const uint8_t* d_out, const int64_t* d_report, const void* d_scratch, long* n_out) {
+    int rc = cc_check_shape(who, shape, n_classes, n_out);
+    if (rc != MPU_OK) return rc;
+    if ((rc = cc_check_connectivity(who, connectivity)) != MPU_OK) return rc;
+    if ((class_mask & 1u) || (class_mask >> n_classes) != 0u)
+        return fail(MPU_EINVAL, "%s: class_mask may name classes 1 .. n_classes - 1 only (mask 0x%lx, n_classes %ld)", who,
+                    (long)class_mask, (long)n_classes);
+    if (!d_labels || !d_out || !d_report || !d_scratch) return fail(MPU_EINVAL, "%s: null argument", who);
+    if (((uintptr_t)d_report % 8) != 0 || ((uintptr_t)d_scratch % 16) != 0)
+        return fail(MPU_EINVAL, "%s: d_report must be aligned to 8 bytes and d_scratch to 16", who);
+    const uintptr_t a = (uintptr_t)d_labels, b = (uintptr_t)d_out, n = (uintptr_t)*n_out;
+    if (!(a == b || a + n <= b || b + n <= a))
+        return fail(MPU_EINVAL, "%s: d_out must be d_labels itself (in place) or not overlap it", who);
     return MPU_OK;
 }
 
@@ -445,9 +651,67 @@ int mpu_keep_largest_components(const uint8_t* d_labels, const int64_t shape[3],
     if ((rc = cc_label(d_labels, d, connectivity, n_classes, hdr, parent, roots, st)) != MPU_OK) return rc;
     const int grid4 = cc_grid((n + 3) / 4);
     cc_count_kernel<<<dim3(grid4), dim3(CC_THREADS), 0, st>>>(roots, parent, d.n);
-    cc_select_kernel<<<dim3(grid4), dim3(CC_THREADS), 0, st>>>(d_labels, roots, parent, d.n, hdr);
+    cc_select_kernel<false><<<dim3(grid4), dim3(CC_THREADS), 0, st>>>(d_labels, roots, parent, d.n, hdr, 0ll);
     cc_apply_kernel<<<dim3(cc_grid((n + 15) / 16)), dim3(CC_THREADS), 0, st>>>(d_labels, roots, d.n, n_classes, class_mask, hdr, d_out,
                                                                               (long long*)d_report);
+    return launch_ok();
+}
+
+int64_t mpu_fill_holes_scratch_bytes(const int64_t shape[3]) {
+    long n = 0;
+    if (cc_check_shape("mpu_fill_holes_scratch_bytes", shape, 1, &n) != MPU_OK) return -1;
+    return CC_HEADER_BYTES + 2 * cc_array_bytes(n) + fh_round(n) + 2 * fh_round(8 * n);
+}
+
+int mpu_remove_small_components(const uint8_t* d_labels, const int64_t shape[3], int32_t connectivity, int32_t n_classes,
+                                uint32_t class_mask, int64_t min_voxels, uint8_t* d_out, int64_t* d_report, void* d_scratch,
+                                void* stream) {
+    const char* who = "mpu_remove_small_components";
+    long n = 0;
+    int rc = cc_check_filter(who, shape, connectivity, n_classes, class_mask, d_labels, d_out, d_report, d_scratch, &n);
+    if (rc != MPU_OK) return rc;
+    if (min_voxels < 1) return fail(MPU_EINVAL, "%s: min_voxels must be >= 1, got %ld", who, (long)min_voxels);
+    const CcDims d = {(int)shape[0], (int)shape[1], (int)shape[2], (int)n};
+    hipStream_t st = (hipStream_t)stream;
+    char* s = (char*)d_scratch;
+    CcHeader* hdr = (CcHeader*)s;
+    int* parent = (int*)(s + CC_HEADER_BYTES);
+    int* roots = (int*)(s + CC_HEADER_BYTES + cc_array_bytes(n));
+    if ((rc = cc_label(d_labels, d, connectivity, n_classes, hdr, parent, roots, st)) != MPU_OK) return rc;
+    const int grid4 = cc_grid((n + 3) / 4);
+    cc_count_kernel<<<dim3(grid4), dim3(CC_THREADS), 0, st>>>(roots, parent, d.n);
+    cc_select_kernel<true><<<dim3(grid4), dim3(CC_THREADS), 0, st>>>(d_labels, roots, parent, d.n, hdr, (long long)min_voxels);
+    cc_drop_small_kernel<<<dim3(grid4), dim3(CC_THREADS), 0, st>>>(d_labels, roots, parent, d.n, n_classes, class_mask,
+                                                                  (long long)min_voxels, hdr, d_out, (long long*)d_report);
+    return launch_ok();
+}
+
+int mpu_fill_holes(const uint8_t* d_labels, const int64_t shape[3], int32_t connectivity, int32_t n_classes, uint32_t class_mask,
+                   uint8_t* d_out, int64_t* d_report, void* d_scratch, void* stream) {
+    const char* who = "mpu_fill_holes";
+    long n = 0;
+    int rc = cc_check_filter(who, shape, connectivity, n_classes, class_mask, d_labels, d_out, d_report, d_scratch, &n);
+    if (rc != MPU_OK) return rc;
+    const CcDims d = {(int)shape[0], (int)shape[1], (int)shape[2], (int)n};
+    hipStream_t st = (hipStream_t)stream;
+    char* s = (char*)d_scratch;
+    CcHeader* hdr = (CcHeader*)s;
+    int* parent = (int*)(s + CC_HEADER_BYTES);
+    int* roots = (int*)(s + CC_HEADER_BYTES + cc_array_bytes(n));
+    uint8_t* bg = (uint8_t*)(s + CC_HEADER_BYTES + 2 * cc_array_bytes(n));
+    unsigned long long* best = (unsigned long long*)(bg + fh_round(n));
+    unsigned long long* cnt = (unsigned long long*)((char*)best + fh_round(8 * n));
+    const int grid4 = cc_grid((n + 3) / 4), grid1 = cc_grid(n);
+    fh_background_kernel<<<dim3(grid4), dim3(CC_THREADS), 0, st>>>(d_labels, bg, d.n);
+    if ((rc = cc_label(bg, d, connectivity, 2, hdr, parent, roots, st)) != MPU_OK) return rc;      // (zeroes the header)
+    fh_init_kernel<<<dim3(grid1), dim3(CC_THREADS), 0, st>>>(roots, best, cnt, d.n);
+    fh_border_kernel<<<dim3(grid1), dim3(CC_THREADS), 0, st>>>(roots, d, best);
+    for (int c = 1; c < n_classes; ++c) {
+        fh_vote_kernel<<<dim3(grid4), dim3(CC_THREADS), 0, st>>>(d_labels, roots, best, cnt, d, c);
+        fh_fold_kernel<<<dim3(grid1), dim3(CC_THREADS), 0, st>>>(roots, best, cnt, d.n, c);
+    }
+    fh_fill_kernel<<<dim3(grid4), dim3(CC_THREADS), 0, st>>>(d_labels, roots, best, d.n, class_mask, hdr, d_out);
+    fh_report_kernel<<<dim3(1), dim3(64), 0, st>>>(hdr, n_classes, (long long*)d_report);
     return launch_ok();
 }
 

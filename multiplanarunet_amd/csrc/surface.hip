@@ -26,6 +26,9 @@
 // two-stage f64 sums) and compacted into one key list (non-negative doubles order like their bit patterns); the two order
 // statistics NumPy's linear percentile needs are found by an exact 8 x 8-bit radix select on that list. The root and the
 // interpolation of the percentile are the host's (NumPy's own arithmetic).
+//
+// Opening / closing by a Euclidean ball (`mp predict --open_mm / --close_mm`, mpu_morph_ball) are two thresholds of the same three
+// passes; their kernels and the one change they need in a pass (a scan cut off at the radius) stand with mpu_morph_ball's kernels.
 #include "common.h"
 #include <math.h>
 
@@ -127,9 +130,12 @@ __global__ __launch_bounds__(SD_THREADS) void edt_start_x_kernel(const int* __re
 
 // Y / X pass over lines of `len` elements `stride` apart: out[i] = min over k of fl(fl(w k^2) + in[i + k stride]); start[i / stride]
 // is the line's table entry above. ROOT: the last pass of a caller who wants distances stores sqrt of it.
-template <bool ROOT>
+// CUT (mpu_morph_ball, which only asks whether the result is <= cut): the scan also stops once fl(w k^2) > cut. Every candidate
+// it skips is >= fl(w k^2) > cut (g >= 0, fl monotone), so a result <= cut is still the exact minimum and any other result is
+// still > cut -- also through the next pass, where a value > cut can only make candidates > cut.
+template <bool ROOT, bool CUT>
 __global__ __launch_bounds__(SD_THREADS) void edt_line_kernel(const double* __restrict__ in, double* __restrict__ out, long n, long stride,
-                                                              int len, double w, const int* __restrict__ start) {
+                                                              int len, double w, const int* __restrict__ start, double cut) {
     const long step = (long)gridDim.x * SD_THREADS;
     for (long i = (long)blockIdx.x * SD_THREADS + threadIdx.x; i < n; i += step) {
         const long line = i / stride;
@@ -143,6 +149,7 @@ __global__ __launch_bounds__(SD_THREADS) void edt_line_kernel(const double* __re
             const double dk = (double)k;
             const double a = w * (dk * dk);
             if (!(a < best)) break;
+            if (CUT && a > cut) break;
             if (k <= nlo) { const double c = a + in[i - (long)k * stride]; best = c < best ? c : best; }
             if (k <= nhi) { const double c = a + in[i + (long)k * stride]; best = c < best ? c : best; }
         }
@@ -344,8 +351,9 @@ inline SdScratch sd_carve(void* d_scratch, const SdDims& d) {
 }
 
 // the three passes: Z -> out, Y -> tmp, X -> out
+// cut >= 0: only `result <= cut` is asked of the output (see edt_line_kernel); root must be false then
 int edt_launch(const uint8_t* labels, const SdDims& d, const double* spacing, int mode, int v, bool root, double* out, double* tmp,
-               const SdScratch& s, hipStream_t st) {
+               const SdScratch& s, hipStream_t st, double cut = -1.0) {
     const double wx = spacing[0] * spacing[0], wy = spacing[1] * spacing[1], wz = spacing[2] * spacing[2];
     const long nlines = (long)d.X * d.Y;
     const int gz = sd_grid(nlines * 64, SD_MAX_BLOCKS * 4), gl = sd_grid(d.n, SD_MAX_BLOCKS * 4);
@@ -356,10 +364,61 @@ int edt_launch(const uint8_t* labels, const SdDims& d, const double* spacing, in
     }
     edt_start_y_kernel<<<dim3(sd_grid(nlines, SD_MAX_BLOCKS)), dim3(SD_THREADS), 0, st>>>(s.line_flag, d.X, d.Y, s.start_y);
     edt_start_x_kernel<<<dim3(sd_grid(d.X, SD_MAX_BLOCKS)), dim3(SD_THREADS), 0, st>>>(s.start_y, d.X, d.Y, s.start_x);
-    edt_line_kernel<false><<<dim3(gl), dim3(SD_THREADS), 0, st>>>(out, tmp, (long)d.n, (long)d.Z, d.Y, wy, s.start_y);
-    if (root) edt_line_kernel<true><<<dim3(gl), dim3(SD_THREADS), 0, st>>>(tmp, out, (long)d.n, (long)d.Y * d.Z, d.X, wx, s.start_x);
-    else edt_line_kernel<false><<<dim3(gl), dim3(SD_THREADS), 0, st>>>(tmp, out, (long)d.n, (long)d.Y * d.Z, d.X, wx, s.start_x);
+    if (cut >= 0.0) {
+        edt_line_kernel<false, true><<<dim3(gl), dim3(SD_THREADS), 0, st>>>(out, tmp, (long)d.n, (long)d.Z, d.Y, wy, s.start_y, cut);
+        edt_line_kernel<false, true><<<dim3(gl), dim3(SD_THREADS), 0, st>>>(tmp, out, (long)d.n, (long)d.Y * d.Z, d.X, wx, s.start_x, cut);
+        return launch_ok();
+    }
+    edt_line_kernel<false, false><<<dim3(gl), dim3(SD_THREADS), 0, st>>>(out, tmp, (long)d.n, (long)d.Z, d.Y, wy, s.start_y, 0.0);
+    if (root) edt_line_kernel<true, false><<<dim3(gl), dim3(SD_THREADS), 0, st>>>(tmp, out, (long)d.n, (long)d.Y * d.Z, d.X, wx, s.start_x, 0.0);
+    else edt_line_kernel<false, false><<<dim3(gl), dim3(SD_THREADS), 0, st>>>(tmp, out, (long)d.n, (long)d.Y * d.Z, d.X, wx, s.start_x, 0.0);
     return launch_ok();
+}
+
+// ---- mpu_morph_ball: opening / closing by a Euclidean ball as two thresholds of the transform above ------------------------------
+// With r2 = fl(radius * radius): dilate(M) = {d2(., M) <= r2}, erode(M) = {d2(., not M) > r2}; close = erode(dilate), open =
+// dilate(erode). Per class c of the mask, ascending, on the map `out` the earlier classes left (launches: 5 + 1 + 5 + 1):
+//   close   A = d2 to {out == c};  mask = A <= r2 (the dilation);  A = d2 to {mask == 0};  out = c where out == 0 and A > r2
+//   open    A = d2 to {out != c};  mask = A >  r2 (the erosion);   A = d2 to {mask == 1};  out = 0 where out == c and not A <= r2
+// d2 is symmetric in its two voxels, so M is inside close(M) and open(M) inside M: closing only ever adds, opening only removes.
+// The mask is one byte per voxel in the key-list region of the scratch, which the transform does not use.
+__global__ __launch_bounds__(SD_THREADS) void mb_begin_kernel(const uint8_t* labels, uint8_t* out, long n, long long* __restrict__ report,
+                                                              int words) {
+    if (blockIdx.x == 0)
+        for (int t = threadIdx.x; t < words; t += SD_THREADS) report[t] = 0ll;
+    if (labels == out) return;
+    const long step = (long)gridDim.x * SD_THREADS;
+    for (long i = (long)blockIdx.x * SD_THREADS + threadIdx.x; i < n; i += step) out[i] = labels[i];
+}
+
+__global__ __launch_bounds__(SD_THREADS) void mb_threshold_kernel(const double* __restrict__ D, double r2, int op, uint8_t* __restrict__ mask,
+                                                                  long n) {
+    const long step = (long)gridDim.x * SD_THREADS;
+    for (long i = (long)blockIdx.x * SD_THREADS + threadIdx.x; i < n; i += step) {
+        const bool within = D[i] <= r2;
+        mask[i] = (op == MPU_MORPH_CLOSE ? within : !within) ? 1 : 0;
+    }
+}
+
+// *counter += the voxels rewritten (one atomic per workgroup that rewrote any)
+__global__ __launch_bounds__(SD_THREADS) void mb_apply_kernel(uint8_t* out, const double* __restrict__ D, double r2, int op, int c, long n,
+                                                              unsigned long long* counter) {
+    __shared__ unsigned long long s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0ull;
+    __syncthreads();
+    const long step = (long)gridDim.x * SD_THREADS;
+    unsigned long long cnt = 0ull;
+    for (long i = (long)blockIdx.x * SD_THREADS + threadIdx.x; i < n; i += step) {
+        const int v = (int)out[i];
+        if (op == MPU_MORPH_CLOSE) {
+            if (v == 0 && D[i] > r2) { out[i] = (uint8_t)c; ++cnt; }
+        } else {
+            if (v == c && !(D[i] <= r2)) { out[i] = 0; ++cnt; }
+        }
+    }
+    if (cnt) atomicAdd(&s_cnt, cnt);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(counter, s_cnt);
 }
 
 }  // namespace
@@ -430,6 +489,45 @@ int mpu_surface_table(const uint8_t* d_pred, const uint8_t* d_truth, const int64
             sd_hist_kernel<<<dim3(gh), dim3(SD_THREADS), 0, st>>>(s.list, s.hdr, shift);
             sd_pick_kernel<<<dim3(1), dim3(SD_THREADS), 0, st>>>(s.hdr, shift, row);
         }
+    }
+    return launch_ok();
+}
+
+int mpu_morph_ball(const uint8_t* d_labels, const int64_t shape[3], const double spacing[3], int32_t n_classes, uint32_t class_mask,
+                   int32_t op, double radius, uint8_t* d_out, int64_t* d_report, void* d_scratch, void* stream) {
+    const char* who = "mpu_morph_ball";
+    long n = 0;
+    int rc = sd_check_shape(who, shape, &n);
+    if (rc != MPU_OK) return rc;
+    if (n_classes < 1 || n_classes > SD_MAXK) return fail(MPU_EUNSUPPORTED, "%s: need 1 <= n_classes <= 16, got %ld", who, (long)n_classes);
+    if ((rc = sd_check_spacing(who, spacing)) != MPU_OK) return rc;
+    if ((class_mask & 1u) || (class_mask >> n_classes) != 0u)
+        return fail(MPU_EINVAL, "%s: class_mask may name classes 1 .. n_classes - 1 only (mask 0x%lx, n_classes %ld)", who,
+                    (long)class_mask, (long)n_classes);
+    if (op != MPU_MORPH_OPEN && op != MPU_MORPH_CLOSE)
+        return fail(MPU_EINVAL, "%s: op must be MPU_MORPH_OPEN or MPU_MORPH_CLOSE, got %ld", who, (long)op);
+    if (!(radius > 0.0) || !(radius < __builtin_huge_val())) return fail(MPU_EINVAL, "%s: radius must be finite and > 0", who);
+    MPU_REQUIRE(d_labels && d_out && d_report && d_scratch, "mpu_morph_ball: null argument");
+    MPU_REQUIRE(((uintptr_t)d_report % 8) == 0 && ((uintptr_t)d_scratch % 16) == 0,
+                "mpu_morph_ball: d_report must be aligned to 8 bytes and d_scratch to 16");
+    const uintptr_t a = (uintptr_t)d_labels, b = (uintptr_t)d_out;
+    MPU_REQUIRE(a == b || a + (uintptr_t)n <= b || b + (uintptr_t)n <= a,
+                "mpu_morph_ball: d_out must be d_labels itself (in place) or not overlap it");
+    const SdDims d = {(int)shape[0], (int)shape[1], (int)shape[2], (int)n};
+    hipStream_t st = (hipStream_t)stream;
+    const SdScratch s = sd_carve(d_scratch, d);
+    uint8_t* mask = (uint8_t*)s.list;
+    unsigned long long* report = (unsigned long long*)d_report;
+    const double r2 = radius * radius;
+    const int g = sd_grid(n, SD_MAX_BLOCKS);
+    mb_begin_kernel<<<dim3(g), dim3(SD_THREADS), 0, st>>>(d_labels, d_out, n, (long long*)d_report, 2 * n_classes);
+    for (int c = 1; c < n_classes; ++c) {
+        if (!((class_mask >> c) & 1u)) continue;
+        const bool closing = op == MPU_MORPH_CLOSE;
+        if ((rc = edt_launch(d_out, d, spacing, closing ? MPU_EDT_EQUAL : MPU_EDT_NOT_EQUAL, c, false, s.A, s.B, s, st, r2)) != MPU_OK) return rc;
+        mb_threshold_kernel<<<dim3(g), dim3(SD_THREADS), 0, st>>>(s.A, r2, op, mask, n);
+        if ((rc = edt_launch(mask, d, spacing, MPU_EDT_EQUAL, closing ? 0 : 1, false, s.A, s.B, s, st, r2)) != MPU_OK) return rc;
+        mb_apply_kernel<<<dim3(g), dim3(SD_THREADS), 0, st>>>(d_out, s.A, r2, op, c, n, report + 2 * c + (closing ? 0 : 1));
     }
     return launch_ok();
 }
