@@ -271,6 +271,48 @@ int mpu_map_accumulate_view_linear(const mpu_voxel_grid* grid, const mpu_view_pr
                                    int32_t p_lo, int32_t p_hi, int32_t owns_oob,
                                    float* d_z, void* stream);
 
+/* Per-voxel uncertainty of the multi-view fusion, in the pass that fuses. For a
+ * voxel let x_v (v = 0..V-1) be the f32 K-vector it reads from view v (exactly
+ * what mpu_map_view_nearest / mpu_map_view_linear give, the fill vector
+ * [1,0,...,0] outside the view's box included) and p what mpu_map_fuse_views
+ * [_linear] computes from them. With
+ *   Hn(q) = -sum_k (q_k/s) ln(q_k/s) / ln K,  s = sum_k q_k
+ * (terms with q_k <= 0 contribute 0; s <= 0 gives 0; K = 1 gives 0):
+ *   d_entropy   f32 [X,Y,Z]  Hn(p), in [0,1]
+ *   d_mi        f32 [X,Y,Z]  max(0, Hn(mean_v x^_v) - mean_v Hn(x^_v)),
+ *                            x^_v = x_v / sum_k x_v[k] (0 when that sum is <= 0),
+ *                            unweighted means in view order
+ *   d_agreement u8  [X,Y,Z]  number of views whose own argmax (first maximum,
+ *                            strict >) equals the fused label of this call
+ * linear != 0: the views are read as mpu_map_fuse_views_linear reads them, else
+ * as mpu_map_fuse_views. d_probs / d_labels (either or both may be NULL) are
+ * byte for byte what those calls give; the kernel is their exact form (no
+ * straight-line variant). Each map pointer may be NULL, not all three. f32
+ * logf and f32 sums: entropy within 1e-5, mi within 3e-5 of fp64.
+ * MPU_EINVAL (message in mpu_last_error(), before any HIP call): NULL grid or
+ * views, n_classes or n_views outside 1..16, all three maps NULL, W or b
+ * missing without sum_fusion, a NULL view field.
+ *
+ * mpu_uncertainty_table: one pass over a label map d_labels u8 [n] (classes
+ * >= n_classes are skipped), the three maps (each may be NULL: its sums are 0;
+ * entropy and mi are clamped to [0,1], NaN counts as 0) and optionally a truth
+ * map d_truth u8 [n]. d_table f64 [K][3][4]: per class c of d_labels and group
+ * (0 all, 1 correct: truth == c, 2 wrong; 1 and 2 are zero when d_truth is
+ * NULL) the voxel count and the sums of entropy, mi and agreement. Sums are
+ * integers (entropy and mi in 2^-32 fixed point), so two calls give identical
+ * bytes. 0 <= n < 2^31. d_scratch: mpu_uncertainty_table_scratch_bytes(n, K)
+ * bytes, 8-byte aligned as d_table (0 for n_classes outside 1..16). */
+int mpu_map_fuse_views_uncertainty(const mpu_voxel_grid* grid, const mpu_view_pred* views,
+                                   int32_t n_views, int32_t n_classes,
+                                   const float* d_W, const float* d_b, int32_t sum_fusion, int32_t linear,
+                                   float* d_probs, uint8_t* d_labels,
+                                   float* d_entropy, float* d_mi, uint8_t* d_agreement,
+                                   void* stream);
+size_t mpu_uncertainty_table_scratch_bytes(int64_t n, int32_t n_classes);
+int mpu_uncertainty_table(const uint8_t* d_labels, const uint8_t* d_truth, const float* d_entropy,
+                          const float* d_mi, const uint8_t* d_agreement, int64_t n, int32_t n_classes,
+                          double* d_table, void* d_scratch, void* stream);
+
 
 /* ------------------------------------------------------------------------ *
  * 2-D U-Net (MFMA-bound): mpunet.models.UNet (mpunet/models/unet.py:20-251)

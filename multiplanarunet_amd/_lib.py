@@ -127,6 +127,10 @@ _SIGS = {
                                                  i32, i32, i32, c_p, c_p]),
     "mpu_map_fuse_views_linear": (C.c_int, [C.POINTER(VoxelGrid), C.POINTER(ViewPred), i32, i32,
                                             c_p, c_p, i32, c_p, c_p, c_p]),
+    "mpu_map_fuse_views_uncertainty": (C.c_int, [C.POINTER(VoxelGrid), C.POINTER(ViewPred), i32, i32,
+                                                 c_p, c_p, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "mpu_uncertainty_table_scratch_bytes": (C.c_size_t, [i64, i32]),
+    "mpu_uncertainty_table": (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, i32, c_p, c_p, c_p]),
     "mpu_fusion_forward": (C.c_int, [c_p, i64, i32, i32, c_p, c_p, c_p, c_p, c_p]),
     "mpu_fusion_finalize": (C.c_int, [c_p, i64, i32, c_p, i32, c_p, c_p, c_p]),
     "mpu_unet_create": (c_p, [C.POINTER(UNetConfig)]),

@@ -17,6 +17,13 @@ from the report tables. Without these flags nothing of it is imported or launche
 --surface_metrics [--nsd_tolerance MM] (no reference counterpart; surface.py): rank 0 also evaluates that saved map against the labels
 by surface distances on the device -- HD, HD95, ASSD and the voxel-border NSD per foreground class, with the voxel sizes of the
 affine -- and writes csv/surface_results.csv. No other output changes, and without the flag surface.py is not imported.
+--uncertainty [--uncertainty_maps entropy,mi,agreement] (no reference counterpart; uncertainty.py): the final fuse also gives, per
+voxel, the entropy of the fused distribution, the mutual information between the views and the number of views that vote for the
+winning class -- <id>_ENTROPY / _MI / _AGREE.nii.gz beside <id>_PRED.nii.gz, or the keys entropy / mi / agreement of the .npz; they
+are properties of the fusion, so clean-up and the filter do not alter them -- and csv/uncertainty_results.csv has their means per
+class of the map that is saved (over the correct and the wrong voxels too when the volume has labels). One GPU and softmax models
+only: refused before a folder is created otherwise. The prediction is the same bytes, and without the flag uncertainty.py is not
+imported.
 """
 import os
 from argparse import ArgumentParser
@@ -83,7 +90,42 @@ def get_argparser():
                         "ASSD and NSD (on the device; csv/surface_results.csv; off by default)")
     p.add_argument("--nsd_tolerance", type=float, default=None,
                    help="tolerance of the NSD of --surface_metrics, in the units of the affine (default 1.0)")
+    p.add_argument("--uncertainty", action="store_true",
+                   help="also save per-voxel uncertainty maps of the multi-view fusion: <id>_ENTROPY (entropy of the fused "
+                        "distribution), <id>_MI (spread between the views) and <id>_AGREE (views that vote for the winning class), "
+                        "and csv/uncertainty_results.csv (on the device, one GPU, softmax models; off by default)")
+    p.add_argument("--uncertainty_maps", type=str, default=None,
+                   help="comma-separated maps --uncertainty computes, out of entropy,mi,agreement (default: all three)")
     return p
+
+
+UNCERTAINTY_SUFFIX = (("entropy", "ENTROPY"), ("mi", "MI"), ("agreement", "AGREE"))      # map name, <id>_<SUFFIX>.nii.gz
+
+
+def uncertainty_plan(args, out_activation=None):
+    """The --uncertainty flags, checked: None when the maps are off, else the tuple of map names in the order entropy, mi,
+    agreement. ValueError on a combination that cannot be served; with out_activation also on a model whose outputs are logits."""
+    on, names = bool(getattr(args, "uncertainty", False)), getattr(args, "uncertainty_maps", None)
+    if not on:
+        if names is not None:
+            raise ValueError("--uncertainty_maps needs --uncertainty")
+        return None
+    if int(getattr(args, "num_GPUs", 1) or 1) > 1:
+        raise ValueError("--uncertainty cannot be combined with --num_GPUs > 1: the plane-sharded predict keeps only the weighted sum "
+                         "of the views per voxel, agreement and mutual information need every view at the voxel")
+    if out_activation is not None and str(out_activation).lower() == "linear":
+        raise ValueError("--uncertainty needs a model with out_activation: softmax: the vectors of an out_activation: linear model "
+                         "are logits, not distributions")
+    known = [n for n, _ in UNCERTAINTY_SUFFIX]
+    if names is None:
+        return tuple(known)
+    asked = [n.strip() for n in str(names).split(",") if n.strip() != ""]
+    for n in asked:
+        if n not in known:
+            raise ValueError("--uncertainty_maps: unknown map %r (known: %s)" % (n, ", ".join(known)))
+    if not asked:
+        raise ValueError("--uncertainty_maps: no map named")
+    return tuple(n for n in known if n in asked)
 
 
 def surface_metrics_plan(args):
@@ -202,14 +244,17 @@ def plan_todo(items, dst_of, continue_, overwrite):
     """(items to predict, first conflicting output or None). What there is to do is settled from the FINAL output names alone, so
     that a volume whose output exists is never read; an output that exists without --overwrite / --continue stops the run where
     the loop reaches it. A temporary file a killed run left behind (prediction_writer.temp_path) is no output: its volume is
-    predicted again and the file is overwritten."""
+    predicted again and the file is overwritten. dst_of may give several names (--uncertainty: the maps beside the prediction):
+    the volume is done when all of them exist, and any of them that exists is a conflict."""
     todo, conflict = [], None
     for item in items:
-        dst = dst_of(item)
-        if os.path.exists(dst) and continue_:
+        dsts = dst_of(item)
+        dsts = [dsts] if isinstance(dsts, str) else list(dsts)
+        have = [d for d in dsts if os.path.exists(d)]
+        if len(have) == len(dsts) and continue_:
             continue
-        if os.path.exists(dst) and not overwrite:
-            conflict = dst
+        if have and not overwrite and not (continue_ and len(dsts) > 1):
+            conflict = have[0]
             break
         todo.append(item)
     return todo, conflict
@@ -228,7 +273,10 @@ def run(args):
     cc = component_filter_plan(args)                      # (flag combinations: refused before anything is looked at)
     sm = surface_metrics_plan(args)
     cl = cleanup_plan(args)
+    unc = uncertainty_plan(args)
     validate_project_dir(project_dir)
+    if unc is not None:                                   # the model's output against the maps' meaning, before anything is created
+        unc = uncertainty_plan(args, load_hparams(project_dir)["build"].get("out_activation"))
     if cc is not None:                                    # the classes against the project's, before anything is loaded or created
         cc = component_filter_plan(args, load_hparams(project_dir)["build"]["n_classes"])
     if cl is not None:
@@ -239,6 +287,9 @@ def run(args):
     if args.force_GPU:
         os.environ["HIP_VISIBLE_DEVICES"] = args.force_GPU
     rank, world, device = D.init_from_env()
+    if unc is not None and world > 1:
+        raise ValueError("--uncertainty cannot be combined with a sharded predict (%d ranks): agreement and mutual information need "
+                         "every view at the voxel" % world)
     log = (lambda *a, **k: print(*a, flush=True)) if rank == 0 else (lambda *a, **k: None)
     hp = load_hparams(project_dir)
     fit, build = hp["fit"], hp["build"]
@@ -277,7 +328,7 @@ def run(args):
     nii = os.path.join(out_dir, "nii_files")
     if rank == 0:
         os.makedirs(nii, exist_ok=True)
-    results, per_view, surface, cleanup = {}, {}, {}, []
+    results, per_view, surface, cleanup, unc_rows = {}, {}, {}, [], {}
 
     def plan(item):
         """(write a NIfTI file?, output folder, output file) of a volume or a dataset entry."""
@@ -288,7 +339,18 @@ def run(args):
         out_base = os.path.join(nii, item.identifier) if args.save_input_files else nii
         return as_nii, out_base, os.path.join(out_base, "%s_PRED.%s" % (item.identifier, "nii.gz" if as_nii else "npz"))
 
-    todo, conflict = plan_todo(vols, lambda item: plan(item)[2], args.continue_, args.overwrite)
+    def unc_path(dst, suffix):
+        """<id>_<SUFFIX>.nii.gz beside <id>_PRED.nii.gz"""
+        return dst[:-len("PRED.nii.gz")] + suffix + ".nii.gz"
+
+    def outputs(item):
+        """Every file that makes up a volume's output: the prediction and, for NIfTI outputs, the --uncertainty maps beside it."""
+        as_nii, _, dst = plan(item)
+        if unc is None or not as_nii:
+            return dst
+        return [dst] + [unc_path(dst, suf) for name, suf in UNCERTAINTY_SUFFIX if name in unc]
+
+    todo, conflict = plan_todo(vols, outputs, args.continue_, args.overwrite)
     if lazy:                                              # at most the current and the next volume are loaded
         from ..volume_queue import LazyQueue, Dataset
         todo = LazyQueue(Dataset(todo, key), logger=log)
@@ -310,14 +372,15 @@ def run(args):
                                                    map_method=args.map_method)
                 probs, labels = res if args.no_argmax else (None, res)
             else:
-                pve = None
+                pve, umaps = None, (None if unc is None else {"maps": unc})
                 if v.labels is not None and not args.no_eval:     # bin/predict.py:334-346: per-view Dice inside the loop
                     rows = per_view.setdefault(v.identifier, {})
                     pve = dict(eval_prob=args.eval_prob, n_classes=build["n_classes"], log=log,
                                report=lambda i, view, vd, md, mean, rows=rows: rows.__setitem__(i, (view, vd, md, float(mean))))
                 probs, labels = multi_view_predict(model, v, views, build["dim"], fit["real_space_span"], fm,
                                                    sum_fusion=args.sum_fusion, batch_size=None,
-                                                   want_probs=args.no_argmax, per_view_eval=pve, map_method=args.map_method)
+                                                   want_probs=args.no_argmax, per_view_eval=pve, map_method=args.map_method,
+                                                   **({} if umaps is None else {"uncertainty": umaps}))
             if rank == 0 and cl is not None:                  # open -> close -> fill holes -> size threshold, before the filter below
                 from .. import surface as edt            # (the ball's spacing: the voxel sizes of the affine)
                 labels = labels.contiguous()
@@ -356,7 +419,21 @@ def run(args):
                     out = {"labels": labels.cpu().numpy(), "affine": v.affine}
                     if args.no_argmax and probs is not None:
                         out["probs"] = probs.cpu().numpy()
+                    if unc is not None:                   # (properties of the fusion: clean-up and the filter do not alter them)
+                        out.update({name: umaps[name].cpu().numpy() for name in unc})
                     writer.submit_npz(dst, out)
+                if unc is not None:
+                    from ..uncertainty import uncertainty_table
+                    if as_nii:
+                        for name, suf in UNCERTAINTY_SUFFIX:
+                            if name in unc:
+                                put_nifti(unc_path(dst, suf), umaps[name], v.affine)
+                    # the map that was saved (after clean-up and the filter), against the labels when the volume has them
+                    t = uncertainty_table(labels.contiguous(), {name: umaps[name] for name in unc}, build["n_classes"],
+                                          truth=None if v.labels is None else v.labels.reshape(labels.shape).contiguous())
+                    unc_rows[v.identifier] = t
+                    log("%s: uncertainty per class: mean entropy %s mean mi %s mean agreement %s"
+                        % (v.identifier, np.round(t["mean_entropy"], 4), np.round(t["mean_mi"], 4), np.round(t["mean_agreement"], 3)))
                 if v.labels is not None and not args.no_eval:
                     d = dice_all(v.labels, labels, n_classes=build["n_classes"], ignore_zero=True)
                     results[v.identifier] = d
@@ -408,6 +485,16 @@ def run(args):
                 for c in range(1, build["n_classes"]):
                     f.write("%s,%d,%.6f,%.6f,%.6f,%.6f,%d,%d\n" % (k, c, s["hd"][c], s["hd95"][c], s["assd"][c], s["nsd"][c],
                                                                    int(s["n_pred_border"][c]), int(s["n_truth_border"][c])))
+    if rank == 0 and unc_rows:                          # one row per (image, class of the saved map); _correct / _wrong: with labels
+        os.makedirs(os.path.join(out_dir, "csv"), exist_ok=True)
+        cols = ["n", "mean_entropy", "mean_mi", "mean_agreement"]
+        cols = cols + [c + g for g in ("_correct", "_wrong") for c in cols]
+        with open(os.path.join(out_dir, "csv", "uncertainty_results.csv"), "w") as f:
+            f.write("image,class," + ",".join(cols) + "\n")
+            for k, t in unc_rows.items():
+                for c in range(build["n_classes"]):
+                    f.write("%s,%d,%s\n" % (k, c, ",".join("" if col not in t else ("%.6f" if col.startswith("mean_") else "%d") % t[col][c]
+                                                            for col in cols)))
     return results
 
 
@@ -418,6 +505,7 @@ def entry_func(args=None):
     from .common import relaunch_per_gpu, await_pids
     if args.wait_for and "RANK" not in os.environ:        # (once, in the launching process: utils.py:337-375)
         await_pids(args.wait_for)
+    uncertainty_plan(args)                               # (--num_GPUs N > 1 is refused here, before any process is started)
     relaunch_per_gpu("predict", argv, args.num_GPUs)     # --num_GPUs N > 1: one process per GPU (returns inside a torchrun job)
     run(args)
 

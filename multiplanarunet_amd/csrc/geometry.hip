@@ -1018,6 +1018,199 @@ __global__ __launch_bounds__(256) void map_fuse_linear_kernel(FuseArgs a) {
     }
 }
 
+// ---- uncertainty of the fusion: what the fused kernels hold per voxel and throw away ------------------------------------------
+// Per voxel, from the V view vectors x_v (what map_view_nearest / map_view_linear give) and the fused vector p:
+//   entropy   = Hn(p)                                        Hn(q) = -sum_k (q_k / s) ln(q_k / s) / ln K,  s = sum_k q_k
+//   mi        = max(0, Hn(mean_v x^_v) - mean_v Hn(x^_v))    x^_v = x_v / sum_k x_v[k]  (Hn(x^_v) = Hn(x_v): Hn normalises)
+//   agreement = #{v : argmax x_v == argmax p}                first maximum, the strict > of softmax_argmax_store
+// Terms with q_k <= 0 contribute 0, s <= 0 gives 0 (and x^_v = 0), K = 1 gives 0. f32 throughout: at most 16 terms
+// r ln r (each <= 1/e, logf a few ulp), so Hn carries ~1e-6 and mi, a difference of two, twice that.
+// The view's argmax is 4 bits: the votes of up to 16 views are one 64-bit word until the fused label is known.
+// normalised vector r = q / s (0 when s <= 0) and Hn(q)
+template <int K>
+__device__ __forceinline__ float entropy_norm(const float (&q)[K], float (&r)[K]) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) s = s + q[k];
+    const bool ok = s > 0.f;
+    float h = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        r[k] = ok ? q[k] / s : 0.f;
+        if (r[k] > 0.f) h = h - r[k] * logf(r[k]);
+    }
+    if (K == 1) return 0.f;
+    const float ln_k = (float)__builtin_log((double)K);
+    return fminf(fmaxf(h / ln_k, 0.f), 1.f);
+}
+template <int K>
+__device__ __forceinline__ int first_max(const float (&q)[K]) {
+    int best = 0; float bv = q[0];
+#pragma unroll
+    for (int k = 1; k < K; ++k) if (q[k] > bv) { bv = q[k]; best = k; }
+    return best;
+}
+
+struct UncArgs { FuseArgs f; float* entropy; float* mi; uint8_t* agreement; };
+
+// voxels of a lane (z, z + 16, ...): four gathers in flight as in map_fuse_kernel while two K-wide accumulators per voxel
+// fit (K <= 4), two up to K = 8, one above (and one for the linear form, as map_fuse_linear_kernel)
+constexpr int unc_voxels(int K, bool linear) { return linear ? 1 : (K <= 4 ? 4 : (K <= 8 ? 2 : 1)); }
+static_assert(MAX_VIEWS * 4 <= 64 && 16 <= (1 << 4), "a view's argmax is a nibble of the 64-bit vote word");
+
+// The exact fused kernel (map_fuse_kernel / map_fuse_linear_kernel: same lookups, same accumulation, same finish, so
+// probs and labels are the bytes those give) that also keeps, per voxel, the sum of the normalised view vectors, the sum
+// of the view entropies and the views' votes. One workgroup = one 4 x 4 x (16 UZ) brick (no grid-stride loop: its state
+// costs the scalar registers that hold a view's parameters).
+template <int K, bool LINEAR>
+__global__ __launch_bounds__(256) void map_fuse_uncertainty_kernel(UncArgs ua) {
+    constexpr int UZ = unc_voxels(K, LINEAR);
+    const FuseArgs& a = ua.f;
+    const GridDev& g = a.grid;
+    const int nz = (g.Z + BRZ * UZ - 1) / (BRZ * UZ), ny = (g.Y + BRY - 1) / BRY;
+    const long blk = blockIdx.x;
+    const int bz = (int)(blk % nz), by = (int)((blk / nz) % ny), bx = (int)(blk / ((long)nz * ny));
+    const int vx = bx * BRX + (threadIdx.x >> 6);
+    const int vy = by * BRY + ((threadIdx.x >> 4) & 3);
+    const int vz0 = bz * BRZ * UZ + (threadIdx.x & 15);
+    if (vx >= g.X || vy >= g.Y) return;
+    double rx[UZ], ry[UZ], rz[UZ];
+    float z[UZ][K], m[UZ][K], hs[UZ];
+    unsigned long long votes[UZ];
+#pragma unroll
+    for (int u = 0; u < UZ; ++u) {
+        voxel_real(g, vx, vy, vz0 + 16 * u, rx[u], ry[u], rz[u]);
+#pragma unroll
+        for (int k = 0; k < K; ++k) { z[u][k] = 0.f; m[u][k] = 0.f; }
+        hs[u] = 0.f; votes[u] = 0ull;
+    }
+#pragma unroll 1
+    for (int v = 0; v < a.V; ++v) {
+        const ViewDev& vw = a.views[v];
+        long off[UZ];
+        if (!LINEAR) {                                    // map_fuse_kernel's lookups: closed form, ONE copy of the exact search
+            unsigned risky = 0;
+#pragma unroll
+            for (int u = 0; u < UZ; ++u) {
+                double qx, qy, qz;
+                mat3_apply(vw.invb, rx[u], ry[u], rz[u], qx, qy, qz);
+                int n0, n1, n2; bool o0, o1, o2;
+                const bool f0 = nearest_fast(vw.g, qx, n0, o0), f1 = nearest_fast(vw.g, qy, n1, o1), f2 = nearest_fast(vw.offs, qz, n2, o2);
+                if (!(f0 && f1 && f2)) risky |= 1u << u;
+                off[u] = (o0 || o1 || o2) ? -1 : (((long)n2 * vw.dim + n0) * vw.dim + n1) * K;
+            }
+            if (__builtin_expect(risky != 0, 0)) {
+#pragma unroll 1
+                for (int u = 0; u < UZ; ++u) {
+                    if (!((risky >> u) & 1u)) continue;
+                    double px = rx[0], py = ry[0], pz = rz[0];          // (selects, not a lane-indexed array: no scratch)
+#pragma unroll
+                    for (int t = 1; t < UZ; ++t) if (t == u) { px = rx[t]; py = ry[t]; pz = rz[t]; }
+                    int pl;
+                    const long o = view_lookup(vw, px, py, pz, K, pl);
+#pragma unroll
+                    for (int t = 0; t < UZ; ++t) if (t == u) off[t] = o;
+                }
+            }
+        }
+        float w[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) w[k] = fuse_weight(a.W, v * K + k, a.sum_fusion);
+#pragma unroll
+        for (int u = 0; u < UZ; ++u) {
+            float x[K], r[K];
+            if (LINEAR) {
+                view_linear<K>(vw, rx[u], ry[u], rz[u], 0, vw.P, x);
+            } else {
+                __builtin_memcpy(x, vw.pred + (off[u] >= 0 ? off[u] : 0), K * sizeof(float));
+                if (off[u] < 0) {
+#pragma unroll
+                    for (int k = 0; k < K; ++k) x[k] = background(k);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k) z[u][k] = fuse_add(z[u][k], w, k, x[k], a.sum_fusion);
+            hs[u] = hs[u] + entropy_norm<K>(x, r);
+#pragma unroll
+            for (int k = 0; k < K; ++k) m[u][k] = m[u][k] + r[k];
+            votes[u] |= (unsigned long long)first_max<K>(x) << (4 * v);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < UZ; ++u) {
+        const int vz = vz0 + 16 * u;
+        if (vz >= g.Z) continue;
+        const long t = ((long)vx * g.Y + vy) * g.Z + vz;
+        fuse_add_bias<K>(z[u], a.b, a.sum_fusion);
+        softmax_argmax_store<K>(z[u], !a.sum_fusion, t, a.probs, a.labels);     // z is the fused vector p from here
+        float r[K];
+        if (ua.entropy) ua.entropy[t] = entropy_norm<K>(z[u], r);
+        if (ua.mi) ua.mi[t] = fmaxf(entropy_norm<K>(m[u], r) - hs[u] / (float)a.V, 0.f);
+        if (ua.agreement) {
+            const int best = first_max<K>(z[u]);
+            int n = 0;
+            for (int v = 0; v < a.V; ++v) n += (int)((votes[u] >> (4 * v)) & 15ull) == best ? 1 : 0;
+            ua.agreement[t] = (uint8_t)n;
+        }
+    }
+}
+
+// ---- table of the maps: per class of a label map and group (all / correct / wrong against a truth map) the voxel count and the
+// sums of entropy, mi and agreement. Integer sums only, so the order of the atomics cannot show: entropy and mi (clamped to
+// [0, 1]; NaN counts as 0) in 2^-32 fixed point, at most n 2^32 < 2^63 for n < 2^31. A workgroup owns 16384 consecutive voxels, a
+// lane every 256th of them; a lane keeps the sums of its current (class, group) in registers and adds them to the
+// workgroup's LDS table when that changes (label maps are coherent: a few LDS atomics per lane), the workgroup adds its table
+// to the global one at the end.
+constexpr int UT_CHUNK = 256 * 64;
+__device__ __forceinline__ unsigned long long unc_fixed(float v) {
+    return (unsigned long long)((double)fminf(fmaxf(v, 0.f), 1.f) * 4294967296.0);
+}
+__global__ __launch_bounds__(256) void uncertainty_table_kernel(const uint8_t* __restrict__ labels, const uint8_t* __restrict__ truth,
+                                                                const float* __restrict__ entropy, const float* __restrict__ mi,
+                                                                const uint8_t* __restrict__ agreement, long n, int K,
+                                                                unsigned long long* acc) {          // acc [K][2][4]
+    __shared__ unsigned long long s[16 * 2 * 4];
+    for (int i = threadIdx.x; i < K * 8; i += 256) s[i] = 0ull;
+    __syncthreads();
+    const long lo = (long)blockIdx.x * UT_CHUNK, hi = lo + UT_CHUNK < n ? lo + UT_CHUNK : n;
+    int key = -1;
+    unsigned long long q[4] = {0ull, 0ull, 0ull, 0ull};
+    for (long i = lo + threadIdx.x; i < hi; i += 256) {
+        const int c = labels[i];
+        const int k = c < K ? 2 * c + ((truth && truth[i] != c) ? 1 : 0) : -1;
+        if (k != key) {
+            if (key >= 0) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (q[j]) atomicAdd(&s[key * 4 + j], q[j]);
+            }
+            key = k;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) q[j] = 0ull;
+        }
+        q[0] += 1ull;
+        if (entropy) q[1] += unc_fixed(entropy[i]);
+        if (mi) q[2] += unc_fixed(mi[i]);
+        if (agreement) q[3] += (unsigned long long)agreement[i];
+    }
+    if (key >= 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (q[j]) atomicAdd(&s[key * 4 + j], q[j]);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < K * 8; i += 256) if (s[i]) atomicAdd(&acc[i], s[i]);
+}
+// table f64 [K][3][4]: group 0 = all, 1 = correct, 2 = wrong (1 and 2 are zero without a truth map); count, sum entropy, sum mi, sum agreement
+__global__ __launch_bounds__(256) void uncertainty_table_finish_kernel(const unsigned long long* acc, int K, int has_truth, double* table) {
+    const int i = threadIdx.x;
+    if (i >= K * 4) return;
+    const int c = i >> 2, j = i & 3;
+    const double sc = (j == 1 || j == 2) ? 1.0 / 4294967296.0 : 1.0;
+    const unsigned long long a0 = acc[(c * 2 + 0) * 4 + j], a1 = acc[(c * 2 + 1) * 4 + j];
+    table[(c * 3 + 0) * 4 + j] = (double)(a0 + a1) * sc;
+    table[(c * 3 + 1) * 4 + j] = has_truth ? (double)a0 * sc : 0.0;
+    table[(c * 3 + 2) * 4 + j] = has_truth ? (double)a1 * sc : 0.0;
+}
+
 template <int K>
 __global__ __launch_bounds__(256) void fusion_forward_kernel(const float* __restrict__ x, long n, int V,
                                                              const float* W, const float* b,
@@ -1369,6 +1562,31 @@ static int make_fuse_args(const char* who, const mpu_voxel_grid* grid, const mpu
     a.V = n_views; a.W = d_W; a.b = d_b; a.sum_fusion = sum_fusion; a.probs = d_probs; a.labels = d_labels;
     return MPU_OK;
 }
+// mpu_map_fuse_views_uncertainty: probs and labels may both be NULL, one of the three maps is required; n_classes is an
+// argument error here (MPU_EINVAL), checked with the rest before the first HIP call
+static int make_unc_args(const char* who, const mpu_voxel_grid* grid, const mpu_view_pred* views, int n_views, int n_classes,
+                         const float* d_W, const float* d_b, int sum_fusion, float* d_probs, uint8_t* d_labels,
+                         float* d_entropy, float* d_mi, uint8_t* d_agreement, UncArgs& ua) {
+    FuseArgs& a = ua.f;
+    MPU_REQUIRE_WHO(grid && views, "null argument");
+    MPU_REQUIRE_WHO(n_classes >= 1 && n_classes <= 16, "n_classes must be in 1..16");
+    MPU_REQUIRE_WHO(n_views >= 1 && n_views <= MAX_VIEWS, "n_views must be in 1..16");
+    MPU_REQUIRE_WHO(sum_fusion || (d_W && d_b), "W and b required unless sum_fusion");
+    MPU_REQUIRE_WHO(d_entropy || d_mi || d_agreement, "no map requested");
+    MPU_REQUIRE_WHO(grid->shape[0] >= 1 && grid->shape[1] >= 1 && grid->shape[2] >= 1, "empty voxel grid");
+    to_grid(*grid, a.grid);
+    for (int v = 0; v < n_views; ++v) {
+        MPU_REQUIRE_WHO(views[v].d_pred && views[v].d_g && views[v].d_offsets, "null view field");
+        MPU_REQUIRE_WHO(views[v].dim >= 2 && views[v].n_planes >= 2, "view needs dim>=2, planes>=2");
+        to_view(views[v], a.views[v]);
+    }
+    a.V = n_views; a.W = d_W; a.b = d_b; a.sum_fusion = sum_fusion; a.probs = d_probs; a.labels = d_labels;
+    ua.entropy = d_entropy; ua.mi = d_mi; ua.agreement = d_agreement;
+    return MPU_OK;
+}
+static long unc_grid(const GridDev& g, int uz) {              // one workgroup per brick
+    return (long)((g.X + BRX - 1) / BRX) * ((g.Y + BRY - 1) / BRY) * ((g.Z + BRZ * uz - 1) / (BRZ * uz));
+}
 #undef MPU_REQUIRE_WHO
 
 extern "C" {
@@ -1605,6 +1823,45 @@ int mpu_fusion_finalize(const float* d_z, int64_t n, int32_t n_classes, const fl
     if (n <= 0) return MPU_OK;
     MPU_DISPATCH_K(n_classes, (fusion_finalize_kernel<KK><<<dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream>>>(
                                    d_z, (long)n, d_b, sum_fusion, d_probs, d_labels)));
+    return launch_ok();
+}
+
+/* the exact fused back-mapping (nearest or linear) with the per-voxel uncertainty maps of the fusion */
+int mpu_map_fuse_views_uncertainty(const mpu_voxel_grid* grid, const mpu_view_pred* views, int32_t n_views,
+                                   int32_t n_classes, const float* d_W, const float* d_b, int32_t sum_fusion, int32_t linear,
+                                   float* d_probs, uint8_t* d_labels, float* d_entropy, float* d_mi, uint8_t* d_agreement,
+                                   void* stream) {
+    UncArgs ua;
+    { const int rc_ = make_unc_args("mpu_map_fuse_views_uncertainty", grid, views, n_views, n_classes, d_W, d_b, sum_fusion,
+                                    d_probs, d_labels, d_entropy, d_mi, d_agreement, ua); if (rc_) return rc_; }
+    { const int rc_ = sync_fast_switch(); if (rc_) return rc_; }
+    if (unc_grid(ua.f.grid, 1) >= (1L << 31)) return mpu::fail(MPU_EUNSUPPORTED, "%s", "mpu_map_fuse_views_uncertainty: more than 2^31 - 1 bricks of 4 x 4 x 16 voxels");
+    if (sched_log_on()) sched_note("map_fuse uncertainty views=%d K=%d linear=%d", n_views, n_classes, linear ? 1 : 0);
+    hipStream_t st = (hipStream_t)stream;
+    if (linear) { MPU_DISPATCH_K(n_classes, (map_fuse_uncertainty_kernel<KK, true><<<dim3((unsigned)unc_grid(ua.f.grid, unc_voxels(KK, true))), dim3(256), 0, st>>>(ua))); }
+    else        { MPU_DISPATCH_K(n_classes, (map_fuse_uncertainty_kernel<KK, false><<<dim3((unsigned)unc_grid(ua.f.grid, unc_voxels(KK, false))), dim3(256), 0, st>>>(ua))); }
+    return launch_ok();
+}
+
+size_t mpu_uncertainty_table_scratch_bytes(int64_t n, int32_t n_classes) {
+    (void)n;                                                   /* one [K][2][4] table of 64-bit sums, whatever n */
+    return (n_classes >= 1 && n_classes <= 16) ? (size_t)n_classes * 2 * 4 * sizeof(unsigned long long) : 0;
+}
+
+int mpu_uncertainty_table(const uint8_t* d_labels, const uint8_t* d_truth, const float* d_entropy, const float* d_mi,
+                          const uint8_t* d_agreement, int64_t n, int32_t n_classes, double* d_table, void* d_scratch, void* stream) {
+    MPU_REQUIRE(n_classes >= 1 && n_classes <= 16, "mpu_uncertainty_table: n_classes must be in 1..16");
+    MPU_REQUIRE(n >= 0 && n < (1LL << 31), "mpu_uncertainty_table: n must be in 0..2^31 - 1");
+    MPU_REQUIRE(d_labels && d_table && d_scratch, "mpu_uncertainty_table: null argument");
+    MPU_REQUIRE((uintptr_t)d_table % 8 == 0 && (uintptr_t)d_scratch % 8 == 0,
+                "mpu_uncertainty_table: d_table and d_scratch must be aligned to 8 bytes");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* acc = (unsigned long long*)d_scratch;
+    MPU_CHECK_HIP(hipMemsetAsync(acc, 0, mpu_uncertainty_table_scratch_bytes(n, n_classes), st));
+    if (n > 0)
+        uncertainty_table_kernel<<<dim3((unsigned)((n + UT_CHUNK - 1) / UT_CHUNK)), dim3(256), 0, st>>>(
+            d_labels, d_truth, d_entropy, d_mi, d_agreement, (long)n, n_classes, acc);
+    uncertainty_table_finish_kernel<<<dim3(1), dim3(256), 0, st>>>(acc, n_classes, d_truth ? 1 : 0, d_table);
     return launch_ok();
 }
 

@@ -24,7 +24,7 @@ def per_view_evaluation(pred, true, mapped_pred, mapped_true, n_classes):
 
 def multi_view_predict(model, volume, views, dim, real_space_span, fusion_model=None,
                        sum_fusion=False, batch_size=None, n_planes="same+20",
-                       want_probs=True, timings=None, per_view_eval=None, map_method="nearest"):
+                       want_probs=True, timings=None, per_view_eval=None, map_method="nearest", uncertainty=None):
     """
     Returns (merged f32 [X,Y,Z,K] or None, merged_map u8 [X,Y,Z]).
     per_view_eval: None, or dict(eval_prob=float, n_classes=int, report=callable(view_index, view, view_dices, mapped_dices,
@@ -38,6 +38,9 @@ def multi_view_predict(model, volume, views, dim, real_space_span, fusion_model=
     per-view evaluation and in the final fuse alike (interpolation.map_real_space_pred). Fusion weights should have been trained with
     the method used here.
     fusion_model: object with .W (V,K) and .b (1,K) device tensors (FusionModel) or None with sum_fusion.
+    uncertainty: None, or a dict (optionally with key "maps": names out of "entropy", "mi", "agreement"; default all three): the final
+    fuse goes through uncertainty.fuse_with_uncertainty -- the exact fused kernel, same probabilities and labels -- and the dict
+    is filled with the per-voxel device tensors under those names.
     """
     if fusion_model is None and not sum_fusion:
         raise ValueError("need a fusion model unless sum_fusion")
@@ -79,8 +82,14 @@ def multi_view_predict(model, volume, views, dim, real_space_span, fusion_model=
     W = b = None
     if not sum_fusion:
         W, b = fusion_model.W, fusion_model.b
-    probs, labels = map_and_fuse(volume, view_preds, W, b, sum_fusion=sum_fusion,
-                                 want_probs=want_probs, want_labels=True, method=map_method)
+    if uncertainty is not None:
+        from .uncertainty import fuse_with_uncertainty, MAPS
+        probs, labels, maps = fuse_with_uncertainty(volume, view_preds, W, b, sum_fusion=sum_fusion, method=map_method,
+                                                    want_probs=want_probs, maps=uncertainty.get("maps") or MAPS)
+        uncertainty.update(maps)
+    else:
+        probs, labels = map_and_fuse(volume, view_preds, W, b, sum_fusion=sum_fusion,
+                                     want_probs=want_probs, want_labels=True, method=map_method)
     if timings is not None:
         f1.record()
         torch.cuda.synchronize()
